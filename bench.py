@@ -17,13 +17,19 @@ taken.  Beside it, "replicas" times every rank stepping its own C3 arena
 (independent replicas, weak scaling, no collective in the data path).
 
 The timed steps are issued with aigar_run: each step (policy + tick +
-observation) is one hipGraph replay.  The per-phase breakdown and the roofline
-kernel's duration come from the following steps issued as separate calls.
+observation) is one hipGraph replay.
 
-Prints ONE JSON line (rank 0).  Extra objects: "roofline" for the dominant
-kernel (k_observe, HIP-event timed live on the stepper's stream) and
-"cpu_baseline" (the C oracle, i.e. a single-thread CPU port of the reference,
-timed on a bounded sample of the same workload on this host).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps
+steps and prints the headline figures only.  --dump-outputs DIR also writes what
+the last timed step returned (DIR/obs.npy: every bot's observation row;
+DIR/player_stats.npy; finite numbers only, a dead bot's NaN entries written as
+0 and counted per row in DIR/<name>_nonfinite.npy) for output-for-output
+comparison of two builds: the same arguments give the same inputs.  --full adds every side measurement: the
+per-phase breakdown and the roofline kernel's duration (the following steps
+issued as separate calls; "roofline" for the dominant kernel k_observe,
+HIP-event timed live on the stepper's stream), "world", "pixels", "batched",
+"greedy" and "cpu_baseline" (the C oracle, i.e. a single-thread CPU port of the
+reference, timed on a bounded sample of the same workload on this host).
 """
 import argparse
 import json
@@ -410,6 +416,34 @@ def c4_leg(args, name, rank, world, local, seed, dist, backend):
             "per_tile": tiles_all}
 
 
+DUMP_BUDGET = 64 << 20  # --dump-outputs: bytes in all
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET, seed=0):
+    """Write each array as path/<name>.npy (float64 / float32 kept, anything else
+    as float64).  Together they stay within `budget` bytes: an array past its
+    equal share is cut to a fixed, seeded sample of its rows (sorted, so the same
+    rows in the same order every run).  Every file holds finite numbers only: the
+    stepper answers NaN for what the reference answers None (the observation row
+    and the view of a dead bot), so each NaN / inf entry is written as 0 and
+    path/<name>_nonfinite.npy keeps, per row, how many entries were -- two builds
+    compare equal only if they agree on both files."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        # (room for the per-row counts and the two .npy headers)
+        share = budget // max(1, len(arrays)) - 8 * a.shape[0] - 8192
+        if a.nbytes > share:
+            rows = max(1, share // max(1, a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(seed).choice(a.shape[0], rows, replace=False))]
+        bad = ~np.isfinite(a)
+        np.save(os.path.join(path, name + "_nonfinite.npy"),
+                bad.reshape(a.shape[0], -1).sum(axis=1).astype(np.float64))
+        np.save(os.path.join(path, name + ".npy"), np.where(bad, a.dtype.type(0), a))
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` (N > 1) outside torch.distributed.run: start the
     N ranks (one process per GPU) the way the driver does, as a CHILD process --
@@ -440,18 +474,28 @@ def main():
     ap.add_argument("--batched-arenas", type=int, default=16,
                     help="also time this many independent arenas of the same workload stepped together on "
                          "the GPU (reported under 'batched', never as 'value'); 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (per-phase breakdown, roofline, world summary, pixels, "
+                         "batched arenas, greedy line, CPU baseline); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned as DIR/<name>.npy (obs: every "
+                         "bot's observation row; player_stats; NaN entries, a dead bot's, as 0 and counted per row "
+                         "in <name>_nonfinite.npy), at most 64 MB in all; ranks of N > 1 write "
+                         "<name>_rank<r>.npy for their replica")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pixels", action="store_true", help="skip the pixel-observation side measurement")
+    ap.add_argument("--no-pixels", action="store_true", help="--full: skip the pixel-observation side measurement")
     ap.add_argument("--no-c4", action="store_true",
                     help="N > 1: report the replicas as value instead of the tiled single arena (C4)")
     ap.add_argument("--profile-run", action="store_true",
-                    help="only the warm-up and the timed graph replays (for rocprofv3: one call per step)")
+                    help="only the warm-up and the timed graph replays even with --full (for rocprofv3: one call "
+                         "per step)")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--policy", default="random", choices=["random", "greedy"],
                     help="synthetic population: Philox random actions, or the reference's Greedy bots "
                          "(bot.py:579-633, ENABLE_GREEDY_SPLIT) on the device")
     args = ap.parse_args()
+    side = args.full and not args.profile_run  # the side measurements: never in a plain run
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -501,7 +545,7 @@ def main():
     run(args.warmup)
     torch.cuda.synchronize()
     stp.sync()
-    w0 = stp.counters()
+    w0 = stp.counters() if args.full else None
     replicas.barrier(dist)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -513,10 +557,15 @@ def main():
     stp.sync()  # raises on any device-side capacity error
     elapsed = replicas.max_over_ranks(dist, elapsed, device="cuda" if backend == "nccl" else None)
     value = replicas.job_throughput(bots * args.steps, world, elapsed)
-    st = stp.get_state()
-    stats = stp.player_stats()
-    work = stp.counters()
-    ticks_timed = max(1, work["ticks"] - w0["ticks"])
+    if args.dump_outputs:  # what the caller of the timed path holds after its last step
+        tag = "_rank%d" % rank if world > 1 else ""
+        dump_outputs(args.dump_outputs, {"obs" + tag: obs.cpu().numpy(), "player_stats" + tag: stp.player_stats()},
+                     seed=args.seed)
+    if args.full:
+        st = stp.get_state()
+        stats = stp.player_stats()
+        work = stp.counters()
+        ticks_timed = max(1, work["ticks"] - w0["ticks"])
     out = {
         "metric": "env-steps/sec at 4096 bots x 100k pellets; 1/2/4/8 MI355X scaling",
         "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -532,7 +581,7 @@ def main():
                    "policy": args.policy,
                    "parallelism": "replicas%d" % world if world > 1 else "single-gpu"},
     }
-    if not args.profile_run:
+    if side:
         # per-phase breakdown and the roofline kernel's duration: the next
         # min(steps, 50) steps issued as separate calls, HIP events on the stepper's stream
         stp.profile(True)
@@ -566,13 +615,14 @@ def main():
                              "traffic: PMC bytes of all the step's kernels per step"}}
         out["breakdown_ms_per_step"] = {"policy": pol_ms / max(1, pol_n), "tick": tick_ms / max(1, tick_n),
                                         "observe": obs_ms / max(1, obs_n)}
-    out["world"] = {"pellets": st["n_pellets"], "cells": st["n_cells"], "viruses": st["n_viruses"],
-                    "blobs": st["n_blobs"], "alive_bots": int(np.sum(stats[:, 0] > 0)), "tick": int(st["tick"]),
-                    "mean_cell_mass": float(np.asarray(st["cells_f"])[:, 2].mean()) if st["n_cells"] else 0.0,
-                    "multi_cell_players": int(np.sum(np.asarray(st["players_i"])[:, 4] > 1)),
-                    "per_tick_in_timed_region": {k: round((work[k] - w0[k]) / ticks_timed, 3) for k in work
-                                                 if k != "ticks"}}
-    if not args.profile_run and not args.no_pixels:
+    if args.full:
+        out["world"] = {"pellets": st["n_pellets"], "cells": st["n_cells"], "viruses": st["n_viruses"],
+                        "blobs": st["n_blobs"], "alive_bots": int(np.sum(stats[:, 0] > 0)), "tick": int(st["tick"]),
+                        "mean_cell_mass": float(np.asarray(st["cells_f"])[:, 2].mean()) if st["n_cells"] else 0.0,
+                        "multi_cell_players": int(np.sum(np.asarray(st["players_i"])[:, 4] > 1)),
+                        "per_tick_in_timed_region": {k: round((work[k] - w0[k]) / ticks_timed, 3) for k in work
+                                                     if k != "ticks"}}
+    if side and not args.no_pixels:
         # RGBGenerator.get_cnn_inputRGB for every bot (side 42, uint8 RGB): a side line,
         side, reps = 42, 20  # not part of the env-step metric (the reference's CNN pixel mode is off by default)
         frames = torch.empty((bots, side, side, 3), dtype=torch.uint8, device="cuda")
@@ -588,12 +638,12 @@ def main():
         out["pixels"] = {"side": side, "dtype": "u8 rgb", "frames_per_s": bots / pix_s, "avg_launch_ms": pix_s * 1e3,
                          "output_GB_s": bots * side * side * 3 / pix_s / 1e9}
     stp.close()
-    if not args.profile_run and world == 1 and rank == 0:
+    if side and world == 1 and rank == 0:
         if args.batched_arenas > 1 and not args.arenas:
             out["batched"] = batched(name, args.batched_arenas, args.policy, ps, pe, args.seed, local)
         if args.policy == "random" and name == "c3":  # the same start with the reference's Greedy bots
             out["greedy"] = greedy_side(name, args.seed, local)
-    if world == 1 and name == "c3" and os.environ.get("AIGAR_C4_SELFTEST") and not args.profile_run:
+    if world == 1 and name == "c3" and os.environ.get("AIGAR_C4_SELFTEST") and side:
         # the C4 code path on one GPU: the whole field as one forced tile over a 1-rank RCCL communicator
         out["c4_selftest"] = c4_leg(args, name, rank, world, local, args.seed, dist, "nccl")
     if not args.no_c4 and world > 1 and name == "c3":
@@ -606,7 +656,7 @@ def main():
         out["config"]["workload"] = c4["workload"]
         out["config"]["parallelism"] = "tiles%dx%d" % replicas_tiles(world)
         out["c4"] = c4
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.profile_run:  # (N = 1 only)
+    if rank == 0 and world == 1 and not args.no_cpu_baseline and side:  # (N = 1 only)
         out["cpu_baseline"] = cpu_baseline(name, args.cpu_budget, policy=args.policy)
         if name == "c3" and args.policy == "random":  # (the file times bench.py's random policy)
             ref_py = reference_python(name)

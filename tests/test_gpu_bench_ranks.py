@@ -34,7 +34,7 @@ def test_two_rank_bench_line(launch):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", "3",
-            "--no-cpu-baseline", "--no-pixels", "--batched-arenas", "0"]
+            "--full", "--no-cpu-baseline", "--no-pixels", "--batched-arenas", "0"]
     if launch == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                "--master-addr", "127.0.0.1", "--master-port", str(_free_port())] + tail

@@ -12,7 +12,7 @@ for i in $(seq $N); do
     v=$(printf "\\x$(printf %x $((65 + k)))"); k=$((k + 1))
     envv="AIGAR_SO=${so:+$R/$so}"
     case "$so" in env:*) envv="${so#env:}";; esac
-    env "$envv" timeout -k 10 120 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-pixels \
+    env "$envv" timeout -k 10 120 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-pixels \
       --batched-arenas 0 --no-c4 $AB_ARGS > $O/${TAG}_abn_${v}$i.json 2>/dev/null || { echo "abn $v failed"; exit 1; }
     python3 -c "import json;d=json.loads(open('$O/${TAG}_abn_${v}$i.json').read().strip().splitlines()[-1]);b=d['breakdown_ms_per_step'];print('$v', round(d['value']/1e6,2), 'M/s  ms/step %.4f tick %.4f obs %.4f' % (d['ms_per_step'], b['tick'], b['observe']))"
   done

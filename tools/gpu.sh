@@ -35,10 +35,10 @@ for S in "$@"; do
         > $O/${TAG}_pytest_gpu.log 2>&1 || { rc=$?; grep -E "FAILED|ERROR|^E  " $O/${TAG}_pytest_gpu.log | head -20; fail suite $rc; }
       tail -1 $O/${TAG}_pytest_gpu.log ;;
     bench)
-      timeout -k 10 400 python -u bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || fail bench $? $O/${TAG}_bench.err
+      timeout -k 10 400 python -u bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || fail bench $? $O/${TAG}_bench.err
       tail -c 400 $O/${TAG}_bench.json ;;
     quick)
-      timeout -k 10 200 python -u bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-pixels --batched-arenas 0 \
+      timeout -k 10 200 python -u bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-pixels --batched-arenas 0 \
         > $O/${TAG}_quick.json 2> $O/${TAG}_quick.err || fail quick $? $O/${TAG}_quick.err
       python3 -c "import json;d=json.loads(open('$O/${TAG}_quick.json').read().strip().splitlines()[-1]);b=d['breakdown_ms_per_step'];print('quick %.2f M/s ms/step %.4f tick %.4f obs %.4f' % (d['value']/1e6, d['ms_per_step'], b['tick'], b['observe']))" ;;
     prof) prof prof $R/bench.py --profile-run --steps 200 --warmup 20 ;;
@@ -63,7 +63,7 @@ for S in "$@"; do
     gloo:*)
       N=${S#gloo:}
       AIGAR_DIST_BACKEND=gloo timeout -k 10 400 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-        --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --gpus $N --steps 50 --warmup 10 \
+        --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --full --gpus $N --steps 50 --warmup 10 \
         --no-cpu-baseline --no-pixels --batched-arenas 0 > $O/${TAG}_gloo$N.json 2> $O/${TAG}_gloo$N.err \
         || fail "gloo $N" $? $O/${TAG}_gloo$N.err
       tail -c 300 $O/${TAG}_gloo$N.json ;;
@@ -72,7 +72,7 @@ for S in "$@"; do
       for i in $(seq $N); do
         for v in A B; do
           so=""; [ $v = B ] && so=$R/$B
-          AIGAR_SO=$so timeout -k 10 120 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-pixels \
+          AIGAR_SO=$so timeout -k 10 120 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-pixels \
             --batched-arenas 0 --no-c4 $AB_ARGS > $O/${TAG}_ab_${v}$i.json 2>/dev/null || fail "ab $v" $?
           python3 -c "import json;d=json.loads(open('$O/${TAG}_ab_${v}$i.json').read().strip().splitlines()[-1]);b=d['breakdown_ms_per_step'];print('$v', round(d['value']/1e6,2), 'M/s  ms/step %.4f tick %.4f obs %.4f' % (d['ms_per_step'], b['tick'], b['observe']))"
         done
