@@ -78,6 +78,7 @@ def load(build_if_missing=False):
         "aigar_create": [C.POINTER(_abi.Config), C.POINTER(vp)],
         "aigar_destroy": [vp],
         "aigar_reset": [vp, u64],
+        "aigar_reset_arenas": [vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), i32],
         "aigar_set_commands": [vp, vp, i32],
         "aigar_policy_random": [vp, C.c_double, C.c_double, u64],
         "aigar_step": [vp, i32],
@@ -169,9 +170,6 @@ class Stepper:
         return r
 
     def close(self):
-        if getattr(self, "_one", None) is not None:
-            self._one.close()
-            self._one = None
         if getattr(self, "h", None):
             self.L.aigar_destroy(self.h)
             self.h = None
@@ -309,18 +307,20 @@ class Stepper:
     def policy_random_bots(self):
         self._chk(self.L.aigar_policy_random_bots(self.h))
 
+    def reset_arenas(self, arenas, seeds):
+        """Field.reset of the listed (distinct) arenas, arena arenas[k] becoming the world a
+        one-arena handle gets from reset(seeds[k]); their bots reset as by load_state, the
+        other arenas untouched.  Kernels on the stepper's stream: no host round trip."""
+        a = np.ascontiguousarray(arenas, np.int32).reshape(-1)
+        s = np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], np.uint64).reshape(-1)
+        if len(a) != len(s):
+            raise ValueError("reset_arenas: %d arenas, %d seeds" % (len(a), len(s)))
+        self._chk(self.L.aigar_reset_arenas(self.h, a.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            s.ctypes.data_as(C.POINTER(C.c_uint64)), len(a)))
+
     def reset_arena(self, arena, seed):
-        """Field.reset of ONE arena of a batched handle (a fresh world keyed by seed;
-        that arena's bots reset as by load_state), the others untouched."""
-        if self.A == 1:
-            return self.reset(seed)
-        c = _abi.Config()
-        C.memmove(C.byref(c), C.byref(self.cfg), C.sizeof(_abi.Config))
-        c.n_arenas = 1
-        if getattr(self, "_one", None) is None:
-            self._one = Stepper(c)
-        self._one.reset(seed)
-        self.load_state(self._one.get_state(0), arena)
+        """reset_arenas for ONE arena (for n_arenas == 1: the world of reset(seed))."""
+        self.reset_arenas([arena], [seed])
 
     def observe_pixels(self, side=42, color_seed=0, rgb=True, out=None):
         """RGBGenerator.get_cnn_inputRGB for every player (rgbGenerator.py:95-110):

@@ -26,6 +26,7 @@ void launch_tile_cmd_apply(const Dev &d, hipStream_t s, int box_recs);
 void launch_pel_gather(const Dev &d, hipStream_t s, int a);
 void launch_tile_apply(const Dev &d, hipStream_t s, int box_recs, int first);
 void launch_reset(const Dev &d, hipStream_t s, uint64_t seed);
+void launch_reset_arenas(const Dev &d, hipStream_t s, const int *al, const uint64_t *seeds, int n);
 void launch_observe(const Dev &d, hipStream_t s, void *out, int dtype, uint32_t epoch,
                     const uint8_t *mask = nullptr, int greedy_next = -1);
 bool observe_fuses_greedy(const Dev &d);
@@ -116,6 +117,15 @@ struct aigar_handle {
   int n_greedy = 0, n_random = 0;  // role counts (aigar_set_roles)
   aigar_env_params envp{};
   void *d_obs = nullptr;
+  // aigar_reset_arenas: the call's arena and seed lists, [n_arenas] each.  The
+  // kernels read the device copies; the async copies read pinned host slots, a
+  // slot reused only once the copy that read it last is done (its event)
+  static constexpr int kResetSlots = 4;
+  int *d_rlist = nullptr;
+  uint64_t *d_rseed = nullptr;
+  char *h_reset = nullptr;  // kResetSlots x 16 A bytes ([A] seeds, [A] arenas), pinned
+  hipEvent_t ev_reset[kResetSlots] = {};
+  unsigned reset_calls = 0;
   void *d_pix = nullptr;  // host-destination staging for aigar_observe_pixels
   uint8_t *d_pix_ovf = nullptr;  // per player: frame left to the pixel kernel's second pass
   size_t pix_bytes = 0;
@@ -241,6 +251,10 @@ static void free_all(aigar_handle *h) {
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->ev_x) (void)hipEventDestroy(h->ev_x);
+  for (hipEvent_t &e : h->ev_reset)
+    if (e) (void)hipEventDestroy(e);
+  if (h->h_reset) (void)hipHostFree(h->h_reset);
+  h->h_reset = nullptr;
   if (h->tb_graph) (void)hipGraphExecDestroy(h->tb_graph);
   if (h->te_graph) (void)hipGraphExecDestroy(h->te_graph);
   if (h->tr_graph) (void)hipGraphExecDestroy(h->tr_graph);
@@ -491,13 +505,21 @@ extern "C" int aigar_create(const aigar_config *cfg, aigar_handle **out) {
   h->d_nnmask = dalloc<uint8_t>(h, NP);
   h->d_stats = dalloc<double>(h, NP * 5);
   h->d_obs = dalloc<double>(h, NP * (size_t)d.L);
-  ok = ok && h->scr_k && h->scr_v && h->d_cmd && h->d_stats && h->d_obs && h->d_mask && h->d_nnmask;
+  h->d_rlist = dalloc<int>(h, A);
+  h->d_rseed = dalloc<uint64_t>(h, A);
+  ok = ok && h->scr_k && h->scr_v && h->d_cmd && h->d_stats && h->d_obs && h->d_mask && h->d_nnmask && h->d_rlist &&
+       h->d_rseed;
 #ifndef AIGAR_NO_ARENA
   }
   h->arena_sizing = false;
   h->arena = nullptr;  // later dalloc calls (pixel buffers) allocate on their own
 #endif
   if (ok) (void)hipMemset(h->d_nnmask, 1, NP);  // every player is NN until aigar_set_roles
+  if (ok && !d.tiled) {  // (aigar_reset_arenas refuses tiled handles)
+    ok = hipHostMalloc((void **)&h->h_reset, aigar_handle::kResetSlots * A * 2 * sizeof(uint64_t),
+                       hipHostMallocDefault) == hipSuccess;
+    for (hipEvent_t &e : h->ev_reset) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+  }
   (void)hipEventCreate(&h->ev0);
   (void)hipEventCreate(&h->ev1);
   if (!ok) {
@@ -571,6 +593,40 @@ extern "C" int aigar_reset(aigar_handle *h, uint64_t seed) {
   launch_reset(d, h->stream, seed);
   HIPCHK(hipGetLastError());
   return check_device_errors(h);
+}
+
+extern "C" int aigar_reset_arenas(aigar_handle *h, const int32_t *arenas, const uint64_t *seeds, int n) {
+  if (!h) return fail("null handle");
+  const Dev &d = h->d;
+  if (d.tiled) return fail("reset_arenas: a tiled handle steps one arena across tiles (reset it with aigar_reset)");
+  if (n < 0) return fail("reset_arenas: n = %d is negative", n);
+  if (n > d.A) return fail("reset_arenas: n = %d arenas listed, the handle has %d", n, d.A);
+  if (n == 0) return 0;
+  if (!arenas || !seeds) return fail("reset_arenas: null list");
+  std::vector<char> seen(d.A, 0);
+  for (int k = 0; k < n; k++) {
+    const int a = arenas[k];
+    if (a < 0 || a >= d.A) return fail("reset_arenas: arena %d (entry %d) out of range [0, %d)", a, k, d.A);
+    if (seen[a]) return fail("reset_arenas: duplicate arena %d (entry %d)", a, k);
+    seen[a] = 1;
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const int slot = (int)(h->reset_calls++ % aigar_handle::kResetSlots);
+  HIPCHK(hipEventSynchronize(h->ev_reset[slot]));  // (done long ago, unless the caller issues resets back to back)
+  char *base = h->h_reset + (size_t)slot * d.A * 2 * sizeof(uint64_t);  // (slots stay 8-byte aligned)
+  uint64_t *hs = (uint64_t *)base;
+  int *ha = (int *)(base + (size_t)d.A * sizeof(uint64_t));
+  memcpy(hs, seeds, sizeof(uint64_t) * n);
+  for (int k = 0; k < n; k++) ha[k] = arenas[k];
+  HIPCHK(hipMemcpyAsync(h->d_rseed, hs, sizeof(uint64_t) * n, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->d_rlist, ha, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipEventRecord(h->ev_reset[slot], h->stream));
+  {
+    Mark m(h, "reset_arenas");
+    launch_reset_arenas(d, h->stream, h->d_rlist, h->d_rseed, n);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 extern "C" int aigar_set_commands(aigar_handle *h, const double *cmd, int on_device) {

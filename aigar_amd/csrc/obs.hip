@@ -1280,6 +1280,25 @@ __global__ void __launch_bounds__(256) k_player_fov(Dev d) { fov_cache_thread(d,
 void launch_player_fov(const Dev &d, hipStream_t s) {
   hipLaunchKernelGGL(k_player_fov, dim3((d.NP + 255) / 256), dim3(256), 0, s, d);
 }
+// ... of the players of the n listed arenas (aigar_reset_arenas).  The overflow
+// pool's epoch moves once per launch, as in fov_cache_thread (there by player 0's
+// thread, which this launch may not have: here by the first thread).
+__global__ void __launch_bounds__(256) k_player_fov_list(Dev d, const int *al, int n) {
+  const int i = GTID;
+  if (i == 0) *d.ob_epoch = 0x80000000u | ((*d.ob_epoch + 1) & 0x7FFFFFFFu);
+  if (i >= n * d.B) return;
+  const int a = al[i / d.B], gp = a * d.B + i % d.B;
+  if (!d.p_alive[gp]) return;
+  const Fov f = player_fov(d, gp);
+  d.p_fx[gp] = f.fx;
+  d.p_fy[gp] = f.fy;
+  d.p_fs[gp] = f.fs;
+  d.p_mass[gp] = f.mass;
+  if (f.rmax > 0) atomic_max_pos(&d.ctl[a].rmax_cell, f.rmax);
+}
+void launch_player_fov_list(const Dev &d, hipStream_t s, const int *al, int n) {
+  hipLaunchKernelGGL(k_player_fov_list, dim3((n * d.B + 255) / 256), dim3(256), 0, s, d, al, n);
+}
 // ---------------------------------------------------- pixel observation
 // RGBGenerator.get_cnn_inputRGB (rgbGenerator.py:95-110) for every player: a
 // white side x side frame, every pellet / blob / virus / player cell in the FOV

@@ -1610,16 +1610,23 @@ __device__ __forceinline__ void cgrid_place_player(const Dev &d, int gp, int n) 
 // closing update (k_pel_update) rewrites only the rows they touch.
 __device__ __forceinline__ int prow_entry(const Dev &d, int bx, int by) { return by * (d.cols + 1) + bx; }
 // staged record j: its rank in its bucket (tiles: -1 outside the held range)
-__global__ void k_prow_count(Dev d) {
-  const int gi = GTID;
-  if (gi >= d.A * d.Pcap) return;
-  const int a = gi / d.Pcap, j = gi - a * d.Pcap;
+__device__ __forceinline__ void prow_count(const Dev &d, int a, int j) {
+  const int gi = a * d.Pcap + j;
   ArenaCtl &c = d.ctl[a];
   if (j == 0) c.n_pel = 0;  // (k_prow_scan adds the rows' counts)
   if (j >= c.n_pnew) return;
   const PelRec r = d.pn[gi];
   const int bx = center_bucket_coord(r.x, d.cols), by = center_bucket_coord(r.y, d.cols);
   d.pel_rank[gi] = tile_holds_bucket(d, bx, by) ? atomicAdd(&d.pncnt[(size_t)a * d.PH1 + prow_entry(d, bx, by)], 1) : -1;
+}
+__global__ void k_prow_count(Dev d) {
+  const int gi = GTID;
+  if (gi < d.A * d.Pcap) prow_count(d, gi / d.Pcap, gi % d.Pcap);
+}
+// (the arena-listed variants, aigar_reset_arenas: staged record i % Pcap of arena al[i / Pcap])
+__global__ void k_prow_count_list(Dev d, const int *al, int n) {
+  const int i = GTID;
+  if (i < n * d.Pcap) prow_count(d, al[i / d.Pcap], i % d.Pcap);
 }
 // block-wide exclusive scan of up to 4 values per thread (256 threads); returns the total
 __device__ __forceinline__ int block_scan4(int *v, int *wsum) {
@@ -1647,9 +1654,9 @@ __device__ __forceinline__ int block_scan4(int *v, int *wsum) {
   return total;
 }
 // one block per (row, arena): the row's bucket starts in home 0 (cols <= 1024)
-__global__ void __launch_bounds__(256) k_prow_scan(Dev d) {
+__device__ __forceinline__ void prow_scan(const Dev &d, int r, int a) {
   __shared__ int wsum[4];
-  const int r = blockIdx.x, a = blockIdx.y, tid = threadIdx.x, C = d.cols;
+  const int tid = threadIdx.x, C = d.cols;
   ArenaCtl &c = d.ctl[a];
   int *cnt = d.pncnt + (size_t)a * d.PH1 + (size_t)r * (C + 1);
   int *st = d.pstart + (size_t)a * d.PH1 + (size_t)r * (C + 1);
@@ -1677,10 +1684,12 @@ __global__ void __launch_bounds__(256) k_prow_scan(Dev d) {
     }
   }
 }
-__global__ void k_prow_scatter(Dev d) {
-  const int gi = GTID;
-  if (gi >= d.A * d.Pcap) return;
-  const int a = gi / d.Pcap, j = gi - a * d.Pcap;
+__global__ void __launch_bounds__(256) k_prow_scan(Dev d) { prow_scan(d, blockIdx.x, blockIdx.y); }
+__global__ void __launch_bounds__(256) k_prow_scan_list(Dev d, const int *al) {
+  prow_scan(d, blockIdx.x, al[blockIdx.y]);
+}
+__device__ __forceinline__ void prow_scatter(const Dev &d, int a, int j) {
+  const int gi = a * d.Pcap + j;
   if (j >= d.ctl[a].src_n_stage) return;
   const int rk = d.pel_rank[gi];
   if (rk < 0) return;  // (tiles: not held here)
@@ -1692,6 +1701,14 @@ __global__ void k_prow_scatter(Dev d) {
   const size_t o = (size_t)a * d.PS + pos;
   d.pel[o] = r;
   d.pel_col[o] = d.pn_col[gi];
+}
+__global__ void k_prow_scatter(Dev d) {
+  const int gi = GTID;
+  if (gi < d.A * d.Pcap) prow_scatter(d, gi / d.Pcap, gi % d.Pcap);
+}
+__global__ void k_prow_scatter_list(Dev d, const int *al, int n) {
+  const int i = GTID;
+  if (i < n * d.Pcap) prow_scatter(d, al[i / d.Pcap], i % d.Pcap);
 }
 // ------------------------------------------------------------ T10 merge
 __device__ __forceinline__ void merge_player(const Dev &d, int gp) {
@@ -5047,14 +5064,12 @@ void launch_pel_gather(const Dev &d, hipStream_t s, int a) {
 }
 
 // ------------------------------------------------------------ init helpers
-__global__ void k_init_ctl(Dev d, uint64_t seed) {
-  int a = GTID;
-  if (a >= d.A) return;
-  ArenaCtl &c = d.ctl[a];
+// key_arena: the arena word of the Philox key (aigar_reset: the arena's own index)
+__device__ __forceinline__ void init_ctl(const Dev &d, ArenaCtl &c, uint64_t seed, int key_arena) {
   c.seq_next = d.B;  // players take 0..B-1 (Field.initialize order)
   c.tick = 0;
   c.key0 = seed;
-  c.key1 = ((uint64_t)a << 32) | 0x9E3779B9ull;
+  c.key1 = ((uint64_t)key_arena << 32) | 0x9E3779B9ull;
   c.ctr_pellet = c.ctr_virus = 0;
   c.n_pel = c.n_pnew = c.n_pel_eaten = 0;
   c.n_blob = c.n_blob_base = 0;
@@ -5076,6 +5091,22 @@ __global__ void k_init_ctl(Dev d, uint64_t seed) {
   c.n_pel_glob = c.n_eaten_glob = c.n_out = c.n_out_pel = c.n_undone = c.n_undone_glob = 0;
   c.n_ho = c.n_ho_live = 0;
   for (int k = 0; k < 8; k++) c.stat[k] = 0;
+}
+
+__global__ void k_init_ctl(Dev d, uint64_t seed) {
+  int a = GTID;
+  if (a >= d.A) return;
+  init_ctl(d, d.ctl[a], seed, a);
+}
+// aigar_reset_arenas: the listed arenas only, each the world a one-arena handle
+// gets from aigar_reset(seeds[i]) -- so the key's arena word is 0.  The whole
+// control block restarts (as aigar_load_state writes it), not only init_ctl's fields.
+__global__ void k_init_ctl_list(Dev d, const int *al, const uint64_t *seeds, int n) {
+  const int i = GTID;
+  if (i >= n) return;
+  ArenaCtl &c = d.ctl[al[i]];
+  c = ArenaCtl{};
+  init_ctl(d, c, seeds[i], 0);
 }
 
 // ------------------------------------------------------------ launch sequences
@@ -5416,6 +5447,92 @@ void launch_reset(const Dev &d, hipStream_t s, uint64_t seed) {
   hipLaunchKernelGGL(k_pnew_commit, dim3(nblk(d.A, 64)), dim3(64), 0, s, d);
   launch_pellet_rows(d, s);  // staging -> the row store
   launch_player_fov(d, s);
+}
+
+// ---------------------------------------------- aigar_reset_arenas (api.hip)
+// The same sequence for the n arenas of the device list al (distinct, in any
+// order), the other arenas untouched: every kernel maps its block or thread
+// index through the list.  First the listed arenas' slices of what aigar_reset,
+// launch_reset and aigar_load_state clear with whole-buffer memsets, and their
+// bots' restart as aigar_load_state leaves it (commands -1 as after aigar_reset).
+template <class T>
+__device__ __forceinline__ void fill_slice(T *p, size_t n, T v) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
+}
+constexpr int kClearBlocks = 64;  // blocks per listed arena (the longest slice: PD reservation keys)
+__global__ void __launch_bounds__(256) k_clear_arenas_list(Dev d, const int *al) {
+  const size_t a = al[blockIdx.y], B = d.B, p0 = a * B, H1 = (size_t)d.H + 1, GG = (size_t)d.G * d.G;
+  for (int k = 0; k < kMaxCells; k++) fill_slice(d.c_flags + (size_t)k * d.NP + p0, B, 0u);
+  fill_slice(d.v_flags + a * d.Vcap, (size_t)d.Vcap, 0u);
+  fill_slice(d.b_flags + a * d.Ecap, (size_t)d.Ecap, 0u);
+  fill_slice(d.p_split + p0, B, 0);
+  fill_slice(d.p_eject + p0, B, 0);
+  fill_slice(d.pel_owner + a * d.PD, (size_t)d.PD, (uint64_t)0);
+  fill_slice((uint32_t *)(d.pel_dead + a * d.PD), (size_t)d.PD / 4, 0u);  // (PD: a multiple of 64 bytes)
+  fill_slice(d.b_owner + a * d.Ecap, (size_t)d.Ecap, (uint64_t)0);
+  for (int sl = 0; sl < 2; sl++)
+    fill_slice(d.scan_state + ((size_t)sl * d.A + a) * d.scan_tiles, (size_t)d.scan_tiles, 0ull);
+  fill_slice(d.pl_state + a * d.pl_tiles, (size_t)d.pl_tiles, 0ull);
+  fill_slice(d.occ + a * d.occ_words, (size_t)d.occ_words, 0ull);
+  fill_slice(d.cstart + a * H1, H1, 0);
+  fill_slice(d.cgcnt + a * 2 * 4100, (size_t)2 * 4100, 0);
+  fill_slice(d.vstart + a * H1, H1, 0);
+  fill_slice(d.bstart + a * H1, H1, 0);
+  fill_slice(d.bmap + a * 64, (size_t)64, (uint64_t)0);
+  fill_slice(d.v_active + a * d.Vcap, (size_t)d.Vcap, 0);
+  // the bots: commands, lastMass = None, lastFovSize, currentAction, the history grids
+  fill_slice(d.p_cmdx + p0, B, -1.0);
+  fill_slice(d.p_cmdy + p0, B, -1.0);
+  fill_slice(d.o_last_mass + p0, B, __builtin_nan(""));
+  fill_slice(d.o_lastfov + p0, B, 0.0);
+  fill_slice(d.o_act_cur + p0 * 4, B * 4, 0.0);
+  fill_slice(d.o_self_lf + p0 * GG, B * GG, 0.0);
+  fill_slice(d.o_self_slf + p0 * GG, B * GG, 0.0);
+  fill_slice(d.o_en_lf + p0 * GG, B * GG, 0.0);
+  fill_slice(d.o_en_slf + p0 * GG, B * GG, 0.0);
+}
+// k_spawn_plan's init = 1 path for arena al[i]: nothing to compact in a fresh
+// world, no dead list -- spawnStuff's counts alone
+__global__ void k_spawn_plan_list(Dev d, const int *al, int n) {
+  const int i = GTID;
+  if (i >= n) return;
+  const int a = al[i];
+  spawn_counts(d, a, 1, 0, 0, spawn_in(d.ctl[a]));
+}
+__global__ void k_spawn_players_list(Dev d, const int *al, int n) {
+  const int i = GTID;
+  if (i < n * d.B) spawn_player(d, al[i / d.B] * d.B + i % d.B, i % d.B, 1);
+}
+__global__ void k_spawn_pellets_list(Dev d, const int *al, int n) {
+  const int i = GTID;
+  if (i < n * d.Pcap) spawn_pellet(d, al[i / d.Pcap] * d.Pcap + i % d.Pcap);
+}
+__global__ void k_spawn_viruses_list(Dev d, const int *al, int n) {
+  const int i = GTID;
+  if (i < n * d.Vcap) spawn_virus(d, al[i / d.Vcap] * d.Vcap + i % d.Vcap);
+}
+__global__ void k_pnew_commit_list(Dev d, const int *al, int n) {
+  const int i = GTID;
+  if (i >= n) return;
+  ArenaCtl &c = d.ctl[al[i]];
+  c.n_pnew += c.n_spawn_p;
+}
+void launch_player_fov_list(const Dev &d, hipStream_t s, const int *al, int n);
+// al, seeds: device lists of n entries (0 < n <= A), checked by the caller
+void launch_reset_arenas(const Dev &d, hipStream_t s, const int *al, const uint64_t *seeds, int n) {
+  hipLaunchKernelGGL(k_clear_arenas_list, dim3(kClearBlocks, n), dim3(256), 0, s, d, al);
+  hipLaunchKernelGGL(k_init_ctl_list, dim3(nblk(n, 64)), dim3(64), 0, s, d, al, seeds, n);
+  hipLaunchKernelGGL(k_spawn_plan_list, dim3(nblk(n, 64)), dim3(64), 0, s, d, al, n);
+  hipLaunchKernelGGL(k_spawn_players_list, dim3(nblk((long)n * d.B, 256)), dim3(256), 0, s, d, al, n);
+  const long np = (long)n * d.Pcap;
+  hipLaunchKernelGGL(k_spawn_pellets_list, dim3(nblk(np, 256)), dim3(256), 0, s, d, al, n);
+  if (d.virus_enabled)
+    hipLaunchKernelGGL(k_spawn_viruses_list, dim3(nblk((long)n * d.Vcap, 256)), dim3(256), 0, s, d, al, n);
+  hipLaunchKernelGGL(k_pnew_commit_list, dim3(nblk(n, 64)), dim3(64), 0, s, d, al, n);
+  hipLaunchKernelGGL(k_prow_count_list, dim3(nblk(np, 256)), dim3(256), 0, s, d, al, n);
+  hipLaunchKernelGGL(k_prow_scan_list, dim3(d.cols, n), dim3(256), 0, s, d, al);
+  hipLaunchKernelGGL(k_prow_scatter_list, dim3(nblk(np, 256)), dim3(256), 0, s, d, al, n);
+  launch_player_fov_list(d, s, al, n);
 }
 
 #ifdef AIGAR_PHASE_TIMING

@@ -110,9 +110,9 @@ class AgarVecEnv:
         greedy = self.torch.as_tensor(self.roles == _abi.ROLE_GREEDY, device=self.dev).to(self.torch.uint8)
         gsplit = bool(getattr(self.parameters, "ENABLE_GREEDY_SPLIT", False)) if self.parameters is not None else False
         for t in range(total + 1):
-            for a in range(self.A):
-                if t > 0 and total - a * per == t:
-                    self.stepper.reset_arena(a, seed + 104729 * (a + 1))
+            fresh = [a for a in range(self.A) if t > 0 and total - a * per == t]
+            if fresh:
+                self.stepper.reset_arenas(fresh, [seed + 104729 * (a + 1) for a in fresh])
             if t == total:
                 break
             # NN players: random points in their view (an untrained network's moves);
@@ -123,7 +123,10 @@ class AgarVecEnv:
             if has_r:
                 self.stepper.policy_random_bots()
             self.stepper.step(1)
-        for a in range(self.A):  # Model.resetBots: every bot of every arena (the world goes on)
+        # Model.resetBots: every bot of every arena (the world goes on).  Still the host
+        # round trip: load_state also re-lays the pellet rows and restarts the arena's
+        # control block and epochs, which no device call does for a running world
+        for a in range(self.A):
             self.stepper.load_state(self.stepper.get_state(a), a)
         self.age[:] = np.arange(self.A) * per
 
@@ -149,11 +152,13 @@ class AgarVecEnv:
         if not len(ended):
             return done
         mask = np.zeros(self.NP, np.uint8)
-        for a in ended:
+        seeds = []
+        for a in ended:  # (ascending arena order)
             self._resets += 1
-            self.stepper.reset_arena(int(a), self.seed + 7919 * self._resets)
+            seeds.append(self.seed + 7919 * self._resets)
             self.age[a] = 0
             mask[a * self.B:(a + 1) * self.B] = 1
+        self.stepper.reset_arenas(ended, seeds)  # one call, on the device
         done[torch.as_tensor(mask.astype(bool), device=self.dev)] = True
         # the new episodes' first states (NN players of the reset arenas)
         nn_reset = (mask & (self.roles == _abi.ROLE_NN)).astype(np.uint8)

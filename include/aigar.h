@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define AIGAR_ABI_VERSION 5
+#define AIGAR_ABI_VERSION 6
 
 /* random number stream of the world (spawns, explosion angles) */
 #define AIGAR_RNG_PHILOX 0   /* Philox4x64-10 keyed by (seed, site, index): device + oracle */
@@ -168,6 +168,17 @@ int aigar_destroy(aigar_handle *h);
 /* Field.initialize()/Field.reset(): spawn every player, pellets, viruses.
  * replaces field.py:57-83 (model.py:90-98) */
 int aigar_reset(aigar_handle *h, uint64_t seed);
+
+/* Field.reset() of the listed arenas only (field.py:69-83) + every bot's reset in
+ * those arenas; all other arenas are untouched.  Afterwards arena arenas[k] is the
+ * world of a one-arena handle of the same config after aigar_reset(seeds[k]),
+ * Philox key included (its arena word is 0, whatever the arena's index), and its
+ * bots restart as after aigar_load_state: history grids, lastFovSize and
+ * currentAction cleared, lastMass None, commands -1.  The arenas must be distinct;
+ * n == 0 does nothing; tiled handles are refused.  Stream-ordered, no host round
+ * trip: the lists are copied before the call returns, device errors surface at the
+ * next call that checks them (aigar_step, aigar_get_state).  Captured graphs stay valid. */
+int aigar_reset_arenas(aigar_handle *h, const int32_t *arenas, const uint64_t *seeds, int n);
 
 /* Player.setCommands(x, y, split, eject) for every player: cmd[A*B][4].
  * replaces player.py:99-102 (called from bot.py:550-577) */
