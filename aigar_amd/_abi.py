@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 RNG_PHILOX = 0
 RNG_MT19937 = 1
@@ -21,6 +21,7 @@ EV_MERGE, EV_VIRUS_EAT_BLOB, EV_VIRUS_SPLIT, EV_CELL_EAT_VIRUS, EV_EXPLODE = 1, 
 EV_CELL_EAT_PELLET, EV_CELL_EAT_BLOB, EV_CELL_EAT_CELL, EV_PLAYER_DEATH, EV_RESPAWN = 6, 7, 8, 9, 10
 
 FLAG_EVENTS = 0x1
+FLAG_SCORE = 0x2  # per-player mass history statistics (Stepper.score*, AgarVecEnv(score=True))
 TILE_OWNED_ONLY = 0x1
 TILE_FORCE = 0x2  # a 1 x 1 tiled handle (the whole field one tile: the one-GPU test of the exchange path)
 

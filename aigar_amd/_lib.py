@@ -88,6 +88,9 @@ def load(build_if_missing=False):
         "aigar_set_actions": [vp, vp, vp, i32],
         "aigar_reset_bots": [vp, vp, i32],
         "aigar_player_stats": [vp, vp, i32],
+        "aigar_score": [vp, vp, i32],
+        "aigar_score_reset": [vp, vp, i32],
+        "aigar_score_trace": [vp, vp, C.c_int64],
         "aigar_get_state": [vp, i32, C.POINTER(_abi.State)],
         "aigar_load_state": [vp, i32, C.POINTER(_abi.State)],
         "aigar_get_events": [vp, i32, C.POINTER(C.c_int64), i32, C.POINTER(i32)],
@@ -354,6 +357,37 @@ class Stepper:
         out = np.zeros((self.NP, 5), np.float64)
         self._chk(self.L.aigar_player_stats(self.h, out.ctypes.data_as(C.c_void_p), 0))
         return out
+
+    def score(self, out=None):
+        """[NP, 4] samples, sum, max, dead of every bot's getMassOverTime() (bot.py:253,639-640);
+        needs a handle created with FLAG_SCORE.  out: numpy array or device tensor."""
+        if out is None:
+            out = np.zeros((self.NP, 4), np.float64)
+        self._check_out(out, (self.NP, 4), ("float64",), "score")
+        p, dev = _ptr(out)
+        self._chk(self.L.aigar_score(self.h, p, dev))
+        return out
+
+    def score_reset(self, mask=None):
+        """Bot.resetMassList for the players where mask != 0 (all if None); stream-ordered."""
+        if isinstance(mask, np.ndarray):
+            mask = np.ascontiguousarray(mask, np.uint8).reshape(self.NP)
+        p, dev = _ptr(mask)
+        self._chk(self.L.aigar_score_reset(self.h, p, dev))
+
+    def score_trace(self, buf):
+        """Attach the DEVICE tensor buf [cap, NP] float64 (row = sample index, column =
+        player) as the mass lists' store, or detach with None.  The caller keeps buf alive
+        while it is attached."""
+        if buf is None:
+            self._chk(self.L.aigar_score_trace(self.h, None, 0))
+            return
+        if not getattr(buf, "is_cuda", False):
+            raise ValueError("score_trace: buf must be a device tensor")
+        if len(buf.shape) != 2:
+            raise ValueError("score_trace: buf must have shape (cap, %d), got %s" % (self.NP, tuple(buf.shape)))
+        self._check_out(buf, (int(buf.shape[0]), self.NP), ("float64",), "score_trace")
+        self._chk(self.L.aigar_score_trace(self.h, C.c_void_p(buf.data_ptr()), int(buf.shape[0])))
 
     def get_state(self, arena=0):
         cnt = _abi.State()

@@ -147,6 +147,12 @@ __device__ __forceinline__ void pel_store(PelRec *p, const PelRec &r) {
 #endif
 }
 
+// aigar_score_trace's buffer [cap][NP] (device memory, written stream-ordered)
+struct ScoreCtl {
+  double *trace;  // null: detached
+  int64_t cap;
+};
+
 struct Dev {
   int A, B, NP, size, cols, H;
   int tiled, tile_id, ntiles, tcap, bm_words;  // tcap: records per outbox; bm_words: u64 words of the bitmap
@@ -272,7 +278,11 @@ struct Dev {
   uint8_t *ob_own;
   int *ob_perm;
   uint64_t *ob_wmask;  // [OBcap][4] x / y index masks of the wide grid (grid_squares > 16)
+  // AIGAR_FLAG_SCORE (else both null): the bots' mass history, Bot.totalMasses (bot.py:253)
+  double *sc;        // [4][NP]: samples, sum, max, dead (SC_*; counts are exact in fp64)
+  ScoreCtl *sc_ctl;  // the attached trace: read by every sample, so graphs never hold its address
 };
+enum { SC_N = 0, SC_SUM = 1, SC_MAX = 2, SC_DEAD = 3 };
 
 constexpr int FCAP = 32;  // stored candidate foods per cell (overflow -> serial)
 

@@ -35,6 +35,9 @@ void launch_policy_refrandom(const Dev &d, hipStream_t s, int skip_rate, int ena
 int launch_observe_pixels(const Dev &d, hipStream_t s, void *out, int dtype, int side, uint64_t seed, uint8_t *ovf);
 void launch_policy(const Dev &d, hipStream_t s, double ps, double pe, uint64_t salt);
 void launch_player_stats(const Dev &d, hipStream_t s, double *out);
+void launch_score_read(const Dev &d, hipStream_t s, double *out);
+void launch_score_reset(const Dev &d, hipStream_t s, const uint8_t *mask);
+void launch_score_trace(const Dev &d, hipStream_t s, double *buf, int64_t cap);
 void launch_player_fov(const Dev &d, hipStream_t s);
 void launch_apply_actions(const Dev &d, hipStream_t s, const double *act, int n_act, int enable_split, int skipping,
                           int record);
@@ -112,6 +115,7 @@ struct aigar_handle {
   int64_t *scr_k = nullptr;
   int *scr_v = nullptr;
   double *d_cmd = nullptr, *d_stats = nullptr;
+  double *d_score = nullptr;  // host-destination staging for aigar_score
   uint8_t *d_mask = nullptr;
   uint8_t *d_nnmask = nullptr;  // 1 for the players of role NN (the env step's observations)
   int n_greedy = 0, n_random = 0;  // role counts (aigar_set_roles)
@@ -307,6 +311,9 @@ extern "C" int aigar_create(const aigar_config *cfg, aigar_handle **out) {
   if (cfg->obs_channels & AIGAR_OBS_ALL &&
       cfg->obs_channels & (AIGAR_OBS_SELF_LF | AIGAR_OBS_SELF_SLF | AIGAR_OBS_ENEMY_LF | AIGAR_OBS_ENEMY_SLF))
     return fail("aigar_create: ALL_PLAYER_GRID with last-frame grids is undefined in the reference");
+  if ((cfg->flags & AIGAR_FLAG_SCORE) &&
+      (std::max(1, cfg->tile_x) * std::max(1, cfg->tile_y) > 1 || (cfg->tile_flags & AIGAR_TILE_FORCE)))
+    return fail("aigar_create: AIGAR_FLAG_SCORE (the mass history score) is not kept on a tiled handle");
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   if (cfg->device < 0 || cfg->device >= ndev) return fail("aigar_create: device %d not present (%d devices)", cfg->device, ndev);
@@ -497,6 +504,12 @@ extern "C" int aigar_create(const aigar_config *cfg, aigar_handle **out) {
   AL(ob_mask, uint32_t, d.OBcap); AL(ob_own, uint8_t, d.OBcap); AL(ob_perm, int, d.OBcap);
   d.ob_wmask = nullptr;
   if (G > 16) AL(ob_wmask, uint64_t, 4 * (size_t)d.OBcap);
+  d.sc = nullptr;
+  d.sc_ctl = nullptr;
+  if (cfg->flags & AIGAR_FLAG_SCORE) {  // (zeroed with the arena: no samples, no trace)
+    AL(sc, double, 4 * NP);
+    AL(sc_ctl, ScoreCtl, 1);
+  }
 #undef AL
   h->scr_k = dalloc<int64_t>(h, A * d.Wcap);
   h->scr_v = dalloc<int>(h, A * d.Wcap);
@@ -507,6 +520,10 @@ extern "C" int aigar_create(const aigar_config *cfg, aigar_handle **out) {
   h->d_obs = dalloc<double>(h, NP * (size_t)d.L);
   h->d_rlist = dalloc<int>(h, A);
   h->d_rseed = dalloc<uint64_t>(h, A);
+  if (d.sc) {
+    h->d_score = dalloc<double>(h, NP * 4);
+    ok = ok && h->d_score;
+  }
   ok = ok && h->scr_k && h->scr_v && h->d_cmd && h->d_stats && h->d_obs && h->d_mask && h->d_nnmask && h->d_rlist &&
        h->d_rseed;
 #ifndef AIGAR_NO_ARENA
@@ -581,6 +598,7 @@ extern "C" int aigar_reset(aigar_handle *h, uint64_t seed) {
   HIPCHK(hipMemsetAsync(d.bmap, 0, sizeof(uint64_t) * A * 64, h->stream));
   HIPCHK(hipMemsetAsync(d.v_active, 0, sizeof(int) * A * d.Vcap, h->stream));
   HIPCHK(hipMemsetAsync(d.o_lastfov, 0, sizeof(double) * NP, h->stream));
+  if (d.sc) HIPCHK(hipMemsetAsync(d.sc, 0, sizeof(double) * 4 * NP, h->stream));  // every mass history starts empty
   // Bot.reset (bot.py:125-164): currentAction None (NN) / [0, 0, 0, 0] (Greedy, Random)
   HIPCHK(hipMemsetAsync(d.o_act_cur, 0, sizeof(double) * NP * 4, h->stream));
   for (double *p : {d.o_self_lf, d.o_self_slf, d.o_en_lf, d.o_en_slf})
@@ -1406,6 +1424,46 @@ extern "C" int aigar_player_stats(aigar_handle *h, double *out, int on_device) {
   return 0;
 }
 
+// ---- AIGAR_FLAG_SCORE: the bots' mass history (k_score_sample, the first launch of every tick)
+static int need_score(aigar_handle *h, const char *who) {
+  if (!h) return fail("null handle");
+  if (!h->d.sc) return fail("%s: the handle keeps no score (create it with AIGAR_FLAG_SCORE in aigar_config.flags)", who);
+  return 0;
+}
+extern "C" int aigar_score(aigar_handle *h, double *out, int on_device) {
+  if (need_score(h, "aigar_score")) return -1;
+  if (!out) return fail("aigar_score: null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  launch_score_read(h->d, h->stream, on_device ? out : h->d_score);
+  HIPCHK(hipGetLastError());
+  if (!on_device) {
+    HIPCHK(hipMemcpyAsync(out, h->d_score, sizeof(double) * 4 * h->d.NP, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  return 0;
+}
+extern "C" int aigar_score_reset(aigar_handle *h, const uint8_t *mask, int on_device) {
+  if (need_score(h, "aigar_score_reset")) return -1;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const uint8_t *m = mask;
+  if (mask && !on_device) {
+    HIPCHK(hipMemcpyAsync(h->d_mask, mask, (size_t)h->d.NP, hipMemcpyHostToDevice, h->stream));
+    m = h->d_mask;
+  }
+  launch_score_reset(h->d, h->stream, m);
+  HIPCHK(hipGetLastError());
+  if (mask && !on_device) HIPCHK(hipStreamSynchronize(h->stream));  // caller may reuse its buffer
+  return 0;
+}
+extern "C" int aigar_score_trace(aigar_handle *h, double *buf, int64_t cap) {
+  if (need_score(h, "aigar_score_trace")) return -1;
+  if (buf && cap < 0) return fail("aigar_score_trace: cap = %lld is negative", (long long)cap);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  launch_score_trace(h->d, h->stream, buf, cap);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 extern "C" int aigar_set_stream(aigar_handle *h, void *s) {
   if (!h) return fail("null handle");
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -1819,6 +1877,8 @@ extern "C" int aigar_load_state(aigar_handle *h, int arena, const aigar_state *s
   // bot-side observation history restarts (NN bot reset, bot.py:151-158)
   HIPCHK(hipMemsetAsync(d.o_lastfov + p0, 0, 8 * B, h->stream));
   HIPCHK(hipMemsetAsync(d.o_act_cur + p0 * 4, 0, 8 * 4 * (size_t)B, h->stream));  // currentAction reset
+  if (d.sc)  // a snapshot carries no mass history: this arena's starts empty
+    for (int f = 0; f < 4; f++) HIPCHK(hipMemsetAsync(d.sc + (size_t)f * NP + p0, 0, 8 * (size_t)B, h->stream));
   hipLaunchKernelGGL(k_fill_d, dim3((B + 255) / 256), dim3(256), 0, h->stream, d.o_last_mass + p0, (size_t)B,
                      __builtin_nan(""));
   for (double *p : {d.o_self_lf, d.o_self_slf, d.o_en_lf, d.o_en_slf})

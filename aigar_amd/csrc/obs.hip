@@ -1265,6 +1265,55 @@ __global__ void k_player_stats(Dev d, double *out) {
   o[4] = f.fs;
 }
 
+// AIGAR_FLAG_SCORE: Bot.makeMove's totalMasses.append(player.getTotalMass())
+// (bot.py:253), the first launch of every tick.  A dead player's p_mass is stale:
+// its sample is 0.0, as getTotalMass of an empty cell list.  The sum is one add
+// per sample in tick order.  Sample k goes to row k of the attached trace while
+// k < cap; address and cap come from device memory (aigar_score_trace).
+__global__ void __launch_bounds__(256) k_score_sample(Dev d) {
+  const int gp = GTID;
+  if (gp >= d.NP) return;
+  const size_t NP = d.NP;
+  const bool alive = d.p_alive[gp];
+  const double m = alive ? d.p_mass[gp] : 0.0;
+  double *sc = d.sc + gp;
+  const double k = sc[SC_N * NP];
+  sc[SC_N * NP] = k + 1.0;
+  sc[SC_SUM * NP] += m;
+  if (m > sc[SC_MAX * NP]) sc[SC_MAX * NP] = m;
+  if (!alive) sc[SC_DEAD * NP] += 1.0;
+  const ScoreCtl c = *d.sc_ctl;
+  if (c.trace && (int64_t)k < c.cap) c.trace[(size_t)(int64_t)k * NP + gp] = m;
+}
+void launch_score_sample(const Dev &d, hipStream_t s) {
+  hipLaunchKernelGGL(k_score_sample, dim3((d.NP + 255) / 256), dim3(256), 0, s, d);
+}
+// aigar_score: out[NP][4] = samples, sum, max, dead
+__global__ void k_score_read(Dev d, double *out) {
+  const int gp = GTID;
+  if (gp >= d.NP) return;
+  for (int f = 0; f < 4; f++) out[(size_t)gp * 4 + f] = d.sc[(size_t)f * d.NP + gp];
+}
+void launch_score_read(const Dev &d, hipStream_t s, double *out) {
+  hipLaunchKernelGGL(k_score_read, dim3((d.NP + 255) / 256), dim3(256), 0, s, d, out);
+}
+// Bot.resetMassList (bot.py:122-123) for the masked players (null: all)
+__global__ void k_score_reset(Dev d, const uint8_t *mask) {
+  const int gp = GTID;
+  if (gp >= d.NP || (mask && !mask[gp])) return;
+  for (int f = 0; f < 4; f++) d.sc[(size_t)f * d.NP + gp] = 0.0;
+}
+void launch_score_reset(const Dev &d, hipStream_t s, const uint8_t *mask) {
+  hipLaunchKernelGGL(k_score_reset, dim3((d.NP + 255) / 256), dim3(256), 0, s, d, mask);
+}
+__global__ void k_score_trace(Dev d, double *buf, int64_t cap) {
+  d.sc_ctl->trace = buf;
+  d.sc_ctl->cap = buf ? cap : 0;
+}
+void launch_score_trace(const Dev &d, hipStream_t s, double *buf, int64_t cap) {
+  hipLaunchKernelGGL(k_score_trace, dim3(1), dim3(1), 0, s, d, buf, cap);
+}
+
 __global__ void k_set_commands(Dev d, const double *cmd) {
   int gp = GTID;
   if (gp >= d.NP) return;

@@ -5180,7 +5180,9 @@ void launch_tick_post(const Dev &d, hipStream_t s, int64_t *scr_k, int *scr_v) {
   const int nbV = d.virus_enabled ? nblk((long)d.A * d.Vcap, 256) : 0;
   hipLaunchKernelGGL(k_pel_update, dim3(d.A * d.cols + nbF + nbV), dim3(256), 0, s, d, nbF);
 }
+void launch_score_sample(const Dev &d, hipStream_t s);
 void launch_tick(const Dev &d, hipStream_t s, int rounds, int64_t *scr_k, int *scr_v, const RandomPolicy *rp) {
+  if (d.sc) launch_score_sample(d, s);  // AIGAR_FLAG_SCORE: the mass sample of Model.update's start (bot.py:253)
   launch_tick_pre(d, s, scr_k, scr_v, rp);
   launch_food(d, s, rounds, Scratch{scr_k, scr_v}, 0, 1);
   launch_tick_post(d, s, scr_k, scr_v);
@@ -5490,6 +5492,8 @@ __global__ void __launch_bounds__(256) k_clear_arenas_list(Dev d, const int *al)
   fill_slice(d.o_self_slf + p0 * GG, B * GG, 0.0);
   fill_slice(d.o_en_lf + p0 * GG, B * GG, 0.0);
   fill_slice(d.o_en_slf + p0 * GG, B * GG, 0.0);
+  if (d.sc)  // AIGAR_FLAG_SCORE: a new episode's mass history starts empty
+    for (int f = 0; f < 4; f++) fill_slice(d.sc + (size_t)f * d.NP + p0, B, 0.0);
 }
 // k_spawn_plan's init = 1 path for arena al[i]: nothing to compact in a fresh
 // world, no dead list -- spawnStuff's counts alone

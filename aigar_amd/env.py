@@ -28,6 +28,13 @@ first decision arena k has played k * int(RESET_LIMIT / n_arenas) ticks of its
 own world with its own population (the NN players on random actions during
 that warm-up, the reference's untrained networks), then every bot is reset
 (Model.resetBots).
+
+Scores (`score=True`; aigar.py:523-538 performAgarioTest): every tick starts with
+each bot's mass sample on the device (Bot.makeMove, bot.py:253).  `score()` gives
+the running episodes' [NP, 4] samples / sum / max / deaths; when an arena's episode
+ends its rows move to `last_score` (and the NN players' summed rewards to
+`last_return`) before the arena is reset, and `test_score()` reduces them to the
+reference's meanMass and maxMass per arena.  The warm-up is not scored.
 """
 import numpy as np
 
@@ -38,7 +45,8 @@ from .model import obs_masks
 
 class AgarVecEnv:
     def __init__(self, n_players, parameters=None, n_arenas=1, virus=None, field_size=0, max_pellets=-1.0,
-                 max_viruses=-1.0, device=0, torch_stream=True, roles=None, reset_limit=None, desync=True, seed=0):
+                 max_viruses=-1.0, device=0, torch_stream=True, roles=None, reset_limit=None, desync=True, seed=0,
+                 score=False):
         import torch
         self.torch = torch
         self.parameters = parameters
@@ -53,6 +61,8 @@ class AgarVecEnv:
         c.max_pellets, c.max_viruses = float(max_pellets), float(max_viruses)
         c.grid_squares, c.obs_channels, c.obs_extras = gsq, ch, ex
         c.rng_mode, c.device = _abi.RNG_PHILOX, device
+        if score:
+            c.flags |= _abi.FLAG_SCORE
         self.stepper = Stepper(c)
         self.dev = torch.device("cuda", device)
         if torch_stream:
@@ -87,6 +97,15 @@ class AgarVecEnv:
         self._mask = torch.zeros(self.NP, dtype=torch.uint8, device=self.dev)  # (persistent: read on the stepper's stream)
         self._r = torch.empty(self.NP, dtype=torch.float64, device=self.dev)
         self._act = {}  # n_act -> persistent action buffer (the decision graph is keyed by its address)
+        self._scored = bool(score)
+        if self._scored:
+            self._own_stream = not torch_stream  # (the stepper's work is then not ordered with torch's)
+            self._score = torch.empty((self.NP, 4), dtype=torch.float64, device=self.dev)
+            self._ret = torch.zeros(self.NP, dtype=torch.float64, device=self.dev)
+            nan = float("nan")
+            # the last finished episode of every arena: NaN until its first episode has ended
+            self.last_score = torch.full((self.NP, 4), nan, dtype=torch.float64, device=self.dev)
+            self.last_return = torch.full((self.NP,), nan, dtype=torch.float64, device=self.dev)
 
     def reset(self, seed=None):
         """Field.reset + every bot's reset (lastMass = None, history grids cleared);
@@ -97,6 +116,11 @@ class AgarVecEnv:
         self._resets = 0
         if self.desync:
             self._desynchronise(seed)
+        if self._scored:  # the episodes are scored from here: not the warm-up
+            self.stepper.score_reset()
+            self._ret.zero_()
+            self.last_score.fill_(float("nan"))
+            self.last_return.fill_(float("nan"))
         return self.observe()
 
     def _desynchronise(self, seed):
@@ -158,8 +182,14 @@ class AgarVecEnv:
             seeds.append(self.seed + 7919 * self._resets)
             self.age[a] = 0
             mask[a * self.B:(a + 1) * self.B] = 1
+        ended_t = torch.as_tensor(mask.astype(bool), device=self.dev)
+        if self._scored:  # the finished episodes' rows, before the reset clears them (no host sync)
+            self._read_score()
+            self.last_score = torch.where(ended_t[:, None], self._score, self.last_score)
+            self.last_return = torch.where(ended_t & self.nn, self._ret, self.last_return)
+            self._ret = torch.where(ended_t, torch.zeros_like(self._ret), self._ret)
         self.stepper.reset_arenas(ended, seeds)  # one call, on the device
-        done[torch.as_tensor(mask.astype(bool), device=self.dev)] = True
+        done[ended_t] = True
         # the new episodes' first states (NN players of the reset arenas)
         nn_reset = (mask & (self.roles == _abi.ROLE_NN)).astype(np.uint8)
         self._mask.copy_(torch.as_tensor(nn_reset))
@@ -179,9 +209,42 @@ class AgarVecEnv:
         buf.copy_(act)
         self.stepper.env_step(buf, self._r, self.obs, self.enable_split, self.skip, self.reward_params)
         reward = self._r.clone()
+        if self._scored:
+            self._ret += torch.where(self.nn, reward, torch.zeros_like(reward))
         done = self._episode_ends()
         alive = ~torch.isnan(self.obs[:, 0]) & self.nn
         return self.obs.clone(), reward, alive, done
+
+    def _read_score(self):
+        self.stepper.score(self._score)
+        if self._own_stream:
+            self.stepper.sync()
+
+    def score(self):
+        """[NP, 4] device tensor of the running episodes: samples, sum, max, deaths of
+        every bot's mass list (Bot.getMassOverTime, bot.py:639-640)."""
+        if not self._scored:
+            raise RuntimeError("AgarVecEnv was created without score=True")
+        self._read_score()
+        return self._score.clone()
+
+    def test_score(self, arena_mask=None):
+        """(meanMass[A], maxMass[A]) of every arena's last finished episode, as
+        performAgarioTest computes them (aigar.py:533-535): the mean over the arena's bots of
+        their mean mass over time, and the largest mass any of them had.  NaN for an arena
+        without a finished episode and where arena_mask (bool [A]) is False."""
+        if not self._scored:
+            raise RuntimeError("AgarVecEnv was created without score=True")
+        torch = self.torch
+        s = self.last_score.view(self.A, self.B, 4)
+        mean = (s[:, :, 1] / s[:, :, 0]).mean(dim=1)
+        top = s[:, :, 2].max(dim=1).values
+        if arena_mask is not None:
+            m = arena_mask if isinstance(arena_mask, torch.Tensor) else torch.as_tensor(np.asarray(arena_mask, bool))
+            m = m.to(device=self.dev, dtype=torch.bool)
+            nan = torch.full_like(mean, float("nan"))
+            mean, top = torch.where(m, mean, nan), torch.where(m, top, nan)
+        return mean, top
 
     def step_calls(self, actions):
         """The same decision as separate calls (apply_actions / Greedy bots / Random

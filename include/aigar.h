@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define AIGAR_ABI_VERSION 6
+#define AIGAR_ABI_VERSION 7
 
 /* random number stream of the world (spawns, explosion angles) */
 #define AIGAR_RNG_PHILOX 0   /* Philox4x64-10 keyed by (seed, site, index): device + oracle */
@@ -71,6 +71,9 @@ extern "C" {
 #define AIGAR_EV_RESPAWN        10  /* (player index, new cell seq)  field.py:277  */
 
 #define AIGAR_FLAG_EVENTS 0x1       /* record the event log of each step */
+/* per-player mass history statistics, sampled on the device at the start of every
+ * tick (aigar_score*; untiled handles only).  Without it no tick launches anything more */
+#define AIGAR_FLAG_SCORE 0x2
 /* tile_flags: decide only the cells this tile owns (the others wait for their
  * owners' messages) -- the strictest exchange pattern, used by the tests */
 #define AIGAR_TILE_OWNED_ONLY 0x1
@@ -313,6 +316,32 @@ int aigar_reset_bots(aigar_handle *h, const uint8_t *mask, int on_device);
 /* per-player summary [A*B][5]: alive, total mass (player.py:129), fov x, fov y, fov size
  * (player.py:156-167). */
 int aigar_player_stats(aigar_handle *h, double *out, int on_device);
+
+/* The bots' mass history (AIGAR_FLAG_SCORE).  Bot.makeMove appends
+ * player.getTotalMass() at the start of every Model.update (bot.py:253); with the
+ * flag every tick of aigar_step / aigar_run / aigar_env_step starts by taking that
+ * sample of every player on the device: the player's total mass, 0.0 while it is
+ * dead.  T ticks after a reset are T samples, the first the fresh world's mass; the
+ * state after the last tick is not sampled.  aigar_reset, aigar_reset_arenas and
+ * aigar_load_state clear the players they restart; aigar_reset_bots does not
+ * (Bot.reset keeps totalMasses).
+ *
+ * aigar_score: out[A*B][4] = samples, sum, max, dead of Bot.getMassOverTime()
+ * (bot.py:639-640) -- what aigar.py:531-535 reduces to meanMass (the mean over bots
+ * of sum / samples) and maxMass (the max over bots of max).  sum is one fp64 add per
+ * sample in tick order; max is 0.0 without samples; dead counts the samples taken
+ * while the player was dead (one per death: stepsUntilRespawn = 1). */
+int aigar_score(aigar_handle *h, double *out, int on_device);
+/* Bot.resetMassList (bot.py:122-123) for the players with mask[i] != 0 (NULL: all):
+ * the next sample is sample 0.  mask: NP bytes, host or (on_device) device.
+ * Stream-ordered. */
+int aigar_score_reset(aigar_handle *h, const uint8_t *mask, int on_device);
+/* The list itself (bot.py:639-640): a DEVICE buffer buf[cap][A*B] (row = sample
+ * index, column = player), NULL to detach.  Sample k of player i goes to
+ * buf[k][i] while k < cap; later samples are counted but not stored.  Column i,
+ * rows [0, min(samples, cap)), is that bot's getMassOverTime().  Stream-ordered;
+ * the buffer's address is read from device memory, so captured graphs stay valid. */
+int aigar_score_trace(aigar_handle *h, double *buf, int64_t cap);
 
 /* Snapshot / restore one arena (parity harness, checkpoint/resume). */
 int aigar_get_state(aigar_handle *h, int arena, aigar_state *st);
