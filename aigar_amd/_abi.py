@@ -26,6 +26,7 @@ TILE_OWNED_ONLY = 0x1
 TILE_FORCE = 0x2  # a 1 x 1 tiled handle (the whole field one tile: the one-GPU test of the exchange path)
 
 
+PIX_RGB, PIX_LAST = 0x1, 0x2  # aigar_pixel_params.flags
 POLICY_NONE, POLICY_RANDOM, POLICY_GREEDY = 0, 1, 2
 ROLE_NN, ROLE_GREEDY, ROLE_RANDOM = 0, 1, 2
 ROLES = {"NN": ROLE_NN, "Greedy": ROLE_GREEDY, "Random": ROLE_RANDOM}
@@ -35,6 +36,11 @@ class EnvParams(C.Structure):
     """aigar_env_params (include/aigar.h): the device Greedy / Random bots of a mixed population."""
     _fields_ = [("greedy_split", C.c_int32), ("random_skip", C.c_int32), ("random_split", C.c_int32),
                 ("random_eject", C.c_int32), ("salt", C.c_uint64)]
+
+
+class PixelParams(C.Structure):
+    """aigar_pixel_params (include/aigar.h): the learner's pixel state (CNN_P_REPR)."""
+    _fields_ = [("side", C.c_int32), ("flags", C.c_int32), ("color_seed", C.c_uint64)]
 
 
 class RunParams(C.Structure):

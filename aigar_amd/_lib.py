@@ -85,6 +85,9 @@ def load(build_if_missing=False):
         "aigar_obs_len": [vp],
         "aigar_observe": [vp, vp, i32, i32],
         "aigar_observe_pixels": [vp, vp, i32, u64, i32, i32],
+        "aigar_pixel_config": [vp, C.POINTER(_abi.PixelParams)],
+        "aigar_pixel_state_len": [vp],
+        "aigar_observe_pixel_state": [vp, vp, i32, i32, vp, i32],
         "aigar_set_actions": [vp, vp, vp, i32],
         "aigar_reset_bots": [vp, vp, i32],
         "aigar_player_stats": [vp, vp, i32],
@@ -166,6 +169,7 @@ class Stepper:
         self.A, self.B = cfg.n_arenas, cfg.bots_per_arena
         self.NP = self.A * self.B
         self.obs_len = self.L.aigar_obs_len(self.h)
+        self.pixel_state_shape = None  # (NP, side, side, C) while a pixel state is configured
 
     def _chk(self, r):
         if r < 0:
@@ -256,7 +260,11 @@ class Stepper:
             raise ValueError("actions and rewards are float64")
         if act.dim() != 2 or act.shape[0] != self.NP or not 2 <= act.shape[1] <= 4:
             raise ValueError("actions must be [%d, 2..4]" % self.NP)
-        if tuple(obs.shape) != (self.NP, self.obs_len) or tuple(reward.shape) != (self.NP,):
+        if self.pixel_state_shape is not None:
+            if tuple(reward.shape) != (self.NP,):
+                raise ValueError("reward must be [%d]" % self.NP)
+            self._check_out(obs, self.pixel_state_shape, ("float64", "float32"), "env_step")
+        elif tuple(obs.shape) != (self.NP, self.obs_len) or tuple(reward.shape) != (self.NP,):
             raise ValueError("reward must be [%d], obs [%d, %d]" % (self.NP, self.NP, self.obs_len))
         prm = params if isinstance(params, _abi.RewardParams) else _abi.RewardParams.from_parameters(params)
         dt = 0 if str(obs.dtype) == "torch.float64" else 1
@@ -338,6 +346,37 @@ class Stepper:
         dt = 2 if d == "uint8" else 0 if d == "float64" else 1
         p, dev = _ptr(out)
         self._chk(self.L.aigar_observe_pixels(self.h, p, int(side), int(color_seed), dt, dev))
+        return out
+
+    def pixel_config(self, side, rgb=False, last=False, color_seed=0):
+        """The learner's pixel state (CNN_P_REPR, bot.py:276-282): side x side frames of
+        1 (grayscale) or 3 (rgb) channels through (frame - 255) / 100, doubled by last
+        ([current | the bot's previous frame]).  While it is set, env_step writes it instead
+        of the grid row.  pixel_config(None) turns it off.  Clears the frame history."""
+        if side is None:
+            self._chk(self.L.aigar_pixel_config(self.h, None))
+            self.pixel_state_shape = None
+            return
+        prm = _abi.PixelParams(int(side), (_abi.PIX_RGB if rgb else 0) | (_abi.PIX_LAST if last else 0),
+                               int(color_seed) & 0xFFFFFFFFFFFFFFFF)
+        self._chk(self.L.aigar_pixel_config(self.h, C.byref(prm)))
+        n = self.L.aigar_pixel_state_len(self.h)
+        self.pixel_state_shape = (self.NP, int(side), int(side), n // (int(side) * int(side)))
+
+    def observe_pixel_state(self, out=None, dtype=np.float32, mask=None):
+        """The configured pixel state of every player, [NP, side, side, C] float64 / float32
+        (mask: only where mask != 0; the other rows of out are kept and those bots' frame
+        history does not advance).  Dead players: NaN rows."""
+        if self.pixel_state_shape is None:
+            raise RuntimeError("aigar: observe_pixel_state: no pixel state is configured (pixel_config)")
+        if out is None:
+            out = np.zeros(self.pixel_state_shape, dtype)
+        d = self._check_out(out, self.pixel_state_shape, ("float64", "float32"), "observe_pixel_state")
+        p, dev = _ptr(out)
+        if isinstance(mask, np.ndarray):
+            mask = np.ascontiguousarray(mask, np.uint8).reshape(self.NP)
+        mp, mdev = _ptr(mask)
+        self._chk(self.L.aigar_observe_pixel_state(self.h, p, 0 if d == "float64" else 1, dev, mp, mdev))
         return out
 
     def set_actions(self, cur=None, prev=None):

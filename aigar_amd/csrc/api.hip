@@ -33,6 +33,8 @@ bool observe_fuses_greedy(const Dev &d);
 void launch_policy_refrandom(const Dev &d, hipStream_t s, int skip_rate, int enable_split, int enable_eject,
                              uint64_t salt);
 int launch_observe_pixels(const Dev &d, hipStream_t s, void *out, int dtype, int side, uint64_t seed, uint8_t *ovf);
+int launch_observe_pixel_state(const Dev &d, hipStream_t s, void *out, int dtype, int side, int flags, uint64_t seed,
+                               uint8_t *ovf, const uint8_t *mask, uint32_t *hist);
 void launch_policy(const Dev &d, hipStream_t s, double ps, double pe, uint64_t salt);
 void launch_player_stats(const Dev &d, hipStream_t s, double *out);
 void launch_score_read(const Dev &d, hipStream_t s, double *out);
@@ -133,6 +135,10 @@ struct aigar_handle {
   void *d_pix = nullptr;  // host-destination staging for aigar_observe_pixels
   uint8_t *d_pix_ovf = nullptr;  // per player: frame left to the pixel kernel's second pass
   size_t pix_bytes = 0;
+  // aigar_pixel_config: the learner's pixel state (side 0: off) and, with AIGAR_PIX_LAST,
+  // every bot's previous frame [NP][side * side] as ~0x00RRGGBB (cleared = the white frame)
+  aigar_pixel_params pix{};
+  uint32_t *d_pix_hist = nullptr;
   std::vector<void *> allocs;
   char *arena = nullptr;  // aigar_create's arrays (dalloc); freed through allocs
   size_t arena_size = 0, arena_used = 0;
@@ -195,6 +201,8 @@ struct aigar_handle {
     void *obs;
     aigar_env_params envp;
     int n_greedy, n_random;
+    aigar_pixel_params pix;  // side 0: the grid row
+    uint32_t *pix_hist;
   } env_key{};
 };
 
@@ -252,6 +260,8 @@ static void free_all(aigar_handle *h) {
   h->d_pix = nullptr;
   h->d_pix_ovf = nullptr;  // (one of allocs)
   h->pix_bytes = 0;
+  if (h->d_pix_hist) (void)hipFree(h->d_pix_hist);
+  h->d_pix_hist = nullptr;
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->ev_x) (void)hipEventDestroy(h->ev_x);
@@ -577,6 +587,20 @@ static int check_device_errors(aigar_handle *h) {
   return 0;
 }
 
+static size_t pix_hist_bytes(const aigar_handle *h) {
+  return (h->pix.flags & AIGAR_PIX_LAST) ? sizeof(uint32_t) * h->d.NP * (size_t)h->pix.side * h->pix.side : 0;
+}
+// the pixel history of the listed arenas' bots (row: the B * side * side words of one arena)
+__global__ void __launch_bounds__(256) k_pix_hist_clear_arenas(uint32_t *hist, size_t row, const int *al) {
+  uint32_t *p = hist + (size_t)al[blockIdx.y] * row;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < row; i += (size_t)gridDim.x * blockDim.x) p[i] = 0;
+}
+// ... of the players with mask[i] != 0 (null: all); LL = side * side words a player
+__global__ void __launch_bounds__(256) k_pix_hist_clear_bots(uint32_t *hist, size_t LL, size_t n, const uint8_t *mask) {
+  const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (i < n && (!mask || mask[i / LL])) hist[i] = 0;
+}
+
 __global__ void k_fill_d(double *p, size_t n, double v) {
   size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
@@ -603,6 +627,7 @@ extern "C" int aigar_reset(aigar_handle *h, uint64_t seed) {
   HIPCHK(hipMemsetAsync(d.o_act_cur, 0, sizeof(double) * NP * 4, h->stream));
   for (double *p : {d.o_self_lf, d.o_self_slf, d.o_en_lf, d.o_en_slf})
     HIPCHK(hipMemsetAsync(p, 0, sizeof(double) * NP * GG, h->stream));
+  if (h->d_pix_hist) HIPCHK(hipMemsetAsync(h->d_pix_hist, 0, pix_hist_bytes(h), h->stream));
   if (d.tiled) {  // every tile's history copy is current (all zero)
     HIPCHK(hipMemsetAsync(d.t_holder, 0xFF, sizeof(int) * NP, h->stream));
     HIPCHK(hipMemsetAsync(d.t_obsby, 0xFF, sizeof(int) * NP, h->stream));
@@ -642,6 +667,11 @@ extern "C" int aigar_reset_arenas(aigar_handle *h, const int32_t *arenas, const 
   {
     Mark m(h, "reset_arenas");
     launch_reset_arenas(d, h->stream, h->d_rlist, h->d_rseed, n);
+    if (h->d_pix_hist) {
+      const size_t row = (size_t)d.B * h->pix.side * h->pix.side;
+      const unsigned nb = (unsigned)std::min<size_t>((row + 255) / 256, 256);
+      hipLaunchKernelGGL(k_pix_hist_clear_arenas, dim3(nb, n), dim3(256), 0, h->stream, h->d_pix_hist, row, h->d_rlist);
+    }
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -1212,7 +1242,11 @@ static void launch_env_decision(aigar_handle *h, hipStream_t s, const aigar_hand
     launch_tick(h->d, s, food_rounds(h), h->scr_k, h->scr_v);
   }
   launch_rewards(h->d, s, k.reward, k.prm, 1, k.skip == 0 ? 1 : 2);  // end of move_NN (bot.py:220-230)
-  launch_observe(h->d, s, k.obs, k.dtype, 0, (k.n_greedy || k.n_random) ? h->d_nnmask : nullptr);
+  const uint8_t *nn = (k.n_greedy || k.n_random) ? h->d_nnmask : nullptr;
+  if (k.pix.side)
+    (void)launch_observe_pixel_state(h->d, s, k.obs, k.dtype, k.pix.side, k.pix.flags, k.pix.color_seed, h->d_pix_ovf,
+                                     nn, k.pix_hist);
+  else launch_observe(h->d, s, k.obs, k.dtype, 0, nn);
 }
 
 extern "C" int aigar_env_step(aigar_handle *h, const double *act, int n_act, int enable_split, int skip,
@@ -1234,6 +1268,9 @@ extern "C" int aigar_env_step(aigar_handle *h, const double *act, int n_act, int
   k.envp = h->envp;
   k.n_greedy = h->n_greedy;
   k.n_random = h->n_random;
+  k.pix = h->pix;
+  k.pix_hist = h->d_pix_hist;
+  if (k.pix.side && ((uintptr_t)obs_out & 15)) return fail("env_step: the pixel state's obs_out must be 16-byte aligned");
   if (h->d.flags & AIGAR_FLAG_EVENTS)  // the event log holds the window's ticks
     hipLaunchKernelGGL(k_step_begin, dim3((h->d.A + 63) / 64), dim3(64), 0, h->stream, h->d);
   if (!h->use_graph) {
@@ -1360,6 +1397,88 @@ extern "C" int aigar_observe_pixels(aigar_handle *h, void *out, int side, uint64
   return 0;
 }
 
+static int pix_channels(const aigar_pixel_params &p) {
+  return ((p.flags & AIGAR_PIX_RGB) ? 3 : 1) * ((p.flags & AIGAR_PIX_LAST) ? 2 : 1);
+}
+
+extern "C" int aigar_pixel_config(aigar_handle *h, const aigar_pixel_params *p) {
+  if (!h) return fail("null handle");
+  aigar_pixel_params q{};
+  if (p && p->side != 0) q = *p;
+  if (q.side) {
+    if (h->d.tiled) return fail("pixel_config: a tiled handle has no pixel state");
+    if (q.side < 1 || q.side > 84) return fail("pixel_config: side must be in [1, 84], got %d", q.side);
+    if (q.flags & ~(AIGAR_PIX_RGB | AIGAR_PIX_LAST)) return fail("pixel_config: unknown flags 0x%x", q.flags);
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));  // (no replay of the graph, no reader of the history is pending)
+  if (h->env_graph) (void)hipGraphExecDestroy(h->env_graph);
+  h->env_graph = nullptr;
+  if (q.side && !h->d_pix_ovf) {
+    h->d_pix_ovf = dalloc<uint8_t>(h, h->d.NP);
+    if (!h->d_pix_ovf) return fail("out of device memory");
+  }
+  const size_t had = pix_hist_bytes(h);
+  h->pix = q;
+  const size_t want = pix_hist_bytes(h);
+  if (want != had) {
+    if (h->d_pix_hist) (void)hipFree(h->d_pix_hist);
+    h->d_pix_hist = nullptr;
+    if (want && hipMalloc((void **)&h->d_pix_hist, want) != hipSuccess) {
+      h->pix = aigar_pixel_params{};
+      return fail("pixel_config: out of device memory (%zu bytes of frame history)", want);
+    }
+  }
+  if (want) HIPCHK(hipMemsetAsync(h->d_pix_hist, 0, want, h->stream));
+  return 0;
+}
+
+extern "C" int aigar_pixel_state_len(aigar_handle *h) {
+  return h ? h->pix.side * h->pix.side * (h->pix.side ? pix_channels(h->pix) : 0) : -1;
+}
+
+extern "C" int aigar_observe_pixel_state(aigar_handle *h, void *out, int dtype, int on_device, const uint8_t *mask,
+                                         int mask_on_device) {
+  if (!h || !out) return fail("null argument");
+  if (!h->pix.side) return fail("observe_pixel_state: no pixel state is configured (aigar_pixel_config)");
+  if (dtype != 0 && dtype != 1) return fail("dtype must be 0 (float64) or 1 (float32)");
+  if (on_device && ((uintptr_t)out & 15)) return fail("observe_pixel_state: a device out must be 16-byte aligned");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const size_t bytes = (size_t)h->d.NP * aigar_pixel_state_len(h) * (dtype == 0 ? 8 : 4);
+  void *dst = out;
+  if (!on_device) {
+    if (bytes > h->pix_bytes) {
+      if (h->d_pix) HIPCHK(hipFree(h->d_pix));
+      h->d_pix = nullptr;
+      h->pix_bytes = 0;
+      HIPCHK(hipMalloc(&h->d_pix, bytes));
+      h->pix_bytes = bytes;
+    }
+    dst = h->d_pix;
+  }
+  const uint8_t *m = mask;
+  if (mask && !mask_on_device) {
+    HIPCHK(hipMemcpyAsync(h->d_mask, mask, (size_t)h->d.NP, hipMemcpyHostToDevice, h->stream));
+    m = h->d_mask;
+  }
+  if (!on_device && mask)  // rows of masked-out bots are left as the caller's buffer has them
+    HIPCHK(hipMemcpyAsync(h->d_pix, out, bytes, hipMemcpyHostToDevice, h->stream));
+  {
+    Mark mk(h, "observe_pixel_state");
+    if (launch_observe_pixel_state(h->d, h->stream, dst, dtype, h->pix.side, h->pix.flags, h->pix.color_seed,
+                                   h->d_pix_ovf, m, h->d_pix_hist))
+      return fail("bad pixel state launch");
+  }
+  HIPCHK(hipGetLastError());
+  if (!on_device) {
+    HIPCHK(hipMemcpyAsync(out, h->d_pix, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return check_device_errors(h);
+  }
+  if (mask && !mask_on_device) HIPCHK(hipStreamSynchronize(h->stream));  // caller may reuse its mask
+  return 0;
+}
+
 __global__ void k_set_actions(Dev d, const double *cur, const double *prev) {
   size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (i >= (size_t)d.NP * 4) return;
@@ -1408,6 +1527,11 @@ extern "C" int aigar_reset_bots(aigar_handle *h, const uint8_t *mask, int on_dev
   }
   const size_t n = (size_t)h->d.NP * h->d.G * h->d.G;
   hipLaunchKernelGGL(k_reset_bots, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d, m);
+  if (h->d_pix_hist) {
+    const size_t LL = (size_t)h->pix.side * h->pix.side, np = LL * h->d.NP;
+    hipLaunchKernelGGL(k_pix_hist_clear_bots, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, h->stream,
+                       h->d_pix_hist, LL, np, m);
+  }
   HIPCHK(hipGetLastError());
   if (mask && !on_device) HIPCHK(hipStreamSynchronize(h->stream));  // caller may reuse its buffer
   return 0;
@@ -1883,6 +2007,10 @@ extern "C" int aigar_load_state(aigar_handle *h, int arena, const aigar_state *s
                      __builtin_nan(""));
   for (double *p : {d.o_self_lf, d.o_self_slf, d.o_en_lf, d.o_en_slf})
     HIPCHK(hipMemsetAsync(p + p0 * GG, 0, 8 * B * GG, h->stream));
+  if (h->d_pix_hist) {
+    const size_t LL = (size_t)h->pix.side * h->pix.side;
+    HIPCHK(hipMemsetAsync(h->d_pix_hist + p0 * LL, 0, sizeof(uint32_t) * B * LL, h->stream));
+  }
   if (d.tiled) {
     HIPCHK(hipMemsetAsync(d.t_holder, 0xFF, sizeof(int) * d.NP, h->stream));
     HIPCHK(hipMemsetAsync(d.t_obsby, 0xFF, sizeof(int) * d.NP, h->stream));

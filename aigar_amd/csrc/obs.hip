@@ -1363,6 +1363,9 @@ void launch_player_fov_list(const Dev &d, hipStream_t s, const int *al, int n) {
 // then drawn one by one: lane 0 runs the span recurrence into a half-width
 // table, all lanes fill the spans, lane 0 runs the anti-aliased rim (its
 // blends are order-dependent).
+// k_observe_pixel_state is the same kernel writing a CNN learner's state
+// (bot.py:276-282: (frame - 255) / 100, channels last) with a player mask and
+// the bot's previous frame.
 #include "pixels.inc"
 
 #include "obs_wide.inc"

@@ -178,11 +178,72 @@ __device__ void pix_aa_rim(uint32_t *fr, int L, int xc, int yc, int rad, uint32_
   }
 }
 
-// out: DT 0 float64 / 1 float32 grayscale [player][x][y]; 2 uint8 RGB [player][x][y][3]
+// The learner's pixel state (bot.py:276-282: (rgb_values - 255) / 100) of one packed pixel,
+// C = 1 (grayscale: the fp64 weighted average, then the expression in fp64) or 3 (RGB:
+// the reference subtracts from a uint8 array, which wraps: ((b + 1) & 255) / 100).
+// T: the output type, rounded once from the fp64 value.
+template <class T>
+struct PixSt {
+  T c0, c1, c2;  // (grayscale: c0 alone)
+};
+template <class T, bool RGB>
+__device__ __forceinline__ PixSt<T> pix_state(uint32_t p) {
+  PixSt<T> v;
+  if (RGB) {
+    v.c0 = (T)((double)(((p >> 16) + 1) & 255) / 100.0);
+    v.c1 = (T)((double)(((p >> 8) + 1) & 255) / 100.0);
+    v.c2 = (T)((double)((p + 1) & 255) / 100.0);
+  } else {
+    const double R = (p >> 16) & 255, G = (p >> 8) & 255, B = p & 255;
+    const double g = ((R * 0.298 + G * 0.587) + B * 0.114) / ((0.298 + 0.587) + 0.114);
+    v.c0 = v.c1 = v.c2 = (T)((g - 255.0) / 100.0);
+  }
+  return v;
+}
+// one pixel's channels [current C | previous C when LAST], contiguous at o: the widest
+// store the row layout keeps aligned (a row starts on a 16-byte boundary, a pixel's 2 or
+// 6 elements on a pair boundary; 3 elements leave only the element's own alignment)
+template <class T, bool RGB, bool LAST>
+__device__ __forceinline__ void pix_store(T *o, const PixSt<T> &a, const PixSt<T> &b) {
+  typedef T T2 __attribute__((ext_vector_type(2)));
+  auto pair = [&](int k, T x, T y) {
+    T2 w;
+    w.x = x;
+    w.y = y;
+    *(T2 *)(o + k) = w;
+  };
+  if (RGB && LAST) {
+    pair(0, a.c0, a.c1);
+    pair(2, a.c2, b.c0);
+    pair(4, b.c1, b.c2);
+  } else if (RGB) {
+    o[0] = a.c0;
+    o[1] = a.c1;
+    o[2] = a.c2;
+  } else if (LAST) {
+    pair(0, a.c0, b.c0);
+  } else {
+    o[0] = a.c0;
+  }
+}
+
+// ST 0 (k_observe_pixels), out: DT 0 float64 / 1 float32 grayscale [player][x][y]; 2 uint8
+// RGB [player][x][y][3].
+// ST = PIX_ST | flags (k_observe_pixel_state), out: DT 0 float64 / 1 float32 pixel state
+// [player][x][y][CT], CT = C (1, or 3 with PIX_ST_RGB) current channels, then with
+// PIX_ST_LAST the C channels of this bot's previous pixel state.  mask (may be null): a
+// player whose byte is 0 is not touched, in either pass.  hist [player][x][y]: the previous
+// frame as ~0x00RRGGBB (so cleared memory is the white frame, whose state is zero); it is
+// read and rewritten by the lane that writes the pixel, only where a row is written, so a
+// frame the first pass leaves to the second advances once.  A dead player's row is all
+// NaN and its history stays.
 // OCAP < PIX_OCAP: first pass, every player; a frame with more objects sets ovf[player]
 // and is left to the OCAP == PIX_OCAP pass, which draws only those players.
-template <int DT, int OCAP>
-__global__ void __launch_bounds__(64) k_observe_pixels(Dev d, void *out, int L, uint64_t cseed, uint8_t *ovf) {
+constexpr int PIX_ST = 1, PIX_ST_RGB = 2, PIX_ST_LAST = 4;
+template <int DT, int OCAP, int ST>
+__device__ __forceinline__ void observe_pixels_body(const Dev &d, void *out, int L, uint64_t cseed, uint8_t *ovf,
+                                                    const uint8_t *mask, uint32_t *hist) {
+  constexpr int C = (ST & PIX_ST_RGB) ? 3 : 1, CT = (ST & PIX_ST_LAST) ? 2 * C : C;
   // per drawn object: the sort key (mass; after the sort, the frame position), the order
   // key kind << 56 | seq (after the sort: kind << 56 | drawn radius << 32 | colour), slot
   __shared__ union {
@@ -199,9 +260,17 @@ __global__ void __launch_bounds__(64) k_observe_pixels(Dev d, void *out, int L, 
   __shared__ int n_obj, bad;
   const int gp = blockIdx.x, lane = threadIdx.x, NP = d.NP, a = gp / d.B, LL = L * L;
   const size_t obase = (size_t)gp * LL;
+  if (ST && mask && !mask[gp]) return;  // (both passes: its flag may be an earlier call's)
   if (OCAP == PIX_OCAP && !ovf[gp]) return;  // drawn by the first pass
   if (!d.p_alive[gp]) {  // getStateRepresentation: None for dead players
     if (lane == 0) ovf[gp] = 0;
+    if (ST) {
+      for (size_t i = lane; i < (size_t)LL * CT; i += 64) {
+        if (DT == 0) ((double *)out)[obase * CT + i] = __builtin_nan("");
+        else ((float *)out)[obase * CT + i] = __builtin_nanf("");
+      }
+      return;
+    }
     for (int i = lane; i < LL; i += 64) {
       if (DT == 0) ((double *)out)[obase + i] = __builtin_nan("");
       else if (DT == 1) ((float *)out)[obase + i] = __builtin_nanf("");
@@ -404,7 +473,12 @@ __global__ void __launch_bounds__(64) k_observe_pixels(Dev d, void *out, int L, 
         if (dx <= hw[dy]) fr[yy * L + xx] = col;  // (clears a batch tag too)
       }
     __syncthreads();
-    if (lane == 0) pix_aa_rim(fr, L, px, py, rad, kind == 2 ? 0u : col);  // viruses: black rim
+    if (lane == 0) {  // viruses: black rim
+      // (the state kernels inline the rim: as a call it costs them a stack frame next to
+      // their scalar spills; k_observe_pixels keeps the compiler's choice, and its code)
+      if (ST) [[clang::always_inline]] pix_aa_rim(fr, L, px, py, rad, kind == 2 ? 0u : col);
+      else pix_aa_rim(fr, L, px, py, rad, kind == 2 ? 0u : col);
+    }
     __syncthreads();
     k++;
   }
@@ -412,6 +486,21 @@ __global__ void __launch_bounds__(64) k_observe_pixels(Dev d, void *out, int L, 
   for (int i = lane; i < LL; i += 64) {
     const int xx = i / L, yy = i - xx * L;
     const uint32_t p = fr[yy * L + xx];
+    if (ST) {
+      uint32_t q = 0xFFFFFFu;
+      if (ST & PIX_ST_LAST) {
+        uint32_t *hp = hist + obase + i;
+        q = ~*hp & 0xFFFFFFu;
+        *hp = ~p & 0xFFFFFFu;
+      }
+      if (DT == 0)
+        pix_store<double, C == 3, CT != C>((double *)out + (obase + i) * CT, pix_state<double, C == 3>(p),
+                                           pix_state<double, C == 3>(q));
+      else
+        pix_store<float, C == 3, CT != C>((float *)out + (obase + i) * CT, pix_state<float, C == 3>(p),
+                                          pix_state<float, C == 3>(q));
+      continue;
+    }
     const double R = (p >> 16) & 255, G = (p >> 8) & 255, B = p & 255;
     if (DT == 2) {
       uint8_t *o = (uint8_t *)out + 3 * (obase + i);
@@ -425,6 +514,15 @@ __global__ void __launch_bounds__(64) k_observe_pixels(Dev d, void *out, int L, 
     }
   }
 }
+template <int DT, int OCAP>
+__global__ void __launch_bounds__(64) k_observe_pixels(Dev d, void *out, int L, uint64_t cseed, uint8_t *ovf) {
+  observe_pixels_body<DT, OCAP, 0>(d, out, L, cseed, ovf, nullptr, nullptr);
+}
+template <int DT, int OCAP, int ST>
+__global__ void __launch_bounds__(64) k_observe_pixel_state(Dev d, void *out, int L, uint64_t cseed, uint8_t *ovf,
+                                                            const uint8_t *mask, uint32_t *hist) {
+  observe_pixels_body<DT, OCAP, ST>(d, out, L, cseed, ovf, mask, hist);
+}
 int launch_observe_pixels(const Dev &d, hipStream_t s, void *out, int dtype, int side, uint64_t seed, uint8_t *ovf) {
   if (side < 1 || side > PIX_LMAX || dtype < 0 || dtype > 2) return -1;
   const size_t lds = (size_t)side * side * 4;
@@ -437,6 +535,34 @@ int launch_observe_pixels(const Dev &d, hipStream_t s, void *out, int dtype, int
   if (dtype == 0) PIX_LAUNCH(0);
   else if (dtype == 1) PIX_LAUNCH(1);
   else PIX_LAUNCH(2);
+#undef PIX_LAUNCH
+  return 0;
+}
+// flags: AIGAR_PIX_RGB | AIGAR_PIX_LAST (hist: [NP][side * side] words when LAST, else unused)
+int launch_observe_pixel_state(const Dev &d, hipStream_t s, void *out, int dtype, int side, int flags, uint64_t seed,
+                               uint8_t *ovf, const uint8_t *mask, uint32_t *hist) {
+  if (side < 1 || side > PIX_LMAX || dtype < 0 || dtype > 1 || (flags & ~(AIGAR_PIX_RGB | AIGAR_PIX_LAST))) return -1;
+  if ((flags & AIGAR_PIX_LAST) && !hist) return -1;
+  const size_t lds = (size_t)side * side * 4;
+#define PIX_LAUNCH(DT, ST)                                                                                       \
+  do {                                                                                                           \
+    hipLaunchKernelGGL((k_observe_pixel_state<DT, PIX_OCAP_FAST, ST>), dim3(d.NP), dim3(64), lds, s, d, out, side, \
+                       seed, ovf, mask, hist);                                                                   \
+    hipLaunchKernelGGL((k_observe_pixel_state<DT, PIX_OCAP, ST>), dim3(d.NP), dim3(64), lds, s, d, out, side, seed, \
+                       ovf, mask, hist);                                                                         \
+  } while (0)
+#define PIX_FLAGS(DT)                                                   \
+  do {                                                                  \
+    switch (flags) {                                                    \
+      case 0: PIX_LAUNCH(DT, PIX_ST); break;                            \
+      case AIGAR_PIX_RGB: PIX_LAUNCH(DT, PIX_ST | PIX_ST_RGB); break;   \
+      case AIGAR_PIX_LAST: PIX_LAUNCH(DT, PIX_ST | PIX_ST_LAST); break; \
+      default: PIX_LAUNCH(DT, PIX_ST | PIX_ST_RGB | PIX_ST_LAST);       \
+    }                                                                   \
+  } while (0)
+  if (dtype == 0) PIX_FLAGS(0);
+  else PIX_FLAGS(1);
+#undef PIX_FLAGS
 #undef PIX_LAUNCH
   return 0;
 }

@@ -19,6 +19,12 @@ each tick against the lastMass of the previous decision); the observation is
 Bot.getStateRepresentation of every NN player (NaN rows for dead players, where
 the reference returns None).
 
+Pixel states: with CNN_REPR and CNN_P_REPR (or `pixels=(side, rgb, last)`) the
+state is the reference's pixel frame through (frame - 255) / 100 (bot.py:276-282),
+`obs` is [NP, side, side, C] of `pixel_dtype`, and everything above holds for it:
+masked to the NN players, NaN rows for dead players, the previous frame (`last`)
+reset with the bot, the same one graph replay per decision.
+
 Episodes (aigar.py:833-837, 876-887): an arena's episode ends after the
 decision in which its tick count passes RESET_LIMIT - FRAME_SKIP_RATE + 2 (the
 reference's collector test); the arena is then reset (Model.resetModel + the
@@ -40,13 +46,13 @@ import numpy as np
 
 from . import _abi
 from ._lib import Stepper
-from .model import obs_masks
+from .model import obs_masks, pixel_params
 
 
 class AgarVecEnv:
     def __init__(self, n_players, parameters=None, n_arenas=1, virus=None, field_size=0, max_pellets=-1.0,
                  max_viruses=-1.0, device=0, torch_stream=True, roles=None, reset_limit=None, desync=True, seed=0,
-                 score=False):
+                 score=False, pixels=None, pixel_dtype=None):
         import torch
         self.torch = torch
         self.parameters = parameters
@@ -93,7 +99,13 @@ class AgarVecEnv:
         self.desync = bool(desync) and self.reset_limit > 0 and n_arenas > 1
         self.age = np.zeros(n_arenas, np.int64)
         self._resets = 0
-        self.obs = torch.empty((self.NP, self.stepper.obs_len), dtype=torch.float64, device=self.dev)
+        self.pixels = tuple(pixels) if pixels is not None else pixel_params(parameters)
+        if self.pixels is not None:
+            side, rgb, last = self.pixels
+            self.stepper.pixel_config(side, rgb=rgb, last=last, color_seed=self.seed)
+            self.obs = torch.empty(self.stepper.pixel_state_shape, dtype=pixel_dtype or torch.float32, device=self.dev)
+        else:
+            self.obs = torch.empty((self.NP, self.stepper.obs_len), dtype=torch.float64, device=self.dev)
         self._mask = torch.zeros(self.NP, dtype=torch.uint8, device=self.dev)  # (persistent: read on the stepper's stream)
         self._r = torch.empty(self.NP, dtype=torch.float64, device=self.dev)
         self._act = {}  # n_act -> persistent action buffer (the decision graph is keyed by its address)
@@ -162,8 +174,14 @@ class AgarVecEnv:
     def observe(self):
         """A fresh tensor: the device buffer is rewritten by the next decision, so
         (s, a, r, s') tuples must not alias it (self.obs is that buffer)."""
-        self.stepper.observe(self.obs, mask=self._nn_u8 if self._mixed else None)
+        self._observe(self._nn_u8 if self._mixed else None)
         return self.obs.clone()
+
+    def _observe(self, mask):
+        if self.pixels is not None:
+            self.stepper.observe_pixel_state(self.obs, mask=mask)
+        else:
+            self.stepper.observe(self.obs, mask=mask)
 
     def _episode_ends(self):
         """Reset the arenas that reached RESET_LIMIT; returns the per-player done mask."""
@@ -193,7 +211,7 @@ class AgarVecEnv:
         # the new episodes' first states (NN players of the reset arenas)
         nn_reset = (mask & (self.roles == _abi.ROLE_NN)).astype(np.uint8)
         self._mask.copy_(torch.as_tensor(nn_reset))
-        self.stepper.observe(self.obs, mask=self._mask)
+        self._observe(self._mask)
         return done
 
     def step(self, actions):
@@ -212,7 +230,7 @@ class AgarVecEnv:
         if self._scored:
             self._ret += torch.where(self.nn, reward, torch.zeros_like(reward))
         done = self._episode_ends()
-        alive = ~torch.isnan(self.obs[:, 0]) & self.nn
+        alive = ~torch.isnan(self.obs.view(self.NP, -1)[:, 0]) & self.nn
         return self.obs.clone(), reward, alive, done
 
     def _read_score(self):
@@ -269,7 +287,7 @@ class AgarVecEnv:
         self.stepper.rewards(self.reward_params, update_last=True, out=self._r)
         reward += torch.nan_to_num(self._r)
         obs = self.observe()
-        alive = ~torch.isnan(obs[:, 0]) & self.nn
+        alive = ~torch.isnan(obs.view(self.NP, -1)[:, 0]) & self.nn
         return obs, reward, alive
 
     def close(self):

@@ -89,6 +89,22 @@ def obs_masks(parameters):
     return ch, ex, int(getattr(parameters, "GRID_SQUARES_PER_FOV", 11))
 
 
+def pixel_params(parameters):
+    """(side, rgb, last) of the pixel state a CNN learner gets (CNN_P_REPR, bot.py:276-282;
+    side as rgbGenerator.py:16-21), or None when the parameters ask for another state."""
+    g = lambda n: getattr(parameters, n, False)  # noqa: E731
+    if parameters is None or not (getattr(parameters, "GRID_VIEW_ENABLED", True) and g("CNN_REPR") and
+                                  g("CNN_P_REPR")):
+        return None
+    if g("CNN_USE_L1"):
+        side = parameters.CNN_INPUT_DIM_1
+    elif g("CNN_USE_L2"):
+        side = parameters.CNN_INPUT_DIM_2
+    else:
+        side = parameters.CNN_INPUT_DIM_3
+    return int(side), bool(g("CNN_P_RGB")), bool(g("CNN_LAST_GRID"))
+
+
 def reference_parameters():
     """The reference's networkParameters module when its code is loaded in this
     process (model.py imports it, then builds Field(virusEnabled) without passing

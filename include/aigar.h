@@ -305,6 +305,40 @@ int aigar_policy_random_bots(aigar_handle *h);
  * per-player / per-pellet colours (the reference draws them from numpy RNG,
  * cell.py:31, player.py:39).  Dead players get zeros (uint8) / NaN (gray). */
 int aigar_observe_pixels(aigar_handle *h, void *out, int side, uint64_t color_seed, int dtype, int on_device);
+/* The pixel state of a CNN learner (CNN_P_REPR, bot.py:276-282): the frame above
+ * through the reference's (rgb_values - 255) / 100, written by the kernel itself.
+ * Grayscale (1 channel): (gray - 255) / 100 in fp64.  AIGAR_PIX_RGB (3 channels): the
+ * reference subtracts from a uint8 array, which wraps, so a byte b becomes
+ * ((b + 1) & 255) / 100 (white 255 -> 0.0, black 0 -> 0.01).  AIGAR_PIX_LAST doubles
+ * the channels, [current C | previous C]: the previous channels are the current
+ * channels of this bot's previous pixel-state observation, and the zero state (the
+ * white frame) before its first one.  (The reference's own CNN_LAST_GRID code cannot
+ * run, bot.py:102, 281-282; this is what its networks are built for, network.py:156-165.)
+ * The history advances only for the bots a call observes (alive, mask != 0), and is
+ * cleared wherever the grid history is: aigar_reset, aigar_reset_arenas,
+ * aigar_load_state, aigar_reset_bots.
+ *
+ * aigar_pixel_config sets the mode of the handle (NULL or side 0: off), allocates and
+ * clears the history, and drops the captured decision graph; side must be in [1, 84];
+ * tiled handles are refused.  aigar_pixel_state_len: side * side * channels (0: off).
+ * aigar_observe_pixel_state: out[A*B][side][side][channels] (surfarray order [x][y],
+ * channels last; a device out must be 16-byte aligned), for the players with
+ * mask[i] != 0 (NULL: all): the other rows of out and those bots' history are left
+ * as they are.  Dead players get NaN rows (all channels) and keep their history.
+ * While a pixel config is set, aigar_env_step writes this state (obs_out
+ * [A*B][side][side][channels], the NN players' rows in a mixed population) instead of
+ * the grid row, still in its one graph. */
+#define AIGAR_PIX_RGB  0x1   /* CNN_P_RGB: 3 channels, else 1 (grayscale)          */
+#define AIGAR_PIX_LAST 0x2   /* + the bot's previous frame (CNN_LAST_GRID's intent) */
+typedef struct aigar_pixel_params {
+  int32_t side;          /* CNN_INPUT_DIM_1/2/3 (rgbGenerator.py:16-21)            */
+  int32_t flags;         /* AIGAR_PIX_*                                            */
+  uint64_t color_seed;   /* as aigar_observe_pixels                                */
+} aigar_pixel_params;
+int aigar_pixel_config(aigar_handle *h, const aigar_pixel_params *p);
+int aigar_pixel_state_len(aigar_handle *h);
+int aigar_observe_pixel_state(aigar_handle *h, void *out, int dtype, int on_device, const uint8_t *mask,
+                              int mask_on_device);
 /* bot.currentAction / bot.lastAction used by the action extras: [A*B][4] each (may be NULL). */
 int aigar_set_actions(aigar_handle *h, const double *cur, const double *prev, int on_device);
 /* Bot.reset (bot.py:125-164) for the players with mask[i] != 0 (NULL: all): the
