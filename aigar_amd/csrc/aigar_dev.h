@@ -98,8 +98,7 @@ enum : uint32_t {
   ERR_TILE_OBS = 2048,    // a tile observed a bot whose view reaches beyond its held pellets
   ERR_TILE_PASSES = 4096,  // a device-bounded tiled tick ended with owned cells undone
   ERR_PREDICT = 8192,      // updatePlayers made other counts than k_players' arena block predicted (head_counts)
-  ERR_TILE_HANDOFF = 16384,  // more dead bots to hand off in one tick than a message has hand-off slots
-  ERR_CLAIM = 32768  // a bounded cell-claim loop (shared-cell kernels) ran out with claims left
+  ERR_TILE_HANDOFF = 16384  // more dead bots to hand off in one tick than a message has hand-off slots
 };
 enum : uint32_t { WARN_NEW_VIRUS_EATS = 1, WARN_DEAD_VIRUS = 2, WARN_TILE_OBS = 4 };
 enum : uint32_t { DIRTY_VIRUS = 1, DIRTY_BLOB = 2 };
@@ -188,7 +187,6 @@ struct Dev {
   uint32_t obs_ch, obs_ex;
   int flags;
   int pp_par;  // playerPlayerOverlap may run as independent groups (pp_pass; AIGAR_PP_SERIAL=1: never)
-  int share_cells;  // launch choice: k_food_prep / k_pp_active share a block's cells (Greedy populations)
   ArenaCtl *ctl;
   // players [NP]
   int *p_alive, *p_respawn, *p_ncells, *p_split, *p_eject, *p_pend;

@@ -334,7 +334,6 @@ extern "C" int aigar_create(const aigar_config *cfg, aigar_handle **out) {
   if (const char *u = getenv("AIGAR_RUN_UNROLL")) h->run_unroll = std::max(1, std::min(64, atoi(u)));
   if (getenv("AIGAR_TILE_GRAPH")) h->tile_graph = true;
   h->d.pp_par = getenv("AIGAR_PP_SERIAL") ? 0 : 1;
-  h->d.share_cells = 0;  // (aigar_run sets it in the graph it captures for the Greedy population)
   // tuning knob: a fixed number of reservation rounds for every population
   if (const char *r = getenv("AIGAR_FOOD_ROUNDS")) h->rounds = std::max(1, std::min(16, atoi(r)));
   Dev &d = h->d;
@@ -582,7 +581,7 @@ static int check_device_errors(aigar_handle *h) {
                   "16 worklist cap, 32 observation cap, 64 candidate cap, 128 slot, 256 pixel-frame object cap, "
                   "512 tile message cap, 1024 tile record lookup, 2048 tile view beyond the held pellets, "
                   "4096 tiled tick ended with undone cells, 8192 new-cell / blob counts not as predicted, "
-                  "16384 more dead bots to hand off than hand-off slots, 32768 cell claims left at the claim bound)",
+                  "16384 more dead bots to hand off than hand-off slots)",
                   ctl[a].err, a);
   return 0;
 }
@@ -791,13 +790,9 @@ static void launch_env_step(aigar_handle *h, hipStream_t s, const aigar_run_para
   const RandomPolicy rp{p.policy == AIGAR_POLICY_RANDOM, p.p_split, p.p_eject, p.seed};
 #endif
   if (p.policy == AIGAR_POLICY_GREEDY && !policy_done) launch_policy_greedy(h->d, s, p.greedy_split ? 1 : 0, nullptr, -1);
-  // a Greedy population splits by choice: many players hold several cells, and the
-  // eat-phase preparation and the pp activity test share a block's cells among its
-  // waves (r05 v41: greedy 16.9 -> 18.2 M env-steps/s; the random population keeps
-  // the one-wave-per-player kernels, for which the sharing cost ~2 %)
-  Dev dt = h->d;
-  dt.share_cells = p.policy == AIGAR_POLICY_GREEDY ? 1 : 0;
-  launch_tick(dt, s, food_rounds(h), h->scr_k, h->scr_v, &rp);
+  // (a Greedy population splits by choice and many players hold several cells: the eat-phase
+  // preparation and the pp activity test walk all of a player's cells at once, tick.hip prep_multi)
+  launch_tick(h->d, s, food_rounds(h), h->scr_k, h->scr_v, &rp);
   if (out) launch_observe(h->d, s, out, dtype, 0, nullptr, fuse_next ? (p.greedy_split ? 1 : 0) : -1);  // epoch 0: the device-side epoch
 }
 // aigar_run's unrolled graph may carry each step's Greedy moves in the step before

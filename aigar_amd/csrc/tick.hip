@@ -1535,15 +1535,28 @@ __device__ __forceinline__ void cgrid_count_cell(const Dev &d, int a, size_t ci,
 // when lds is given, to lds[0..n]; the counts are re-zeroed for the next tick;
 // bits (optional): one bit per non-empty bucket, 16 per thread (bucket b at bit
 // b % 16 of bits[b / 16]: a little-endian bitmap)
-__device__ void count_scan_256(int *cnt, int n, int *start, int *lds, uint16_t *bits) {
+// mid: called by every thread once the count loads are issued and before their
+// first use -- loads the caller issues there travel with the scan's
+struct NoMid {
+  __device__ void operator()() const {}
+};
+template <class Mid = NoMid>
+__device__ void count_scan_256(int *cnt, int n, int *start, int *lds, uint16_t *bits, Mid mid = Mid()) {
   __shared__ int wsum[4];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int4 *c4 = reinterpret_cast<const int4 *>(cnt);
   int v[16], sum = 0;
+  int4 q4[4];
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     const int j = tid * 16 + 4 * k;
-    int4 q = j < n ? c4[j >> 2] : make_int4(0, 0, 0, 0);
+    q4[k] = j < n ? c4[j >> 2] : make_int4(0, 0, 0, 0);
+  }
+  mid();
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int j = tid * 16 + 4 * k;
+    const int4 q = q4[k];
     v[4 * k] = j < n ? q.x : 0;
     v[4 * k + 1] = j + 1 < n ? q.y : 0;
     v[4 * k + 2] = j + 2 < n ? q.z : 0;
@@ -1564,7 +1577,15 @@ __device__ void count_scan_256(int *cnt, int n, int *start, int *lds, uint16_t *
     if (lane >= off) inc += t;
   }
   if (lane == 63) wsum[w] = inc;
-  __syncthreads();
+  if constexpr (std::is_same<Mid, NoMid>::value) {
+    __syncthreads();
+  } else {
+    // only wsum crosses the barrier: order LDS alone, so the loads mid() issued stay in
+    // flight over it (a full workgroup fence waits for every outstanding global access)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+  }
   int run = inc - sum;
   for (int k = 0; k < w; k++) run += wsum[k];
   const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
@@ -1583,9 +1604,10 @@ __device__ void count_scan_256(int *cnt, int n, int *start, int *lds, uint16_t *
     if (lds) lds[n] = total;
   }
 }
-__device__ void cgrid_scan_block(const Dev &d, int a) {
+template <class Mid = NoMid>
+__device__ __forceinline__ void cgrid_scan_block(const Dev &d, int a, Mid mid = Mid()) {
   const int cc = cgrid_cols(d);
-  count_scan_256(cgrid_counts(d, a, 0), cc * cc, d.cstart + (size_t)a * (d.H + 1), nullptr, nullptr);
+  count_scan_256(cgrid_counts(d, a, 0), cc * cc, d.cstart + (size_t)a * (d.H + 1), nullptr, nullptr, mid);
 }
 // step 3 for player gp's n cells (k_food_commit round 1)
 __device__ __forceinline__ void cgrid_place_player(const Dev &d, int gp, int n) {
@@ -1842,7 +1864,6 @@ __device__ __forceinline__ void vb_active_blob(const Dev &d, int gb) {
 // the blob grid's second step (blob_count): one block per arena loads the
 // counts (re-zeroing them for the next tick), scans them in LDS, stores the
 // bucket starts and places every ranked blob
-__device__ void count_scan_256(int *cnt, int n, int *start, int *lds, uint16_t *bits);
 __device__ void blob_grid_place(const Dev &d, int a, int *cnt) {
   const int tid = threadIdx.x, T = blockDim.x, s = d.cshift;
   const int cc = (d.cols + (1 << s) - 1) >> s;
@@ -2436,7 +2457,6 @@ constexpr int PREP_WAVES = 1;  // wavefronts per player (wave h takes cells h, h
 // pass once the owners' outcomes arrived).  Cells that cannot touch a held food
 // are skipped.  resume: only cells not yet final (f_done != 1) are prepared.
 __device__ __forceinline__ double tile_rall() { return sqrt(kMaxMass / kPi) * (1 + 1e-9); }  // any cell's radius bound
-template <bool SHARE>
 __global__ void __launch_bounds__(256, 4) k_food_prep(Dev d, int rounds, int resume) {
   FLOOR(4);
   TILE_GATE(d);
@@ -2445,49 +2465,55 @@ __global__ void __launch_bounds__(256, 4) k_food_prep(Dev d, int rounds, int res
   __shared__ int s_idx[4][PREP_CAND];
   __shared__ uint8_t s_sel[4][PREP_CAND];
   __shared__ uint64_t s_bm[4][64];  // each wave's arena blob bitmap (blob_grid_place)
-  // blocks [0, A) when not resuming first run the player-cell grid's scan for
-  // arena blockIdx.x (cgrid_scan_block; read by the commit round), then their
-  // players: as extra blocks they were the 1025th block of a launch whose 1024
-  // fill the GPU once, and started ~5 us late
-  if (!resume && (int)blockIdx.x < d.A) cgrid_scan_block(d, blockIdx.x);
+  // blocks [0, A) when not resuming also run the player-cell grid's scan for
+  // arena blockIdx.x (cgrid_scan_block; read by the commit round): as extra
+  // blocks they were the 1025th block of a launch whose 1024 fill the GPU once,
+  // and started ~5 us late.  The scan runs between the player's load round and
+  // its first use (below), so these four waves do not start a scan late.
+  const bool head = !resume && (int)blockIdx.x < d.A;
   PT_BEGIN(0);
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int wi = xcd_block(blockIdx.x, gridDim.x) * 4 + w, gp = wi / PREP_WAVES,
             h = wi - gp * PREP_WAVES;
-  static_assert(PREP_WAVES == 1, "the block's cell sharing assumes one wave per player");
-  // SHARE (Greedy populations, many multi-cell players): a block's four players
-  // share their further cells -- a wave prepares its player's first cell, then
-  // claims cells 1 .. n-1 of its own player and of the block's other players of
-  // the same arena (q_next: LDS claim counters), so a multi-cell player's cells
-  // run side by side on the waves whose players had one (cells are independent
-  // here: each reserves with its own priority).  A wave that reads a count before
-  // its owner published it skips that player; the owner then claims its cells
-  // itself.  (Under the random population few players have several cells and the
-  // claims cost more than they save: ~1.5 us on this kernel, r05 v41.)
-  __shared__ int q_n[4], q_next[4], q_a[4];
-  if constexpr (SHARE) {
-    if (lane == 0) {
-      q_n[w] = 0;
-      q_next[w] = 1;  // (cell 0: its owner, unclaimed)
-    }
-    __syncthreads();
-  }
+  static_assert(PREP_WAVES == 1, "prep_multi assumes one wave per player");
   if (gp < d.NP && gp % d.B == 0 && h == 0 && lane == 0) d.ctl[gp / d.B].food_undone[1] = 0;  // round 1's failure count
-  if (gp >= d.NP) return;
-  // this wave's first list row rides the liveness / count load round (the row
-  // exists whatever the count: h < PREP_WAVES <= kMaxCells)
-  const int s_first = uni((int)d.p_list[h * d.NP + gp]);
-  s_bm[w][lane] = d.bmap[(size_t)(gp / d.B) * 64 + lane];  // (read after the pellet walk: its waits cover it)
-  const bool alive = d.p_alive[gp];
-  const int NP = d.NP, a = gp / d.B;
+  if (gp >= d.NP && !head) return;
+  // the player's load round (a head block's wave past the last player loads the
+  // last player's: every address is valid, and it leaves after the scan).
+  // This wave's first list row rides the liveness / count load round (the row
+  // exists whatever the count: h < PREP_WAVES <= kMaxCells); lane k also takes
+  // list row k, for the players with several cells (prep_multi).
+  const int gpl = min(gp, d.NP - 1);
+  const int NP = d.NP, a = gpl / d.B;
+  const int v_first = d.p_list[h * NP + gpl];
+  const int v_slot = d.p_list[(lane < kMaxCells ? lane : 0) * NP + gpl];
+  s_bm[w][lane] = d.bmap[(size_t)a * 64 + lane];  // (read after the pellet walk: its waits cover it)
+  const bool alive = d.p_alive[gpl];
   Food F(d, a);
   const uint32_t base = d.ctl[a].food_round;
-  const int n0 = uni(d.p_ncells[gp]);  // (wave-uniform values kept in SGPRs: 4 waves per SIMD fit in 128 VGPRs)
-  const int n = alive ? n0 : 0;
-  if (SHARE && lane == 0) {
-    q_a[w] = a;
-    __hip_atomic_store(&q_n[w], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  const int v_n = d.p_ncells[gpl];
+  if (head) {
+    // the first cell's record, loaded here only to have its lines in the CU's
+    // cache when prep_cell asks for them: the scan's load, barrier and stores
+    // overlap the player round and this one
+    double t0 = 0, t1 = 0, t2 = 0, t3 = 0;
+    long long t4 = 0;
+    cgrid_scan_block(d, blockIdx.x, [&] {
+      if (gp < NP && alive && v_n > 0) {
+        const size_t ci = (size_t)v_first * NP + gp;
+        t0 = d.c_x[ci];
+        t1 = d.c_y[ci];
+        t2 = d.c_m[ci];
+        t3 = d.c_r[ci];
+        t4 = d.c_seq[ci];
+      }
+    });
+    asm volatile("" ::"v"(t0), "v"(t1), "v"(t2), "v"(t3), "v"(t4));
+    if (gp >= NP) return;
   }
+  const int s_first = uni(v_first);
+  const int n0 = uni(v_n);  // (wave-uniform values kept in SGPRs: 4 waves per SIMD fit in 128 VGPRs)
+  const int n = alive ? n0 : 0;
   PT_MARK(0, 1);
   // cell k of player gpc (arena a), pool index ci
   auto prep_cell = [&](const int gpc, const int k, const size_t ci) {
@@ -2649,39 +2675,168 @@ __global__ void __launch_bounds__(256, 4) k_food_prep(Dev d, int rounds, int res
     wave_sync_lds();
     PT_MARK(0, 6);
   };
-  // its own first cell (the slot arrived with the count) unclaimed, then claims of
-  // the block's further cells, its own player's first; one call site (two
-  // inlined copies of the cell spilled VGPRs)
-  if constexpr (!SHARE) {  // the player's cells one after the other
-    for (int k = 0; k < n; k++) prep_cell(gp, k, (size_t)(k == 0 ? s_first : uni((int)d.p_list[k * NP + gp])) * NP + gp);
-    return;
-  }
-  const int g0 = xcd_block(blockIdx.x, gridDim.x) * 4;
-  int gpc = gp, kc = n > 0 ? 0 : -1, sc = s_first;
-  int step = 0;
-  for (; step <= 4 * kMaxCells; step++) {
-    if (kc < 0) {  // the next claim: a player of the block (same arena) with a cell left
-      for (int t = 0; t < 4 && kc < 0; t++) {
-        const int w2 = (w + t) & 3;
-        const int n2 = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&q_n[w2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-        if (n2 <= 1 || __builtin_amdgcn_readfirstlane(q_a[w2]) != a) continue;
-        const int leader = __ffsll((long long)__ballot(1)) - 1;  // (the claim by the first active lane)
-        int k = 0;
-        if (lane == leader) k = atomicAdd(&q_next[w2], 1);
-        k = __builtin_amdgcn_readlane(k, leader);
-        if (k >= n2) continue;
-        gpc = __builtin_amdgcn_readfirstlane(g0 + w2);
-        kc = k;
-        sc = __builtin_amdgcn_readfirstlane((int)d.p_list[k * NP + gpc]);
+  // A player with several cells (first pass, untiled): ONE walk for all of them,
+  // so its dependent load rounds do not grow with its cell count (the scheme of
+  // obs.hip's wave_fov_walk_k).  Cell g lives on lanes 4g .. 4g + 3.  The cells'
+  // pellet-row spans are laid end to end (one lane per row, the staged range one
+  // more row per cell), the rows' items are flattened by a second prefix, and every
+  // batch of 64 candidates is tested against its own cell's box.  Compaction keeps
+  // the flattened order, so a cell's kept candidates are one segment [ps, ps + pc)
+  // of the wave's list; selection, rank and reservation then run per candidate
+  // against its cell.  Returns false -- before any global store or atomic -- when
+  // the player does not fit (more than 64 rows, more than PREP_CAND candidates in
+  // all, a cell with more than FCAP foods in reach) or a cell has a blob near:
+  // the per-cell loop below is exact for all of those.
+  auto prep_multi = [&]() -> bool {
+    const int n = uni(n0);  // (the player is alive)
+    const int g = lane >> 2, sub = lane & 3;
+    const bool has = g < n;
+    const int slot = __shfl(v_slot, g);
+    const size_t ci = (size_t)(has ? slot : s_first) * NP + gp;
+    const double x = d.c_x[ci], y = d.c_y[ci], m = d.c_m[ci], r = d.c_r[ci];
+    PT_MARK(0, 2);
+    const Rect q = footprint(x, y, r, d.size);
+    const Span sp = grid_span(q, 1, d.cols, 0);
+    const int ngrid = sp.by1 - sp.by0 + 1;
+    const bool qok = has && q.x0 <= q.x1 && q.y0 <= q.y1;
+    auto prefix = [&](int v, int &total) {  // exclusive, over the wave
+      int inc = v;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const int t = __shfl_up(inc, off);
+        if (lane >= off) inc += t;
       }
-      if (kc < 0) break;
+      total = uni(__shfl(inc, 63));
+      return inc - v;
+    };
+    int R;
+    const int rbase = prefix(qok && sub == 0 ? ngrid + (F.nst > 0 ? 1 : 0) : 0, R);
+    if (R > 64) return false;
+    // row `lane`: its cell, its two start entries (or the staged range)
+    int c = 0;
+    for (int k = 1; k < n; k++) c = (__builtin_amdgcn_readlane(rbase, 4 * k) <= lane) ? k : c;
+    const int rr = lane - __shfl(rbase, 4 * c), c_by0 = __shfl(sp.by0, 4 * c), c_bx0 = __shfl(sp.bx0, 4 * c),
+              c_bx1 = __shfl(sp.bx1, 4 * c), c_ng = __shfl(ngrid, 4 * c);
+    int lo = 0, len = 0;
+    if (lane < R) {
+      if (rr < c_ng) {
+        const int *st = d.pstart + (size_t)a * d.PH1;
+        const int b = (c_by0 + rr) * (d.cols + 1);
+        lo = st[b + c_bx0];
+        len = st[b + c_bx1 + 1] - lo;
+      } else {
+        lo = F.n0;
+        len = F.nst;
+      }
     }
-    prep_cell(gpc, kc, (size_t)sc * NP + gpc);
-    kc = -1;
+    int T;
+    const int excl = prefix(len, T);
+    int cnt = 0, pc = 0;
+    for (int t0 = 0; t0 < T; t0 += 64) {
+      const int t = t0 + lane;
+      int row = 0;
+      for (int k = 1; k < R; k++) row = (__builtin_amdgcn_readlane(excl, k) <= t) ? k : row;
+      const int j = __shfl(lo, row) + (t - __shfl(excl, row)), cc = __shfl(c, row);
+      const Rect qc{__shfl(q.x0, 4 * cc), __shfl(q.x1, 4 * cc), __shfl(q.y0, 4 * cc), __shfl(q.y1, 4 * cc)};
+      bool keep = false;
+      double fx = 0, fy = 0, fm = 0;
+      int64_t fsq = 0;
+      if (t < T) {
+        F.load(j, fx, fy, fm, fsq);  // (a first pass: every pellet is alive, as in prep_cell)
+        keep = rect_hit(footprint(fx, fy, pellet_radius(fm), d.size), qc);
+      }
+      const unsigned long long bal = __ballot(keep);
+      const int at = cnt + __popcll(bal & ((1ull << lane) - 1));
+      if (keep && at < PREP_CAND) {
+        s_seq[w][at] = Food::order_key(j, fsq);
+        s_x[w][at] = fx;
+        s_y[w][at] = fy;
+        s_m[w][at] = fm;
+        s_idx[w][at] = j;
+        s_sel[w][at] = (uint8_t)cc;
+      }
+      cnt += __popcll(bal);
+      for (int k = 0; k < n; k++) {
+        const int ck = __popcll(__ballot(keep && cc == k));
+        pc += g == k ? ck : 0;
+      }
+    }
+    PT_MARK(0, 3);
+    if (cnt > PREP_CAND) return false;
+    int all;
+    const int ps = __shfl(prefix(sub == 0 ? pc : 0, all), lane & ~3);
+    wave_sync_lds();
+    // the cell's bound sums: four lanes a cell, then across them.  The sum feeds only
+    // the bounds M, Rm and Rp, which carry 1e-9 of slack, so its order is free.
+    double ls = 0;
+    for (int i = sub; i < pc; i += 4) ls += s_m[w][ps + i];
+    ls += __shfl_xor(ls, 1);
+    ls += __shfl_xor(ls, 2);
+    const double M = py_min(kMaxMass, (m + ls) * (1 + 1e-9));
+    const double Rm = fmax(r, radius_of(M)) * (1 + 1e-9);
+    // no blob turn here: a cell with a blob near its box sends the player to the loop
+    // (Rm is no smaller than prep_cell's Rp, so no blob that loop would walk is missed)
+    bool near = false;
+    const Rect qb = footprint(x, y, Rm, d.size);
+    if (has && F.any_blobs() && qb.x0 <= qb.x1 && qb.y0 <= qb.y1) {  // Food::blobs_near, four lanes a cell
+      const Span gb = grid_span(qb, 1, d.cols, d.cshift);
+      const int bw = gb.bx1 - gb.bx0 + 1, nb = bw * (gb.by1 - gb.by0 + 1);
+      for (int i = sub; i < nb; i += 4) {
+        const int b = (gb.by0 + i / bw) * gb.stride + gb.bx0 + i % bw;
+        near |= (s_bm[w][b >> 6] >> (b & 63)) & 1;
+      }
+    }
+    if (__ballot(near)) return false;
+    PT_MARK(0, 4);
+    int nsel = 0;
+    for (int i0 = 0; i0 < cnt; i0 += 64) {
+      const int i = i0 + lane;
+      const int cc = i < cnt ? s_sel[w][i] : 0;
+      const double cx = __shfl(x, 4 * cc), cy = __shfl(y, 4 * cc), cM = __shfl(M, 4 * cc), cR = __shfl(Rm, 4 * cc);
+      bool sel = false;
+      if (i < cnt) {
+        const double fx = s_x[w][i], fy = s_y[w][i];
+        sel = (cM > 1.25 * s_m[w][i]) && ((cx - fx) * (cx - fx) + (cy - fy) * (cy - fy) < cR * cR);
+      }
+      for (int k = 0; k < n; k++) {
+        const int ck = __popcll(__ballot(sel && cc == k));
+        nsel += g == k ? ck : 0;
+      }
+      if (sel) s_sel[w][i] = (uint8_t)(cc | 0x80);  // (its own entry: read above by this lane alone)
+    }
+    if (__ballot(has && nsel > FCAP)) return false;
+    wave_sync_lds();
+    PT_MARK(0, 5);
+    // the player fits: lists, reservations and counts, as prep_cell writes them
+    const int p = gp - a * d.B;
+    for (int i0 = 0; i0 < cnt; i0 += 64) {
+      const int i = i0 + lane;
+      const int tag = i < cnt ? s_sel[w][i] : 0, cc = tag & 0x7F;
+      const int cps = __shfl(ps, 4 * cc), cpc = __shfl(pc, 4 * cc);
+      if (tag & 0x80) {
+        const int64_t sq = s_seq[w][i];
+        int rk = 0;
+        for (int jj = cps; jj < cps + cpc; jj++) rk += ((s_sel[w][jj] & 0x80) && s_seq[w][jj] < sq);
+        const int j = s_idx[w][i];
+        d.f_list[((size_t)cc * NP + gp) * FCAP + rk] = j;
+        atomicMax((unsigned long long *)F.owner(j),
+                  (unsigned long long)food_key(base + 1, (uint32_t)p * kMaxCells + cc));
+      }
+    }
+    if (has && sub == 0) {
+      d.f_cnt[(size_t)g * NP + gp] = (uint8_t)nsel;
+      d.f_done[ci] = (nsel == 0);
+    }
+    PT_MARK(0, 6);
+    return true;
+  };
+  if (n >= 2 && !resume && !d.tiled) {
+    if (prep_multi()) return;
+    wave_sync_lds();  // (a player that did not fit left candidates in the list)
   }
-  // (a block holds at most 4 x kMaxCells cells: the bound is never reached unless the
-  // claim counters are corrupt -- then cells went unprepared, which must not pass silently)
-  if (step > 4 * kMaxCells && lane == wave_leader()) set_err(d, a, ERR_CLAIM);
+  // the player's cells one after the other (one call site: two inlined copies of
+  // the cell spilled VGPRs)
+  for (int k = 0; k < n; k++) prep_cell(gp, k, (size_t)(k == 0 ? s_first : uni((int)d.p_list[k * NP + gp])) * NP + gp);
 }
 // one eaten food: the event (in its reference phase), kill, growth
 // (eatCell -> adjustCellSize -> grow, field.py:327-344)
@@ -3210,7 +3365,6 @@ __device__ __forceinline__ void occ_rebuild_dirty(const Dev &d, int a, const uin
 
 // one wavefront per player: cells with an overlapping enemy cell at phase start
 // (+ the player's cells into the spawn occupancy)
-// (!SHARE: each wave tests its own player's cells in order)
 __device__ __forceinline__ void pp_active_own(const Dev &d PT_PARAMS) {
   const int lane = threadIdx.x & 63;
   const int gp = xcd_block(blockIdx.x, gridDim.x) * 4 + (threadIdx.x >> 6);
@@ -3218,6 +3372,7 @@ __device__ __forceinline__ void pp_active_own(const Dev &d PT_PARAMS) {
   if (d.tiled && gp == 0 && lane == 0 && d.ctl[0].n_undone_glob != 0) atomicOr(&d.ctl[0].err, ERR_TILE_PASSES);
   if (gp >= d.NP) return;
   const int s_first = d.p_list[gp];  // (list row 0 rides the liveness / count load round)
+  const int v_slot = d.p_list[(lane < kMaxCells ? lane : 0) * d.NP + gp];  // (and row k on lane k: pp_multi)
   if (!d.p_alive[gp]) return;
   const int NP = d.NP, a = gp / d.B;
   const int *st = d.cstart + (size_t)a * (d.H + 1);
@@ -3226,6 +3381,73 @@ __device__ __forceinline__ void pp_active_own(const Dev &d PT_PARAMS) {
   int n = d.p_ncells[gp];
   bool anyp = false;
   PT_MARK(3, 1);
+  // A player with several cells: one walk over the cell-grid rows of all of them
+  // (as k_food_prep's prep_multi: lane k holds cell k, the cells' row spans laid
+  // end to end, one lane per row), so the item indirection and the candidates'
+  // records are one load round each for the whole player.  Every candidate is
+  // tested against its own cell.  Returns false, having written nothing, when the
+  // rows do not fit the wave (nothing else has to fit: candidates are only tested).
+  auto pp_multi = [&]() -> bool {
+    const int nu = uni(n);
+    const bool has = lane < nu;
+    const size_t ci = (size_t)(has ? v_slot : s_first) * NP + gp;
+    const double x = d.c_x[ci], y = d.c_y[ci], m = d.c_m[ci], r = d.c_r[ci];
+    PT_MARK(3, 2);
+    const Rect q = footprint(x, y, r, d.size);
+    const Span sp = grid_span(q, E, d.cols, d.cshift_c);
+    const int nrow = has && q.x0 <= q.x1 && q.y0 <= q.y1 ? sp.by1 - sp.by0 + 1 : 0;
+    auto prefix = [&](int v, int &total) {  // exclusive, over the wave
+      int inc = v;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const int t = __shfl_up(inc, off);
+        if (lane >= off) inc += t;
+      }
+      total = uni(__shfl(inc, 63));
+      return inc - v;
+    };
+    int R;
+    const int rbase = prefix(nrow, R);
+    if (R > 64) return false;
+    int c = 0;
+    for (int k = 1; k < nu; k++) c = (__builtin_amdgcn_readlane(rbase, k) <= lane) ? k : c;
+    const int rr = lane - __shfl(rbase, c), c_by0 = __shfl(sp.by0, c), c_bx0 = __shfl(sp.bx0, c),
+              c_bx1 = __shfl(sp.bx1, c);
+    int lo = 0, len = 0;
+    if (lane < R) {
+      const int b = (c_by0 + rr) * sp.stride;
+      lo = st[b + c_bx0];
+      len = st[b + c_bx1 + 1] - lo;
+    }
+    int T;
+    const int excl = prefix(len, T);
+    unsigned act = 0;  // bit k: cell k has a partner (wave-uniform)
+    for (int t0 = 0; t0 < T && act != (1u << nu) - 1; t0 += 64) {
+      const int t = t0 + lane;
+      int row = 0;
+      for (int k = 1; k < R; k++) row = (__builtin_amdgcn_readlane(excl, k) <= t) ? k : row;
+      const int idx = __shfl(lo, row) + (t - __shfl(excl, row)), cc = __shfl(c, row);
+      const double cx = __shfl(x, cc), cy = __shfl(y, cc), cm = __shfl(m, cc), cr = __shfl(r, cc);
+      const Rect qc{__shfl(q.x0, cc), __shfl(q.x1, cc), __shfl(q.y0, cc), __shfl(q.y1, cc)};
+      bool hit = false;
+      if (t < T) {  // pp_active_own's predicate, against the candidate lane's own cell
+        const int e = it[idx];
+        if ((d.c_flags[e] & F_ALIVE) && (int)(e % NP) > gp && rect_hit(cell_rect(d, e), qc)) {
+          const double me = d.c_m[e];
+          hit = overlap(cx, cy, cm, cr, d.c_x[e], d.c_y[e], me, d.c_r[e]) && (can_eat(cm, me) || can_eat(me, cm));
+        }
+      }
+      for (int k = 0; k < nu; k++) act |= __ballot(hit && cc == k) ? 1u << k : 0u;
+    }
+    for (int k = 0; k < nu; k++)  // the cells into the spawn occupancy
+      occ_add(d, a, Rect{__builtin_amdgcn_readlane(q.x0, k), __builtin_amdgcn_readlane(q.x1, k),
+                         __builtin_amdgcn_readlane(q.y0, k), __builtin_amdgcn_readlane(q.y1, k)});
+    if (has) d.c_active[ci] = (act >> lane) & 1;
+    anyp = act != 0;
+    PT_MARK(3, 3);
+    return true;
+  };
+  if (n >= 2 && pp_multi()) n = 0;  // (done: the loop below is for single cells and players that do not fit)
   for (int k = 0; k < n; k++) {
     size_t ci = (size_t)(k == 0 ? s_first : d.p_list[k * NP + gp]) * NP + gp;
     double x = d.c_x[ci], y = d.c_y[ci], m = d.c_m[ci], r = d.c_r[ci];
@@ -3254,102 +3476,10 @@ __device__ __forceinline__ void pp_active_own(const Dev &d PT_PARAMS) {
     else set_err(d, a, ERR_WORK_CAP);
   }
 }
-// SHARE (Greedy populations): a block's four players share their cells as in
-// k_food_prep -- a wave tests its own player's first cell, then claims the
-// remaining cells of the block's players of its arena (q_next).  A one-cell
-// player is queued by its own wave; for a player with more cells every tested
-// cell marks q_any and counts in q_done, and the wave that tests the last one
-// queues the player if marked.
-template <bool SHARE>
 __global__ void __launch_bounds__(256) k_pp_active(Dev d) {
   FLOOR(6);
   PT_BEGIN(3);
-  if constexpr (!SHARE) {
-    pp_active_own(d PT_ARGS);
-    return;
-  }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int g0 = xcd_block(blockIdx.x, gridDim.x) * 4, gp = g0 + w;
-  __shared__ int q_n[4], q_next[4], q_done[4], q_any[4], q_a[4];
-  if (lane == 0) {
-    q_n[w] = 0;
-    q_next[w] = 1;  // (cell 0: its owner, unclaimed)
-    q_done[w] = 0;
-    q_any[w] = 0;
-  }
-  __syncthreads();
-  // C4, device-bounded eat passes: the tick may go on only if no owned cell is undone
-  if (d.tiled && gp == 0 && lane == 0 && d.ctl[0].n_undone_glob != 0) atomicOr(&d.ctl[0].err, ERR_TILE_PASSES);
-  if (gp >= d.NP) return;
-  const int s_first = d.p_list[gp];  // (list row 0 rides the liveness / count load round)
-  const bool alive = d.p_alive[gp];
-  const int NP = d.NP, a = gp / d.B;
-  const int *st = d.cstart + (size_t)a * (d.H + 1);
-  const int *it = d.citems + (size_t)a * kMaxCells * d.B;
-  const int E = expand_for(d.ctl[a].rmax_cell);
-  const int n = alive ? d.p_ncells[gp] : 0;
-  if (lane == 0) {
-    q_a[w] = a;
-    __hip_atomic_store(&q_n[w], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  }
-  PT_MARK(3, 1);
-  int wc = w, kc = n > 0 ? 0 : -1, nc = n, sc = s_first;
-  int step = 0;
-  for (; step <= 4 * kMaxCells; step++) {
-    if (kc < 0) {  // the next claim: a player of the block (same arena) with a cell left
-      for (int t = 0; t < 4 && kc < 0; t++) {
-        const int w2 = (w + t) & 3;
-        const int n2 = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&q_n[w2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-        if (n2 <= 1 || __builtin_amdgcn_readfirstlane(q_a[w2]) != a) continue;
-        const int leader = __ffsll((long long)__ballot(1)) - 1;  // (the claim by the first active lane)
-        int k = 0;
-        if (lane == leader) k = atomicAdd(&q_next[w2], 1);
-        k = __builtin_amdgcn_readlane(k, leader);
-        if (k >= n2) continue;
-        wc = w2;
-        kc = k;
-        nc = n2;
-        sc = __builtin_amdgcn_readfirstlane((int)d.p_list[k * NP + g0 + w2]);
-      }
-      if (kc < 0) break;
-    }
-    const int gpc = __builtin_amdgcn_readfirstlane(g0 + wc);
-    const size_t ci = (size_t)sc * NP + gpc;
-    double x = d.c_x[ci], y = d.c_y[ci], m = d.c_m[ci], r = d.c_r[ci];
-    PT_MARK(3, 2);
-    Rect q = footprint(x, y, r, d.size);
-    occ_add(d, a, q);
-    bool any = wave_any_in_grid(st, it, d.cols, q, E, [&](int e) {
-      // only the LOWER-index player of a pair is marked: its turn comes first
-      // and resolves the pair ("the one that can eat does", field.py:238-243).
-      // The higher-index side's turn could only see a changed pair, and every
-      // change re-activates it: a growth re-activates the cells overlapping the
-      // grown one; a cell skipped by the live-list quirk re-activates its partners.
-      if (!(d.c_flags[e] & F_ALIVE) || (int)(e % NP) <= gpc) return false;
-      if (!rect_hit(cell_rect(d, e), q)) return false;
-      // a pair where neither side can eat stays inert until one of them grows
-      double me = d.c_m[e];
-      return overlap(x, y, m, r, d.c_x[e], d.c_y[e], me, d.c_r[e]) && (can_eat(m, me) || can_eat(me, m));
-    }, d.cshift_c);
-    const int leader = __ffsll((long long)__ballot(1)) - 1;
-    if (lane == leader) {
-      d.c_active[ci] = any;
-      bool push = any;
-      if (nc > 1) {
-        if (any) atomicOr(&q_any[wc], 1);
-        push = atomicAdd(&q_done[wc], 1) == nc - 1 &&  // (after the mark: LDS atomics of a CU apply in order)
-               __hip_atomic_load(&q_any[wc], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0;
-      }
-      if (push) {
-        const int wq = atomicAdd(&d.ctl[a].n_pend, 1);
-        if (wq < d.Wcap) d.work[(size_t)a * d.Wcap + wq] = gpc - a * d.B;
-        else set_err(d, a, ERR_WORK_CAP);
-      }
-    }
-    PT_MARK(3, 3);
-    kc = -1;
-  }
-  if (step > 4 * kMaxCells && lane == wave_leader()) set_err(d, a, ERR_CLAIM);  // (as in k_food_prep)
+  pp_active_own(d PT_ARGS);
 }
 
 // removes cell e (pool index) from its player's list; returns true if the player died
@@ -5133,12 +5263,8 @@ void launch_pellet_rows(const Dev &d, hipStream_t s) {
 static void launch_food(const Dev &d, hipStream_t s, int rounds, Scratch scr, int resume = 0, int fold = 0) {
   rounds = std::max(rounds, 1);
   const int g = nblk(d.NP, 256);
-  if (d.share_cells)
-    hipLaunchKernelGGL(k_food_prep<true>, dim3(std::max(nblk((long)d.NP * PREP_WAVES, 4), resume ? 0 : d.A)), dim3(256),
-                       0, s, d, rounds, resume);
-  else
-    hipLaunchKernelGGL(k_food_prep<false>, dim3(std::max(nblk((long)d.NP * PREP_WAVES, 4), resume ? 0 : d.A)), dim3(256),
-                       0, s, d, rounds, resume);
+  hipLaunchKernelGGL(k_food_prep, dim3(std::max(nblk((long)d.NP * PREP_WAVES, 4), resume ? 0 : d.A)), dim3(256), 0, s, d,
+                     rounds, resume);
   for (int r = 1; r <= rounds; r++) {
     hipLaunchKernelGGL(k_food_commit, dim3(g), dim3(256), 0, s, d, r, r == rounds ? 1 : 0, scr.k, scr.v, rounds,
                        fold && r == rounds ? 1 : 0, r == 1 && !resume ? 1 : 0);
@@ -5165,8 +5291,7 @@ void launch_tick_pre(const Dev &d, hipStream_t s, int64_t *scr_k, int *scr_v, co
 }
 // the phases after it: playerPlayerOverlap, spawnStuff, closing rebuild (field.py:233-313)
 void launch_tick_post(const Dev &d, hipStream_t s, int64_t *scr_k, int *scr_v) {
-  if (d.share_cells) hipLaunchKernelGGL(k_pp_active<true>, dim3(nblk(d.NP, 4)), dim3(256), 0, s, d);
-  else hipLaunchKernelGGL(k_pp_active<false>, dim3(nblk(d.NP, 4)), dim3(256), 0, s, d);
+  hipLaunchKernelGGL(k_pp_active, dim3(nblk(d.NP, 4)), dim3(256), 0, s, d);
   // playerPlayerOverlap's serial pass + spawnStuff's plan + the end-of-tick virus
   // grid + the closing pellet update's sorted kill / join lists (and the pellet spawns)
   hipLaunchKernelGGL(k_spawn_plan, dim3(d.A), dim3(1024),
