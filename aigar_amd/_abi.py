@@ -43,6 +43,15 @@ class PixelParams(C.Structure):
     _fields_ = [("side", C.c_int32), ("flags", C.c_int32), ("color_seed", C.c_uint64)]
 
 
+EXP_PRIORITIZED = 0x1  # aigar_exp_params.flags
+
+
+class ExpParams(C.Structure):
+    """aigar_exp_params (include/aigar.h): the learners' replay memory (replay_buffer.py)."""
+    _fields_ = [("capacity", C.c_int64), ("state_dtype", C.c_int32), ("flags", C.c_int32), ("alpha", C.c_double),
+                ("beta", C.c_double), ("seed", C.c_uint64)]
+
+
 class RunParams(C.Structure):
     """aigar_run_params (include/aigar.h): the policy replayed inside aigar_run's step graph."""
     _fields_ = [("policy", C.c_int32), ("greedy_split", C.c_int32), ("p_split", C.c_double),

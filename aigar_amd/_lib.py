@@ -88,6 +88,12 @@ def load(build_if_missing=False):
         "aigar_pixel_config": [vp, C.POINTER(_abi.PixelParams)],
         "aigar_pixel_state_len": [vp],
         "aigar_observe_pixel_state": [vp, vp, i32, i32, vp, i32],
+        "aigar_exp_config": [vp, C.POINTER(_abi.ExpParams)],
+        "aigar_exp_info": [vp, C.POINTER(C.c_int64)],
+        "aigar_exp_add": [vp, vp, vp, vp, vp, vp, vp, i32, i32],
+        "aigar_exp_sample": [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+        "aigar_exp_gather": [vp, vp, i32, vp, vp, vp, vp, vp],
+        "aigar_exp_update_priorities": [vp, vp, vp, i32],
         "aigar_set_actions": [vp, vp, vp, i32],
         "aigar_reset_bots": [vp, vp, i32],
         "aigar_player_stats": [vp, vp, i32],
@@ -170,6 +176,7 @@ class Stepper:
         self.NP = self.A * self.B
         self.obs_len = self.L.aigar_obs_len(self.h)
         self.pixel_state_shape = None  # (NP, side, side, C) while a pixel state is configured
+        self.exp = None  # (state row shape, state dtype name, prioritized) while a replay memory is configured
 
     def _chk(self, r):
         if r < 0:
@@ -378,6 +385,111 @@ class Stepper:
         mp, mdev = _ptr(mask)
         self._chk(self.L.aigar_observe_pixel_state(self.h, p, 0 if d == "float64" else 1, dev, mp, mdev))
         return out
+
+    # ---- replay memory (include/aigar.h: aigar_exp_*)
+    def exp_config(self, capacity, prioritized=False, alpha=0.6, beta=0.4, dtype="float64", seed=0):
+        """The handle's replay memory (replay_buffer.py): a ring of capacity transitions whose
+        states have the handle's current state shape (the pixel state when one is configured,
+        else the observation row) in dtype; prioritized: with the sum / min trees.  While it
+        is set every env_step appends the NN players' transitions inside its graph.
+        exp_config(None) frees it."""
+        if not capacity:
+            self._chk(self.L.aigar_exp_config(self.h, None))
+            self.exp = None
+            return
+        d = str(dtype).replace("torch.", "").replace("<class 'numpy.", "").replace("'>", "")
+        if d not in ("float64", "float32"):
+            raise ValueError("exp_config: dtype must be float64 or float32, got %s" % (dtype,))
+        prm = _abi.ExpParams(int(capacity), 0 if d == "float64" else 1, _abi.EXP_PRIORITIZED if prioritized else 0,
+                             float(alpha), float(beta), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        self._chk(self.L.aigar_exp_config(self.h, C.byref(prm)))
+        row = tuple(self.pixel_state_shape[1:]) if self.pixel_state_shape is not None else (self.obs_len,)
+        self.exp = (row, d, bool(prioritized))
+
+    def _need_exp(self, what):
+        if self.exp is None:
+            raise RuntimeError("aigar: %s: no replay memory is configured (exp_config)" % what)
+        return self.exp
+
+    def _check_dev(self, t, shape, dtypes, what):
+        if not getattr(t, "is_cuda", False):
+            raise ValueError("%s takes device tensors" % what)
+        return self._check_out(t, shape, dtypes, what)
+
+    def exp_info(self):
+        """{capacity, size, next_idx, added} of the memory (a host round trip)."""
+        self._need_exp("exp_info")
+        v = (C.c_int64 * 4)()
+        self._chk(self.L.aigar_exp_info(self.h, v))
+        return {"capacity": v[0], "size": v[1], "next_idx": v[2], "added": v[3]}
+
+    def exp_add(self, s, a, r, s2, done, mask=None):
+        """ReplayBuffer.add for the rows with mask != 0 (all if None), in row order: s, s2
+        [n, *state shape] of the memory's dtype, a [n, 4] and r [n] float64, done [n] uint8 /
+        bool; all numpy arrays or all device tensors."""
+        row, d, _ = self._need_exp("exp_add")
+        n = int(s.shape[0])
+        dev = None
+        ptrs = []
+        for x, shape, dts in ((s, (n,) + row, (d,)), (a, (n, 4), ("float64",)), (r, (n,), ("float64",)),
+                              (s2, (n,) + row, (d,)), (done, (n,), ("uint8", "bool")),
+                              (mask, (n,), ("uint8", "bool"))):
+            if x is None:
+                ptrs.append(None)
+                continue
+            self._check_out(x, shape, dts, "exp_add")
+            p, on = _ptr(x)
+            if dev is not None and on != dev:
+                raise ValueError("exp_add: all numpy arrays or all device tensors")
+            dev = on
+            ptrs.append(p)
+        self._chk(self.L.aigar_exp_add(self.h, ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], ptrs[5], n, dev))
+
+    def _exp_rows(self, batch, s, a, r, s2, done, what):
+        row, d, _ = self._need_exp(what)
+        out = []
+        for x, shape, dts in ((s, (batch,) + row, (d,)), (a, (batch, 4), ("float64",)), (r, (batch,), ("float64",)),
+                              (s2, (batch,) + row, (d,)), (done, (batch,), ("uint8", "bool"))):
+            if x is None:
+                out.append(None)
+            else:
+                self._check_dev(x, shape, dts, what)
+                out.append(C.c_void_p(x.data_ptr()))
+        return out
+
+    def exp_sample(self, w, idx, u=None, s=None, a=None, r=None, s2=None, done=None):
+        """One mini-batch of len(idx) draws on device tensors (aigar_exp_sample): idx [batch]
+        int64 and w [batch] float64 are written, and row k of the given s, a, r, s2, done
+        gets transition idx[k]; u [batch] float64 in [0, 1) are the draws (None: the
+        memory's own Philox stream).  Stream-ordered, no host round trip."""
+        batch = int(idx.shape[0])
+        rows = self._exp_rows(batch, s, a, r, s2, done, "exp_sample")
+        self._check_dev(w, (batch,), ("float64",), "exp_sample")
+        self._check_dev(idx, (batch,), ("int64",), "exp_sample")
+        up = None
+        if u is not None:
+            self._check_dev(u, (batch,), ("float64",), "exp_sample")
+            up = C.c_void_p(u.data_ptr())
+        self._chk(self.L.aigar_exp_sample(self.h, batch, up, rows[0], rows[1], rows[2], rows[3], rows[4],
+                                          C.c_void_p(w.data_ptr()), C.c_void_p(idx.data_ptr())))
+
+    def exp_gather(self, idx, s=None, a=None, r=None, s2=None, done=None):
+        """Row k of the given device tensors gets transition idx[k] (idx: int64 device tensor);
+        rows whose index is outside [0, size) are left as they are."""
+        batch = int(idx.shape[0])
+        rows = self._exp_rows(batch, s, a, r, s2, done, "exp_gather")
+        self._check_dev(idx, (batch,), ("int64",), "exp_gather")
+        self._chk(self.L.aigar_exp_gather(self.h, C.c_void_p(idx.data_ptr()), batch, *rows))
+
+    def exp_update_priorities(self, idx, prio):
+        """PrioritizedReplayBuffer.update_priorities on device tensors idx [n] int64, prio [n]
+        float64 (the last of a repeated index wins; prio <= 0 and indices outside [0, size)
+        are skipped); nothing in uniform mode."""
+        self._need_exp("exp_update_priorities")
+        n = int(idx.shape[0])
+        self._check_dev(idx, (n,), ("int64",), "exp_update_priorities")
+        self._check_dev(prio, (n,), ("float64",), "exp_update_priorities")
+        self._chk(self.L.aigar_exp_update_priorities(self.h, C.c_void_p(idx.data_ptr()), C.c_void_p(prio.data_ptr()), n))
 
     def set_actions(self, cur=None, prev=None):
         c = None if cur is None else np.ascontiguousarray(cur, np.float64)

@@ -51,6 +51,8 @@ void launch_set_commands(const Dev &d, hipStream_t s, const double *cmd);
 
 using namespace aigar;
 
+#include "replay.inc"
+
 static thread_local std::string g_err;
 static int fail(const char *fmt, ...) {
   char buf[1024];
@@ -203,7 +205,13 @@ struct aigar_handle {
     int n_greedy, n_random;
     aigar_pixel_params pix;  // side 0: the grid row
     uint32_t *pix_hist;
+    const void *exp;  // the replay memory the decision appends to (null: none)
   } env_key{};
+  // aigar_exp_config: the learners' replay memory (replay.inc; cap 0: off)
+  Exp exp;
+  std::vector<void *> exp_allocs;
+  int *d_exp_off = nullptr;  // aigar_exp_add's slot offsets, [exp_off_n]
+  size_t exp_off_n = 0;
 };
 
 extern "C" const char *aigar_last_error(void) { return g_err.c_str(); }
@@ -262,6 +270,11 @@ static void free_all(aigar_handle *h) {
   h->pix_bytes = 0;
   if (h->d_pix_hist) (void)hipFree(h->d_pix_hist);
   h->d_pix_hist = nullptr;
+  for (void *p : h->exp_allocs) (void)hipFree(p);
+  h->exp_allocs.clear();
+  if (h->d_exp_off) (void)hipFree(h->d_exp_off);
+  h->d_exp_off = nullptr;
+  h->exp = Exp{};
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->ev_x) (void)hipEventDestroy(h->ev_x);
@@ -627,6 +640,7 @@ extern "C" int aigar_reset(aigar_handle *h, uint64_t seed) {
   for (double *p : {d.o_self_lf, d.o_self_slf, d.o_en_lf, d.o_en_slf})
     HIPCHK(hipMemsetAsync(p, 0, sizeof(double) * NP * GG, h->stream));
   if (h->d_pix_hist) HIPCHK(hipMemsetAsync(h->d_pix_hist, 0, pix_hist_bytes(h), h->stream));
+  if (h->exp.cap) HIPCHK(hipMemsetAsync(h->exp.has_old, 0, NP, h->stream));  // Bot.reset: oldState = None
   if (d.tiled) {  // every tile's history copy is current (all zero)
     HIPCHK(hipMemsetAsync(d.t_holder, 0xFF, sizeof(int) * NP, h->stream));
     HIPCHK(hipMemsetAsync(d.t_obsby, 0xFF, sizeof(int) * NP, h->stream));
@@ -671,6 +685,8 @@ extern "C" int aigar_reset_arenas(aigar_handle *h, const int32_t *arenas, const 
       const unsigned nb = (unsigned)std::min<size_t>((row + 255) / 256, 256);
       hipLaunchKernelGGL(k_pix_hist_clear_arenas, dim3(nb, n), dim3(256), 0, h->stream, h->d_pix_hist, row, h->d_rlist);
     }
+    if (h->exp.cap)
+      hipLaunchKernelGGL(k_exp_clear_arenas, dim3(n), dim3(256), 0, h->stream, h->exp.has_old, d.B, h->d_rlist);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -1227,6 +1243,26 @@ extern "C" int aigar_tile_observers(aigar_handle *h, int32_t *out) {
 // the Greedy and Random bots' moves (Model.takeBotActions, model.py:113-115; the
 // moves are independent of each other), then Field.update; the observation is
 // computed for the NN bots only.
+// The decision's append (replay.inc): the NN players that had an old state emit
+// (old state, action, window reward, new row, dead) into the ring in ascending player
+// order, then the new rows are latched -- two launches at the end of the graph.
+static void launch_exp_append(aigar_handle *h, hipStream_t s, const double *act, int n_act, const double *reward,
+                              const void *obs) {
+  const Exp &e = h->exp;
+  const int NP = h->d.NP;
+  hipLaunchKernelGGL(k_exp_plan, dim3(1), dim3(kExpPlanThreads), 0, s, e, 0, h->d.p_role, (const uint8_t *)nullptr, NP,
+                     e.off);
+  if (e.dtype == 0)
+    hipLaunchKernelGGL(k_exp_rows<uint64_t>, dim3(NP), dim3(256), 0, s, e, e.off, e.old, e.stride, (const char *)obs, act,
+                       n_act, reward, (const uint8_t *)nullptr, h->d.p_role, 1);
+  else
+    hipLaunchKernelGGL(k_exp_rows<uint32_t>, dim3(NP), dim3(256), 0, s, e, e.off, e.old, e.stride, (const char *)obs, act,
+                       n_act, reward, (const uint8_t *)nullptr, h->d.p_role, 1);
+}
+static void launch_exp_latch(aigar_handle *h, hipStream_t s, const void *obs, int dtype, const uint8_t *mask) {
+  hipLaunchKernelGGL(k_exp_latch, dim3(h->d.NP), dim3(256), 0, s, h->exp, obs, dtype, mask);
+}
+
 static void launch_env_decision(aigar_handle *h, hipStream_t s, const aigar_handle::EnvKey &k) {
   for (int t = 0; t <= k.skip; t++) {
     if (t > 0) launch_rewards(h->d, s, k.reward, k.prm, 0, t == 1 ? 1 : 2);  // updateRewards (bot.py:166-168)
@@ -1242,6 +1278,7 @@ static void launch_env_decision(aigar_handle *h, hipStream_t s, const aigar_hand
     (void)launch_observe_pixel_state(h->d, s, k.obs, k.dtype, k.pix.side, k.pix.flags, k.pix.color_seed, h->d_pix_ovf,
                                      nn, k.pix_hist);
   else launch_observe(h->d, s, k.obs, k.dtype, 0, nn);
+  if (k.exp) launch_exp_append(h, s, k.act, k.n_act, k.reward, k.obs);
 }
 
 extern "C" int aigar_env_step(aigar_handle *h, const double *act, int n_act, int enable_split, int skip,
@@ -1265,6 +1302,10 @@ extern "C" int aigar_env_step(aigar_handle *h, const double *act, int n_act, int
   k.n_random = h->n_random;
   k.pix = h->pix;
   k.pix_hist = h->d_pix_hist;
+  k.exp = h->exp.cap ? h->exp.ctl : nullptr;
+  if (h->exp.cap && dtype != h->exp.dtype)
+    return fail("env_step: dtype %d differs from the replay memory's state_dtype %d (aigar_exp_config)", dtype,
+                h->exp.dtype);
   if (k.pix.side && ((uintptr_t)obs_out & 15)) return fail("env_step: the pixel state's obs_out must be 16-byte aligned");
   if (h->d.flags & AIGAR_FLAG_EVENTS)  // the event log holds the window's ticks
     hipLaunchKernelGGL(k_step_begin, dim3((h->d.A + 63) / 64), dim3(64), 0, h->stream, h->d);
@@ -1346,6 +1387,8 @@ extern "C" int aigar_observe_masked(aigar_handle *h, void *out, int dtype, int o
   {
     Mark mk(h, "observe");
     launch_observe(h->d, h->stream, dst, dtype, ++h->obs_calls, m);
+    // (with a pixel config the memory's states are pixel states: a grid row is none of them)
+    if (h->exp.cap && !h->pix.side) launch_exp_latch(h, h->stream, dst, dtype, m);
   }
   HIPCHK(hipGetLastError());
   if (!on_device) {
@@ -1398,6 +1441,9 @@ static int pix_channels(const aigar_pixel_params &p) {
 
 extern "C" int aigar_pixel_config(aigar_handle *h, const aigar_pixel_params *p) {
   if (!h) return fail("null handle");
+  if (h->exp.cap)
+    return fail("pixel_config: a replay memory is set, its rows have the current state's width "
+                "(free it first: aigar_exp_config(h, NULL))");
   aigar_pixel_params q{};
   if (p && p->side != 0) q = *p;
   if (q.side) {
@@ -1425,6 +1471,230 @@ extern "C" int aigar_pixel_config(aigar_handle *h, const aigar_pixel_params *p) 
     }
   }
   if (want) HIPCHK(hipMemsetAsync(h->d_pix_hist, 0, want, h->stream));
+  return 0;
+}
+
+
+// ------------------------------------------------------------ replay memory
+static void exp_free(aigar_handle *h) {
+  for (void *p : h->exp_allocs) (void)hipFree(p);
+  h->exp_allocs.clear();
+  h->exp = Exp{};
+}
+static int exp_state_len(aigar_handle *h) {
+  return h->pix.side ? h->pix.side * h->pix.side * pix_channels(h->pix) : h->d.L;
+}
+static int need_exp(aigar_handle *h, const char *who) {
+  if (!h) return fail("null handle");
+  if (!h->exp.cap) return fail("%s: no replay memory is configured (aigar_exp_config)", who);
+  return 0;
+}
+
+extern "C" int aigar_exp_config(aigar_handle *h, const aigar_exp_params *p) {
+  if (!h) return fail("null handle");
+  const bool on = p && p->capacity != 0;
+  if (on) {
+    if (h->d.tiled) return fail("exp_config: a tiled handle has no replay memory");
+    if (p->capacity < h->d.NP)
+      return fail("exp_config: capacity %lld is below the handle's %d players (one decision's transitions)",
+                  (long long)p->capacity, h->d.NP);
+    if (p->capacity > ((int64_t)1 << 30)) return fail("exp_config: capacity %lld above 2^30", (long long)p->capacity);
+    if (p->state_dtype != 0 && p->state_dtype != 1) return fail("exp_config: state_dtype must be 0 (float64) or 1 (float32)");
+    if (p->flags & ~AIGAR_EXP_PRIORITIZED) return fail("exp_config: unknown flags 0x%x", p->flags);
+    if ((p->flags & AIGAR_EXP_PRIORITIZED) && (!(p->alpha >= 0) || !(p->beta > 0)))
+      return fail("exp_config: need alpha >= 0 and beta > 0 (got %g, %g)", p->alpha, p->beta);
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));  // (no replay of the graph, no reader of the memory is pending)
+  if (h->env_graph) (void)hipGraphExecDestroy(h->env_graph);
+  h->env_graph = nullptr;
+  exp_free(h);
+  if (!on) return 0;
+  Exp e;
+  e.cap = p->capacity;
+  e.it_cap = 1;
+  while (e.it_cap < e.cap) e.it_cap *= 2;
+  e.dtype = p->state_dtype;
+  e.esz = e.dtype == 0 ? 8 : 4;
+  e.L = exp_state_len(h);
+  e.stride = ((size_t)e.L * e.esz + 15) & ~(size_t)15;
+  e.prio = (p->flags & AIGAR_EXP_PRIORITIZED) ? 1 : 0;
+  e.alpha = p->alpha;
+  e.beta = p->beta;
+  e.seed = p->seed;
+  const size_t cap = (size_t)e.cap, NP = (size_t)h->d.NP;
+  bool ok = true;
+  size_t total = 0;
+  auto get = [&](size_t bytes) -> void * {
+    void *q = nullptr;
+    if (!ok) return nullptr;
+    total += bytes;
+    if (hipMalloc(&q, bytes ? bytes : 1) != hipSuccess) {
+      (void)hipGetLastError();
+      ok = false;
+      return nullptr;
+    }
+    h->exp_allocs.push_back(q);
+    return q;
+  };
+  e.s = (char *)get(cap * e.stride);
+  e.s2 = (char *)get(cap * e.stride);
+  e.a = (double *)get(cap * 4 * sizeof(double));
+  e.r = (double *)get(cap * sizeof(double));
+  e.done = (uint8_t *)get(cap);
+  if (e.prio) {
+    e.vsum = (double *)get(2 * (size_t)e.it_cap * sizeof(double));
+    e.vmin = (double *)get(2 * (size_t)e.it_cap * sizeof(double));
+    e.last = (int *)get(cap * sizeof(int));
+  }
+  e.ctl = (ExpCtl *)get(sizeof(ExpCtl));
+  e.old = (char *)get(NP * e.stride);
+  e.has_old = (uint8_t *)get(NP);
+  e.off = (int *)get(NP * sizeof(int));
+  if (!ok) {
+    exp_free(h);
+    return fail("exp_config: out of device memory (%zu bytes for %lld transitions of %d values)", total,
+                (long long)p->capacity, e.L);
+  }
+  // cleared: rows zero, trees empty, no old states
+  HIPCHK(hipMemsetAsync(e.s, 0, cap * e.stride, h->stream));
+  HIPCHK(hipMemsetAsync(e.s2, 0, cap * e.stride, h->stream));
+  HIPCHK(hipMemsetAsync(e.a, 0, cap * 4 * sizeof(double), h->stream));
+  HIPCHK(hipMemsetAsync(e.r, 0, cap * sizeof(double), h->stream));
+  HIPCHK(hipMemsetAsync(e.done, 0, cap, h->stream));
+  HIPCHK(hipMemsetAsync(e.old, 0, NP * e.stride, h->stream));
+  HIPCHK(hipMemsetAsync(e.has_old, 0, NP, h->stream));
+  if (e.prio)
+    hipLaunchKernelGGL(k_exp_fill_i, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, h->stream, e.last, cap, -1);
+  const size_t ni = e.prio ? 2 * (size_t)e.it_cap : 1;
+  hipLaunchKernelGGL(k_exp_init, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, h->stream, e);
+  HIPCHK(hipGetLastError());
+  h->exp = e;
+  return 0;
+}
+
+extern "C" int aigar_exp_info(aigar_handle *h, int64_t info[4]) {
+  if (need_exp(h, "exp_info")) return -1;
+  if (!info) return fail("null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  ExpCtl c;
+  HIPCHK(hipMemcpyAsync(&c, h->exp.ctl, sizeof c, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  info[0] = h->exp.cap;
+  info[1] = c.size;
+  info[2] = c.next;
+  info[3] = c.added;
+  return 0;
+}
+
+extern "C" int aigar_exp_add(aigar_handle *h, const void *s, const double *a, const double *r, const void *s2,
+                             const uint8_t *done, const uint8_t *mask, int n, int on_device) {
+  if (need_exp(h, "exp_add")) return -1;
+  if (n < 0) return fail("exp_add: n = %d is negative", n);
+  if (n == 0) return 0;
+  if (!s || !a || !r || !s2 || !done) return fail("exp_add: null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const Exp &e = h->exp;
+  const size_t row = (size_t)e.L * e.esz, N = (size_t)n;
+  if ((size_t)n > h->exp_off_n) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->d_exp_off) (void)hipFree(h->d_exp_off);
+    h->d_exp_off = nullptr;
+    h->exp_off_n = 0;
+    if (hipMalloc((void **)&h->d_exp_off, N * sizeof(int)) != hipSuccess) {
+      (void)hipGetLastError();
+      h->d_exp_off = nullptr;
+      return fail("exp_add: out of device memory");
+    }
+    h->exp_off_n = N;
+  }
+  char *stage = nullptr;
+  if (!on_device) {  // one staging block: s | s2 | a | r | done | mask (each part 16-byte aligned)
+    auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t o_s2 = up(N * row), o_a = o_s2 + up(N * row), o_r = o_a + up(N * 32), o_d = o_r + up(N * 8),
+                 o_m = o_d + up(N), bytes = o_m + up(N);
+    if (hipMalloc((void **)&stage, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail("exp_add: out of device memory (%zu bytes of staging)", bytes);
+    }
+    hipError_t er = hipMemcpyAsync(stage, s, N * row, hipMemcpyHostToDevice, h->stream);
+    if (er == hipSuccess) er = hipMemcpyAsync(stage + o_s2, s2, N * row, hipMemcpyHostToDevice, h->stream);
+    if (er == hipSuccess) er = hipMemcpyAsync(stage + o_a, a, N * 32, hipMemcpyHostToDevice, h->stream);
+    if (er == hipSuccess) er = hipMemcpyAsync(stage + o_r, r, N * 8, hipMemcpyHostToDevice, h->stream);
+    if (er == hipSuccess) er = hipMemcpyAsync(stage + o_d, done, N, hipMemcpyHostToDevice, h->stream);
+    if (er == hipSuccess && mask) er = hipMemcpyAsync(stage + o_m, mask, N, hipMemcpyHostToDevice, h->stream);
+    if (er != hipSuccess) {
+      (void)hipStreamSynchronize(h->stream);
+      (void)hipFree(stage);
+      return fail("exp_add: copy failed: %s", hipGetErrorString(er));
+    }
+    s = stage;
+    s2 = stage + o_s2;
+    a = (const double *)(stage + o_a);
+    r = (const double *)(stage + o_r);
+    done = (const uint8_t *)(stage + o_d);
+    if (mask) mask = (const uint8_t *)(stage + o_m);
+  }
+  hipLaunchKernelGGL(k_exp_plan, dim3(1), dim3(kExpPlanThreads), 0, h->stream, e, 1, (const uint8_t *)nullptr, mask, n,
+                     h->d_exp_off);
+  if (e.dtype == 0)
+    hipLaunchKernelGGL(k_exp_rows<uint64_t>, dim3(n), dim3(256), 0, h->stream, e, h->d_exp_off, (const char *)s, row,
+                       (const char *)s2, a, 4, r, done, (const uint8_t *)nullptr, 0);
+  else
+    hipLaunchKernelGGL(k_exp_rows<uint32_t>, dim3(n), dim3(256), 0, h->stream, e, h->d_exp_off, (const char *)s, row,
+                       (const char *)s2, a, 4, r, done, (const uint8_t *)nullptr, 0);
+  hipError_t er = hipGetLastError();
+  if (stage) {
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(stage);
+  }
+  if (er != hipSuccess) return fail("exp_add: launch failed: %s", hipGetErrorString(er));
+  return 0;
+}
+
+static void launch_exp_fetch(aigar_handle *h, const int64_t *idx, int batch, void *s, double *a, double *r, void *s2,
+                             uint8_t *done, int count) {
+  const Exp &e = h->exp;
+  if (e.dtype == 0)
+    hipLaunchKernelGGL(k_exp_fetch<uint64_t>, dim3(batch), dim3(256), 0, h->stream, e, idx, (char *)s, a, r, (char *)s2,
+                       done, count);
+  else
+    hipLaunchKernelGGL(k_exp_fetch<uint32_t>, dim3(batch), dim3(256), 0, h->stream, e, idx, (char *)s, a, r, (char *)s2,
+                       done, count);
+}
+
+extern "C" int aigar_exp_sample(aigar_handle *h, int batch, const double *u, void *s, double *a, double *r, void *s2,
+                                uint8_t *done, double *w, int64_t *idx) {
+  if (need_exp(h, "exp_sample")) return -1;
+  if (batch < 1) return fail("exp_sample: batch = %d", batch);
+  if (!w || !idx) return fail("exp_sample: w and idx are needed");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  hipLaunchKernelGGL(k_exp_draw, dim3((batch + 255) / 256), dim3(256), 0, h->stream, h->exp, batch, u, w, idx);
+  launch_exp_fetch(h, idx, batch, s, a, r, s2, done, 1);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int aigar_exp_gather(aigar_handle *h, const int64_t *idx, int batch, void *s, double *a, double *r, void *s2,
+                                uint8_t *done) {
+  if (need_exp(h, "exp_gather")) return -1;
+  if (batch < 0) return fail("exp_gather: batch = %d", batch);
+  if (batch == 0) return 0;
+  if (!idx) return fail("exp_gather: null idx");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  launch_exp_fetch(h, idx, batch, s, a, r, s2, done, 0);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int aigar_exp_update_priorities(aigar_handle *h, const int64_t *idx, const double *prio, int n) {
+  if (need_exp(h, "exp_update_priorities")) return -1;
+  if (n < 0) return fail("exp_update_priorities: n = %d is negative", n);
+  if (n == 0 || !h->exp.prio) return 0;  // (ReplayBuffer.update_priorities: pass)
+  if (!idx || !prio) return fail("exp_update_priorities: null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  hipLaunchKernelGGL(k_exp_update, dim3(1), dim3(kExpPlanThreads), 0, h->stream, h->exp, idx, prio, n);
+  HIPCHK(hipGetLastError());
   return 0;
 }
 
@@ -1463,6 +1733,7 @@ extern "C" int aigar_observe_pixel_state(aigar_handle *h, void *out, int dtype, 
     if (launch_observe_pixel_state(h->d, h->stream, dst, dtype, h->pix.side, h->pix.flags, h->pix.color_seed,
                                    h->d_pix_ovf, m, h->d_pix_hist))
       return fail("bad pixel state launch");
+    if (h->exp.cap) launch_exp_latch(h, h->stream, dst, dtype, m);
   }
   HIPCHK(hipGetLastError());
   if (!on_device) {
@@ -1527,6 +1798,8 @@ extern "C" int aigar_reset_bots(aigar_handle *h, const uint8_t *mask, int on_dev
     hipLaunchKernelGGL(k_pix_hist_clear_bots, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, h->stream,
                        h->d_pix_hist, LL, np, m);
   }
+  if (h->exp.cap)  // Bot.reset: oldState = None (bot.py:186)
+    hipLaunchKernelGGL(k_exp_clear_bots, dim3((h->d.NP + 255) / 256), dim3(256), 0, h->stream, h->exp.has_old, h->d.NP, m);
   HIPCHK(hipGetLastError());
   if (mask && !on_device) HIPCHK(hipStreamSynchronize(h->stream));  // caller may reuse its buffer
   return 0;
@@ -2006,6 +2279,7 @@ extern "C" int aigar_load_state(aigar_handle *h, int arena, const aigar_state *s
     const size_t LL = (size_t)h->pix.side * h->pix.side;
     HIPCHK(hipMemsetAsync(h->d_pix_hist + p0 * LL, 0, sizeof(uint32_t) * B * LL, h->stream));
   }
+  if (h->exp.cap) HIPCHK(hipMemsetAsync(h->exp.has_old + p0, 0, B, h->stream));
   if (d.tiled) {
     HIPCHK(hipMemsetAsync(d.t_holder, 0xFF, sizeof(int) * d.NP, h->stream));
     HIPCHK(hipMemsetAsync(d.t_obsby, 0xFF, sizeof(int) * d.NP, h->stream));

@@ -41,7 +41,20 @@ the running episodes' [NP, 4] samples / sum / max / deaths; when an arena's epis
 ends its rows move to `last_score` (and the NN players' summed rewards to
 `last_return`) before the arena is reset, and `test_score()` reduces them to the
 reference's meanMass and maxMass per arena.  The warm-up is not scored.
+
+Replay memory (`memory=True` or a dict; replay_buffer.py, aigar.py:1109-1125): the
+stepper keeps the learners' experience replay memory on the device.  Every `step`
+appends, inside its graph, the NN players' (oldState, action, reward, newState, done)
+transitions of bot.py:204-217 (a dead player's newState is a NaN row and done is set;
+a time-limit end is not a done, aigar.py:851-887); `sample()` draws a mini-batch into
+device tensors, uniform or prioritized with importance weights, and
+`update_priorities()` writes the trainer's |td| + 1e-4 back (aigar.py:1075-1086).
+`memory=True` reads MEMORY_CAPACITY, PRIORITIZED_EXP_REPLAY_ENABLED, MEMORY_ALPHA,
+MEMORY_BETA and MEMORY_BATCH_LEN from `parameters`; a dict (capacity, prioritized,
+alpha, beta, batch, seed) overrides them.  It is never switched on by `parameters` alone.
 """
+import collections
+
 import numpy as np
 
 from . import _abi
@@ -49,10 +62,13 @@ from ._lib import Stepper
 from .model import obs_masks, pixel_params
 
 
+Batch = collections.namedtuple("Batch", "s a r s2 done w idx")
+
+
 class AgarVecEnv:
     def __init__(self, n_players, parameters=None, n_arenas=1, virus=None, field_size=0, max_pellets=-1.0,
                  max_viruses=-1.0, device=0, torch_stream=True, roles=None, reset_limit=None, desync=True, seed=0,
-                 score=False, pixels=None, pixel_dtype=None):
+                 score=False, pixels=None, pixel_dtype=None, memory=None):
         import torch
         self.torch = torch
         self.parameters = parameters
@@ -118,6 +134,70 @@ class AgarVecEnv:
             # the last finished episode of every arena: NaN until its first episode has ended
             self.last_score = torch.full((self.NP, 4), nan, dtype=torch.float64, device=self.dev)
             self.last_return = torch.full((self.NP,), nan, dtype=torch.float64, device=self.dev)
+        self.memory = None
+        self._mem_sync = not torch_stream  # (the stepper's work is then not ordered with torch's)
+        if memory:  # (explicit only: existing callers pass full parameter sets)
+            m = {"capacity": int(g("MEMORY_CAPACITY", 40000)),
+                 "prioritized": bool(g("PRIORITIZED_EXP_REPLAY_ENABLED", False)),
+                 "alpha": float(g("MEMORY_ALPHA", 0.6)), "beta": float(g("MEMORY_BETA", 0.4)),
+                 "batch": int(g("MEMORY_BATCH_LEN", 32)), "seed": self.seed}
+            if isinstance(memory, dict):
+                unknown = set(memory) - set(m)
+                if unknown:
+                    raise ValueError("memory: unknown keys %s" % sorted(unknown))
+                m.update(memory)
+            self.memory = m
+            self.stepper.exp_config(m["capacity"], prioritized=m["prioritized"], alpha=m["alpha"], beta=m["beta"],
+                                    dtype=self.obs.dtype, seed=m["seed"])
+
+    def sample(self, batch=None, u=None):
+        """One mini-batch of the replay memory as device tensors (s, a, r, s2, done, w, idx):
+        batch draws (MEMORY_BATCH_LEN by default), from the float64 tensor u [batch] in [0, 1)
+        or the memory's own stream.  w are the importance weights (1.0 in uniform mode).  A
+        memory too small to draw from gives idx -1 and w NaN (rows zero)."""
+        if self.memory is None:
+            raise RuntimeError("AgarVecEnv was created without memory=")
+        torch = self.torch
+        n = int(self.memory["batch"] if batch is None else batch)
+        row = tuple(self.obs.shape[1:])
+        s = torch.zeros((n,) + row, dtype=self.obs.dtype, device=self.dev)
+        s2 = torch.zeros_like(s)
+        a = torch.zeros((n, 4), dtype=torch.float64, device=self.dev)
+        r = torch.zeros(n, dtype=torch.float64, device=self.dev)
+        done = torch.zeros(n, dtype=torch.bool, device=self.dev)
+        w = torch.empty(n, dtype=torch.float64, device=self.dev)
+        idx = torch.empty(n, dtype=torch.int64, device=self.dev)
+        if u is not None:
+            u = torch.as_tensor(u, dtype=torch.float64, device=self.dev).contiguous()
+        if self._mem_sync:
+            torch.cuda.synchronize(self.dev)
+        self.stepper.exp_sample(w, idx, u=u, s=s, a=a, r=r, s2=s2, done=done)
+        if self._mem_sync:
+            self.stepper.sync()
+        return Batch(s, a, r, s2, done, w, idx)
+
+    def update_priorities(self, idx, td_error):
+        """The trainer's write-back (aigar.py:1075-1086): priority |td_error| + 1e-4 for the
+        sampled idx; nothing in uniform mode (ReplayBuffer.update_priorities)."""
+        if self.memory is None:
+            raise RuntimeError("AgarVecEnv was created without memory=")
+        if not self.memory["prioritized"]:
+            return
+        torch = self.torch
+        idx = torch.as_tensor(idx, dtype=torch.int64, device=self.dev).contiguous()
+        td = torch.as_tensor(td_error, dtype=torch.float64, device=self.dev).contiguous()
+        prio = td.abs() + 1e-4
+        if self._mem_sync:
+            torch.cuda.synchronize(self.dev)
+        self.stepper.exp_update_priorities(idx, prio)
+        if self._mem_sync:
+            self.stepper.sync()  # (prio is freed when this returns)
+
+    def memory_size(self):
+        """Transitions the memory holds (aigar_exp_info: a host round trip)."""
+        if self.memory is None:
+            raise RuntimeError("AgarVecEnv was created without memory=")
+        return int(self.stepper.exp_info()["size"])
 
     def reset(self, seed=None):
         """Field.reset + every bot's reset (lastMass = None, history grids cleared);

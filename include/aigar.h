@@ -339,6 +339,80 @@ int aigar_pixel_config(aigar_handle *h, const aigar_pixel_params *p);
 int aigar_pixel_state_len(aigar_handle *h);
 int aigar_observe_pixel_state(aigar_handle *h, void *out, int dtype, int on_device, const uint8_t *mask,
                               int mask_on_device);
+/* The learners' experience replay memory (replay_buffer.py: ReplayBuffer and
+ * PrioritizedReplayBuffer over common/segment_tree.py; driven by aigar.py:1109-1125,
+ * 1174-1177, 1075-1086), owned by the handle: a ring of `capacity` transitions
+ * (state, action[4], reward, next state, done) and, prioritized, the sum and min trees
+ * of 2 * it_cap doubles (it_cap: the next power of two >= capacity), all on the device.
+ *
+ * aigar_exp_config allocates and clears it (NULL or capacity 0: frees it) and drops the
+ * captured decision graph.  The state width is aigar_pixel_state_len() when a pixel
+ * config is set, else aigar_obs_len(); capacity must be at least n_arenas *
+ * bots_per_arena (one decision's transitions); tiled handles are refused.  While a
+ * memory is set, aigar_pixel_config is refused (the rows keep their width) and so is an
+ * aigar_env_step whose dtype differs from state_dtype.  A failed allocation is an error
+ * return.
+ *
+ * Transitions.  Every player carries an old state (Bot.oldState, bot.py:186): the last
+ * state an observation call computed for it while it was alive -- set by aigar_observe*,
+ * aigar_observe_pixel_state (for the players they observe) and aigar_env_step, cleared
+ * by a NaN state (a dead player: the reference's None) and wherever the bots' history
+ * is: aigar_reset, aigar_reset_arenas, aigar_load_state, aigar_reset_bots.  After its
+ * observation, aigar_env_step appends, still in its one graph, one transition for every
+ * NN player that had an old state (bot.py:204-217): the old state, this call's action
+ * padded with zeros to 4 values, this call's window reward, the new state row (NaN if
+ * the player is dead) and done = the player is dead; the new state then becomes the old
+ * state (none if dead).  So a player dead at decision time contributes nothing, no
+ * transition bridges a death or a reset, and a time-limit end is not marked done
+ * (aigar.py:851-887).  Greedy and Random players never contribute.  Slots are given in
+ * ascending player index starting at next_idx and wrap at capacity; size = min(size + n,
+ * capacity) -- ReplayBuffer.add once per transition in that order (replay_buffer.py:24-31).
+ * A new slot's leaf is pow(max_priority, alpha) (max_priority starts at 1.0).
+ *
+ * aigar_exp_add: the same add for caller rows i < n with mask[i] != 0 (NULL: all), in
+ * row order: s, s2 [n][width] of state_dtype, a [n][4], r [n], done [n]; host pointers
+ * (copied during the call) or, on_device, device pointers on the handle's stream.  Of
+ * more than capacity rows the last capacity remain, as in the reference.
+ * aigar_exp_info (synchronises): capacity, size, next_idx, transitions ever added.
+ *
+ * aigar_exp_sample: ALL pointers are DEVICE pointers; stream-ordered, no host round trip
+ * (size is read on the device, so the call can sit in a caller's graph).  u[batch] are
+ * the draws in [0, 1); u NULL: the device draws u_k as the top 53 bits of Philox keyed
+ * by (seed, number of sample calls so far, k).  Uniform: idx = floor(u * size), w = 1.0.
+ * Prioritized, replay_buffer.py:114-171 bit for bit, quirks included: mass = u *
+ * sum(0, size - 1), which reduces the leaves [0, size - 2] (the newest-indexed item is
+ * left out of the mass), associated the way _reduce_helper nests a prefix range
+ * (v[left] + (v[left'] + ...)); then find_prefixsum_idx (> goes left, else subtract and
+ * go right); w = pow(leaf / total * size, -beta) / pow(min / total * size, -beta) with
+ * total and min the tree roots; every pow is glibc's (aigar_selftest_pow).  Row k of
+ * s, a, r, s2, done (each may be NULL) gets transition idx[k].  A memory too small to
+ * draw from (size 0; size < 2 when prioritized, where the reference recurses forever)
+ * gives idx = -1 and w = NaN and leaves the rows as they are; no error is raised.
+ * aigar_exp_gather: the same row fetch for the caller's idx[batch] (DEVICE pointers);
+ * rows whose index is outside [0, size) are left untouched.
+ *
+ * aigar_exp_update_priorities (replay_buffer.py:173-195, batched; DEVICE pointers,
+ * stream-ordered): leaf idx[j] becomes pow(prio[j], alpha) in both trees; of several
+ * entries with one index the last in idx order wins; max_priority becomes the max of
+ * itself and every given priority, overwritten duplicates included.  Entries with
+ * prio <= 0 or an index outside [0, size) are skipped.  Nothing happens in uniform mode. */
+#define AIGAR_EXP_PRIORITIZED 0x1   /* PRIORITIZED_EXP_REPLAY_ENABLED */
+typedef struct aigar_exp_params {
+  int64_t capacity;     /* MEMORY_CAPACITY: transitions kept, a ring; >= n_arenas * bots_per_arena */
+  int32_t state_dtype;  /* 0 float64, 1 float32: how states are stored and handed out            */
+  int32_t flags;        /* AIGAR_EXP_*                                                            */
+  double alpha, beta;   /* MEMORY_ALPHA (>= 0), MEMORY_BETA (> 0)                                 */
+  uint64_t seed;        /* Philox salt of the memory's own sampling draws                         */
+} aigar_exp_params;
+int aigar_exp_config(aigar_handle *h, const aigar_exp_params *p);
+int aigar_exp_info(aigar_handle *h, int64_t info[4]);
+int aigar_exp_add(aigar_handle *h, const void *s, const double *a, const double *r, const void *s2,
+                  const uint8_t *done, const uint8_t *mask, int n, int on_device);
+int aigar_exp_sample(aigar_handle *h, int batch, const double *u, void *s, double *a, double *r, void *s2,
+                     uint8_t *done, double *w, int64_t *idx);
+int aigar_exp_gather(aigar_handle *h, const int64_t *idx, int batch, void *s, double *a, double *r, void *s2,
+                     uint8_t *done);
+int aigar_exp_update_priorities(aigar_handle *h, const int64_t *idx, const double *prio, int n);
 /* bot.currentAction / bot.lastAction used by the action extras: [A*B][4] each (may be NULL). */
 int aigar_set_actions(aigar_handle *h, const double *cur, const double *prev, int on_device);
 /* Bot.reset (bot.py:125-164) for the players with mask[i] != 0 (NULL: all): the

@@ -2,7 +2,8 @@
 """Learner-loop throughput: AgarVecEnv decisions at C3
 size with the reference's NN-bot frame skipping (FRAME_SKIP_RATE = 7,
 networkParameters.py:33), one graph replay per decision (env.step) against the
-same decision as separate calls (env.step_calls).  Prints one JSON line."""
+same decision as separate calls (env.step_calls).  Prints one JSON line.
+--memory: the replay memory's cost at the same shape instead (see memory())."""
 import json
 import os
 import sys
@@ -13,13 +14,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def parameters():
+    return types.SimpleNamespace(VIRUS_SPAWN=True, ENABLE_SPLIT=True, PELLET_GRID=True, SELF_GRID=True, WALL_GRID=True,
+                                 ENEMY_GRID=True, VIRUS_GRID=True, SELF_GRID_LF=True, ENEMY_GRID_LF=True,
+                                 USE_FOVSIZE=True, USE_TOTALMASS=True, USE_LAST_ACTION=True, USE_LAST_FOVSIZE=True,
+                                 GRID_SQUARES_PER_FOV=11, EXTRA_INPUT=True, FRAME_SKIP_RATE=7)
+
+
 def main():
     import torch
     from aigar_amd.env import AgarVecEnv
-    p = types.SimpleNamespace(VIRUS_SPAWN=True, ENABLE_SPLIT=True, PELLET_GRID=True, SELF_GRID=True, WALL_GRID=True,
-                              ENEMY_GRID=True, VIRUS_GRID=True, SELF_GRID_LF=True, ENEMY_GRID_LF=True,
-                              USE_FOVSIZE=True, USE_TOTALMASS=True, USE_LAST_ACTION=True, USE_LAST_FOVSIZE=True,
-                              GRID_SQUARES_PER_FOV=11, EXTRA_INPUT=True, FRAME_SKIP_RATE=7)
+    p = parameters()
     bots, n = 4096, 40
     out = {"workload": "C3 AgarVecEnv: 4096 NN bots, field 4800, 100k pellets, viruses, FRAME_SKIP_RATE 7",
            "ticks_per_decision": p.FRAME_SKIP_RATE + 1}
@@ -42,5 +47,64 @@ def main():
     print(json.dumps(out))
 
 
+def timed(torch, f, n):
+    """ms per call of f over n calls, device events around the batch (after 3 warm-up calls)."""
+    for _ in range(3):
+        f()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(n):
+        f()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+def memory(rounds=3, n=40):
+    """--memory: the cost of the replay memory at the same C3 shape.  Decisions with the
+    memory off and on, alternated `rounds` times (same seed, so the envs of a round play
+    the same world at the same age); the append's added time per round beside a plain device-to-device copy of the bytes it
+    writes; one sample() of 32 and of 4096 rows, uniform and prioritized."""
+    import torch
+    from aigar_amd.env import AgarVecEnv
+    p = parameters()
+    bots = 4096
+    envs = {"off": AgarVecEnv(bots, p, field_size=4800, max_pellets=100000.0),
+            "on": AgarVecEnv(bots, p, field_size=4800, max_pellets=100000.0, memory=True),
+            "on_prioritized": AgarVecEnv(bots, p, field_size=4800, max_pellets=100000.0,
+                                         memory={"prioritized": True})}
+    act = torch.rand((bots, 4), dtype=torch.float64, device="cuda")
+    for env in envs.values():
+        env.reset(1)
+        for _ in range(5):
+            env.step(act)
+    ms = {k: [] for k in envs}
+    for _ in range(rounds):
+        for k, env in envs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                env.step(act)
+            torch.cuda.synchronize()
+            ms[k].append((time.perf_counter() - t0) / n * 1e3)
+    L = envs["on"].stepper.obs_len
+    wrote = 3 * bots * L * 8  # old state -> slot, new state -> slot, new state -> old state
+    src, dst = torch.empty(wrote, dtype=torch.uint8, device="cuda"), torch.empty(wrote, dtype=torch.uint8, device="cuda")
+    out = {"workload": "C3 AgarVecEnv, 4096 NN bots, FRAME_SKIP_RATE 7, MEMORY_CAPACITY 40000, state row %d float64" % L,
+           "decisions": n, "rounds": rounds,
+           "ms_per_decision": ms, "decisions_per_s_off": [1e3 / x for x in ms["off"]],
+           # per round: the three envs play the same world, whose decisions get dearer as it matures
+           "added_ms_per_decision": {k: [x - y for x, y in zip(ms[k], ms["off"])] for k in ("on", "on_prioritized")},
+           "append_bytes_written": wrote, "d2d_copy_same_bytes_ms": timed(torch, lambda: dst.copy_(src), 200),
+           "memory_size": envs["on"].memory_size(), "sample_ms": {}}
+    for k in ("on", "on_prioritized"):
+        for batch in (32, 4096):
+            out["sample_ms"]["%s_%d" % (k, batch)] = timed(torch, lambda: envs[k].sample(batch), 200)
+    for env in envs.values():
+        env.close()
+    print(json.dumps(out))
+
+
 if __name__ == "__main__":
-    main()
+    memory() if "--memory" in sys.argv else main()
