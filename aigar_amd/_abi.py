@@ -52,6 +52,18 @@ class ExpParams(C.Structure):
                 ("beta", C.c_double), ("seed", C.c_uint64)]
 
 
+DECIDE_EGREEDY, DECIDE_BOLTZMANN = 0, 1  # aigar_decide_params.strategy (EXPLORATION_STRATEGY)
+STRATEGIES = {"e-Greedy": DECIDE_EGREEDY, "Boltzmann": DECIDE_BOLTZMANN}
+DECIDE_MAX_OUT = 1024
+WARN_Q_NONFINITE = 0x8  # aigar_warnings: a live player's Q row held a NaN or an infinity
+
+
+class DecideParams(C.Structure):
+    """aigar_decide_params (include/aigar.h): the Q-learning bots' action selection (qLearning.py:208-243)."""
+    _fields_ = [("n_out", C.c_int32), ("strategy", C.c_int32), ("q_dtype", C.c_int32), ("pad", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
 class RunParams(C.Structure):
     """aigar_run_params (include/aigar.h): the policy replayed inside aigar_run's step graph."""
     _fields_ = [("policy", C.c_int32), ("greedy_split", C.c_int32), ("p_split", C.c_double),

@@ -94,6 +94,10 @@ def load(build_if_missing=False):
         "aigar_exp_sample": [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp],
         "aigar_exp_gather": [vp, vp, i32, vp, vp, vp, vp, vp],
         "aigar_exp_update_priorities": [vp, vp, vp, i32],
+        "aigar_decide_config": [vp, C.POINTER(_abi.DecideParams), vp],
+        "aigar_decide": [vp, vp, vp, vp, vp, vp, vp],
+        "aigar_env_step_q": [vp, vp, vp, vp, i32, i32, C.POINTER(_abi.RewardParams), vp, vp, i32, vp, vp],
+        "aigar_warnings": [vp, i32, C.POINTER(C.c_uint32)],
         "aigar_set_actions": [vp, vp, vp, i32],
         "aigar_reset_bots": [vp, vp, i32],
         "aigar_player_stats": [vp, vp, i32],
@@ -177,6 +181,7 @@ class Stepper:
         self.obs_len = self.L.aigar_obs_len(self.h)
         self.pixel_state_shape = None  # (NP, side, side, C) while a pixel state is configured
         self.exp = None  # (state row shape, state dtype name, prioritized) while a replay memory is configured
+        self.dec = None  # (n_out, q dtype name) while an action selection is configured
 
     def _chk(self, r):
         if r < 0:
@@ -490,6 +495,77 @@ class Stepper:
         self._check_dev(idx, (n,), ("int64",), "exp_update_priorities")
         self._check_dev(prio, (n,), ("float64",), "exp_update_priorities")
         self._chk(self.L.aigar_exp_update_priorities(self.h, C.c_void_p(idx.data_ptr()), C.c_void_p(prio.data_ptr()), n))
+
+    # ---- action selection of the Q-learning bots (include/aigar.h: aigar_decide*)
+    def decide_config(self, actions, strategy="e-Greedy", q_dtype="float32", seed=0):
+        """The handle's action selection (qLearning.py:208-243): actions is the table
+        [n_out, 4] (aigar_amd.actions.discrete_actions), strategy "e-Greedy" or "Boltzmann"
+        (or its code), q_dtype the dtype of the Q rows, seed the salt of the own draws.
+        decide_config(None) turns it off."""
+        if actions is None:
+            self._chk(self.L.aigar_decide_config(self.h, None, None))
+            self.dec = None
+            return
+        t = np.ascontiguousarray(actions, np.float64)
+        if t.ndim != 2 or t.shape[1] != 4:
+            raise ValueError("decide_config: the action table must be [n_out, 4], got %s" % (t.shape,))
+        d = str(q_dtype).replace("torch.", "").replace("<class 'numpy.", "").replace("'>", "")
+        if d not in ("float64", "float32"):
+            raise ValueError("decide_config: q_dtype must be float64 or float32, got %s" % (q_dtype,))
+        st = _abi.STRATEGIES[strategy] if isinstance(strategy, str) else int(strategy)
+        prm = _abi.DecideParams(int(t.shape[0]), st, 0 if d == "float64" else 1, 0, int(seed) & 0xFFFFFFFFFFFFFFFF)
+        self._chk(self.L.aigar_decide_config(self.h, C.byref(prm), t.ctypes.data_as(C.c_void_p)))
+        self.dec = (int(t.shape[0]), d)
+
+    def _decide_args(self, q, explore, u, idx, val, what):
+        if self.dec is None:
+            raise RuntimeError("aigar: %s: no action selection is configured (decide_config)" % what)
+        n, d = self.dec
+        self._check_dev(q, (self.NP, n), (d,), what)
+        self._check_dev(explore, (2,), ("float64",), what)
+        self._check_dev(idx, (self.NP,), ("int32",), what)
+        self._check_dev(val, (self.NP,), ("float64",), what)
+        up = None
+        if u is not None:
+            self._check_dev(u, (self.NP, 3), ("float64",), what)
+            up = C.c_void_p(u.data_ptr())
+        return C.c_void_p(q.data_ptr()), C.c_void_p(explore.data_ptr()), up
+
+    def decide(self, q, explore, idx, val, u=None, act=None):
+        """The selection alone on device tensors (aigar_decide): q [NP, n_out], explore
+        [epsilon, temperature] float64, u [NP, 3] float64 draws in [0, 1) (None: the own
+        Philox stream); writes idx [NP] int32, val [NP] float64 and the chosen table rows
+        into act [NP, 4] (dead and non-NN players: -1, NaN, row untouched)."""
+        qp, ep, up = self._decide_args(q, explore, u, idx, val, "decide")
+        ap = None
+        if act is not None:
+            self._check_dev(act, (self.NP, 4), ("float64",), "decide")
+            ap = C.c_void_p(act.data_ptr())
+        self._chk(self.L.aigar_decide(self.h, qp, ep, up, C.c_void_p(idx.data_ptr()), C.c_void_p(val.data_ptr()), ap))
+
+    def env_step_q(self, q, explore, reward, obs, idx, val, u=None, enable_split=True, skip=0, params=None):
+        """One Q-learning decision on device tensors (aigar_env_step_q): decide, then
+        env_step with the chosen table rows; one graph replay."""
+        qp, ep, up = self._decide_args(q, explore, u, idx, val, "env_step_q")
+        for t in (reward, obs):
+            if not getattr(t, "is_cuda", False) or not t.is_contiguous():
+                raise ValueError("env_step_q takes contiguous device tensors")
+        self._check_dev(reward, (self.NP,), ("float64",), "env_step_q")
+        if self.pixel_state_shape is not None:
+            self._check_out(obs, self.pixel_state_shape, ("float64", "float32"), "env_step_q")
+        else:
+            self._check_out(obs, (self.NP, self.obs_len), ("float64", "float32"), "env_step_q")
+        prm = params if isinstance(params, _abi.RewardParams) else _abi.RewardParams.from_parameters(params)
+        dt = 0 if str(obs.dtype) == "torch.float64" else 1
+        self._chk(self.L.aigar_env_step_q(self.h, qp, ep, up, int(bool(enable_split)), int(skip), C.byref(prm),
+                                          C.c_void_p(reward.data_ptr()), C.c_void_p(obs.data_ptr()), dt,
+                                          C.c_void_p(idx.data_ptr()), C.c_void_p(val.data_ptr())))
+
+    def warnings(self, arena=0):
+        """The arena's sticky quirk bits since its last reset (aigar_warnings; _abi.WARN_*)."""
+        v = C.c_uint32(0)
+        self._chk(self.L.aigar_warnings(self.h, int(arena), C.byref(v)))
+        return v.value
 
     def set_actions(self, cur=None, prev=None):
         c = None if cur is None else np.ascontiguousarray(cur, np.float64)

@@ -100,7 +100,10 @@ enum : uint32_t {
   ERR_PREDICT = 8192,      // updatePlayers made other counts than k_players' arena block predicted (head_counts)
   ERR_TILE_HANDOFF = 16384  // more dead bots to hand off in one tick than a message has hand-off slots
 };
-enum : uint32_t { WARN_NEW_VIRUS_EATS = 1, WARN_DEAD_VIRUS = 2, WARN_TILE_OBS = 4 };
+enum : uint32_t {
+  WARN_NEW_VIRUS_EATS = 1, WARN_DEAD_VIRUS = 2, WARN_TILE_OBS = 4,
+  WARN_Q_NONFINITE = 8  // k_decide met a NaN or an infinity in a live player's Q row (index 0 was taken)
+};
 enum : uint32_t { DIRTY_VIRUS = 1, DIRTY_BLOB = 2 };
 
 // event phases (sort key high word), in reference order within a tick

@@ -219,15 +219,27 @@ AIGAR_HD double glibc_exp_inline(double x, double xtail) {
   uint64_t sbits = gexp_data(15 + (int)idx) + top;
   const double r2 = r * r;
   const double tmp = fma(fma(r, C5, C4), r2 * r2, fma(fma(r, C3, C2), r2, r + tail));
-  if (abstop == 0) {  // glibc specialcase (results near overflow / underflow; not on the stepper's path)
+  if (abstop == 0) {  // glibc specialcase (results near overflow / underflow)
     if ((ki & 0x80000000ull) == 0) {
       sbits -= 1009ull << 52;
       const double scale = as_double(sbits);
       return 0x1p1009 * fma(tmp, scale, scale);
     }
+    // k < 0: results below 2^-1022 (the Boltzmann weights of a small temperature,
+    // decide.inc) are re-rounded around 1.0 before the scaling, so that the
+    // subnormal result is rounded once.  No fma here: scale * tmp is one product
+    // used twice in glibc's object code (tools/gen/check_decide_pow.cpp).
     sbits += 1022ull << 52;
     const double scale = as_double(sbits);
-    return 0x1p-1022 * (scale + scale * tmp);  // (subnormal double rounding not restated)
+    double y = scale + scale * tmp;
+    if (y < 1.0) {  // (sign_bias 0: scale > 0, y >= 0)
+      double lo = scale - y + scale * tmp;
+      const double hi = 1.0 + y;
+      lo = 1.0 - hi + y + lo;
+      y = (hi + lo) - 1.0;
+      if (y == 0.0) y = 0.0;  // the sign of zero: +0
+    }
+    return 0x1p-1022 * y;
   }
   const double scale = as_double(sbits);
   return fma(tmp, scale, scale);

@@ -52,6 +52,7 @@ void launch_set_commands(const Dev &d, hipStream_t s, const double *cmd);
 using namespace aigar;
 
 #include "replay.inc"
+#include "decide.inc"
 
 static thread_local std::string g_err;
 static int fail(const char *fmt, ...) {
@@ -206,7 +207,18 @@ struct aigar_handle {
     aigar_pixel_params pix;  // side 0: the grid row
     uint32_t *pix_hist;
     const void *exp;  // the replay memory the decision appends to (null: none)
+    const double *exp_act;  // ... and the action rows it stores, [NP][exp_n_act]
+    int exp_n_act;
+    // aigar_env_step_q: the selection in front of the decision (q null: none)
+    const void *q;
+    const double *explore, *u;
+    int32_t *idx_out;
+    double *val_out;
+    Decide dec;
   } env_key{};
+  // aigar_decide_config: the Q-learning bots' action selection (decide.inc; n_out 0: off)
+  Decide dec{};
+  std::vector<void *> dec_allocs;
   // aigar_exp_config: the learners' replay memory (replay.inc; cap 0: off)
   Exp exp;
   std::vector<void *> exp_allocs;
@@ -272,6 +284,9 @@ static void free_all(aigar_handle *h) {
   h->d_pix_hist = nullptr;
   for (void *p : h->exp_allocs) (void)hipFree(p);
   h->exp_allocs.clear();
+  for (void *p : h->dec_allocs) (void)hipFree(p);
+  h->dec_allocs.clear();
+  h->dec = Decide{};
   if (h->d_exp_off) (void)hipFree(h->d_exp_off);
   h->d_exp_off = nullptr;
   h->exp = Exp{};
@@ -1278,19 +1293,16 @@ static void launch_env_decision(aigar_handle *h, hipStream_t s, const aigar_hand
     (void)launch_observe_pixel_state(h->d, s, k.obs, k.dtype, k.pix.side, k.pix.flags, k.pix.color_seed, h->d_pix_ovf,
                                      nn, k.pix_hist);
   else launch_observe(h->d, s, k.obs, k.dtype, 0, nn);
-  if (k.exp) launch_exp_append(h, s, k.act, k.n_act, k.reward, k.obs);
+  if (k.exp) launch_exp_append(h, s, k.exp_act, k.exp_n_act, k.reward, k.obs);
 }
 
-extern "C" int aigar_env_step(aigar_handle *h, const double *act, int n_act, int enable_split, int skip,
-                              const aigar_reward_params *p, double *reward_out, void *obs_out, int dtype) {
-  if (!h || !act || !p || !reward_out || !obs_out) return fail("null argument");
-  if (n_act < 2 || n_act > 4) return fail("env_step: n_act must be 2, 3 or 4");
+// The decision of aigar_env_step / aigar_env_step_q: the key's common part, then the
+// replay of its graph (k.q: the selection's kernel in front, decide.inc).
+static int env_step_keyed(aigar_handle *h, aigar_handle::EnvKey &k, int enable_split, int skip,
+                          const aigar_reward_params *p, double *reward_out, void *obs_out, int dtype) {
   if (skip < 0) return fail("env_step: skip < 0");
   if (dtype != 0 && dtype != 1) return fail("dtype must be 0 (float64) or 1 (float32)");
   HIPCHK(hipSetDevice(h->cfg.device));
-  aigar_handle::EnvKey k{};
-  k.act = act;
-  k.n_act = n_act;
   k.enable_split = enable_split ? 1 : 0;
   k.skip = skip;
   k.dtype = dtype;
@@ -1303,18 +1315,26 @@ extern "C" int aigar_env_step(aigar_handle *h, const double *act, int n_act, int
   k.pix = h->pix;
   k.pix_hist = h->d_pix_hist;
   k.exp = h->exp.cap ? h->exp.ctl : nullptr;
+  if (!k.q) {  // (the selection stores the index, [NP][1])
+    k.exp_act = k.act;
+    k.exp_n_act = k.n_act;
+  }
   if (h->exp.cap && dtype != h->exp.dtype)
     return fail("env_step: dtype %d differs from the replay memory's state_dtype %d (aigar_exp_config)", dtype,
                 h->exp.dtype);
   if (k.pix.side && ((uintptr_t)obs_out & 15)) return fail("env_step: the pixel state's obs_out must be 16-byte aligned");
   if (h->d.flags & AIGAR_FLAG_EVENTS)  // the event log holds the window's ticks
     hipLaunchKernelGGL(k_step_begin, dim3((h->d.A + 63) / 64), dim3(64), 0, h->stream, h->d);
+  auto launch = [&](hipStream_t cs) {
+    if (k.q) launch_decide(h->d, cs, k.dec, k.q, k.explore, k.u, k.idx_out, k.val_out, k.dec.act);
+    launch_env_decision(h, cs, k);
+  };
   if (!h->use_graph) {
-    launch_env_decision(h, h->stream, k);
+    launch(h->stream);
   } else {
     if (!h->env_graph || memcmp(&h->env_key, &k, sizeof k) != 0) {
       if (h->env_graph) (void)hipGraphExecDestroy(h->env_graph);
-      h->env_graph = capture_graph(h, [&](hipStream_t cs) { launch_env_decision(h, cs, k); });
+      h->env_graph = capture_graph(h, launch);
       if (!h->env_graph) return fail("env_step: graph capture failed");
       h->env_key = k;
     }
@@ -1322,6 +1342,111 @@ extern "C" int aigar_env_step(aigar_handle *h, const double *act, int n_act, int
     HIPCHK(hipGraphLaunch(h->env_graph, h->stream));
   }
   HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int aigar_env_step(aigar_handle *h, const double *act, int n_act, int enable_split, int skip,
+                              const aigar_reward_params *p, double *reward_out, void *obs_out, int dtype) {
+  if (!h || !act || !p || !reward_out || !obs_out) return fail("null argument");
+  if (n_act < 2 || n_act > 4) return fail("env_step: n_act must be 2, 3 or 4");
+  aigar_handle::EnvKey k{};
+  k.act = act;
+  k.n_act = n_act;
+  return env_step_keyed(h, k, enable_split, skip, p, reward_out, obs_out, dtype);
+}
+
+// ------------------------------------------------------------ action selection
+static void dec_free(aigar_handle *h) {
+  for (void *p : h->dec_allocs) (void)hipFree(p);
+  h->dec_allocs.clear();
+  h->dec = Decide{};
+}
+static int need_dec(aigar_handle *h, const char *who) {
+  if (!h) return fail("null handle");
+  if (!h->dec.n_out) return fail("%s: no action selection is configured (aigar_decide_config)", who);
+  return 0;
+}
+
+extern "C" int aigar_decide_config(aigar_handle *h, const aigar_decide_params *p, const double *actions) {
+  if (!h) return fail("null handle");
+  if (p) {
+    if (h->d.tiled) return fail("decide_config: a tiled handle has no action selection");
+    if (!actions) return fail("decide_config: null action table");
+    if (p->n_out < 1 || p->n_out > 1024) return fail("decide_config: n_out = %d is outside 1..1024", p->n_out);
+    if (p->strategy != 0 && p->strategy != 1) return fail("decide_config: strategy must be 0 (e-Greedy) or 1 (Boltzmann)");
+    if (p->q_dtype != 0 && p->q_dtype != 1) return fail("decide_config: q_dtype must be 0 (float64) or 1 (float32)");
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));  // (no replay of the graph is pending)
+  if (h->env_graph) (void)hipGraphExecDestroy(h->env_graph);
+  h->env_graph = nullptr;
+  dec_free(h);
+  if (!p) return 0;
+  Decide c{};
+  c.n_out = p->n_out;
+  c.strategy = p->strategy;
+  c.q_dtype = p->q_dtype;
+  c.seed = p->seed;
+  const size_t NP = (size_t)h->d.NP, nt = (size_t)c.n_out * 4;
+  void *m[3] = {nullptr, nullptr, nullptr};
+  const size_t bytes[3] = {nt * sizeof(double), NP * 4 * sizeof(double), NP * sizeof(double)};
+  for (int i = 0; i < 3; i++) {
+    if (hipMalloc(&m[i], bytes[i]) != hipSuccess) {
+      (void)hipGetLastError();
+      dec_free(h);
+      return fail("decide_config: out of device memory");
+    }
+    h->dec_allocs.push_back(m[i]);
+  }
+  c.table = (double *)m[0];
+  c.act = (double *)m[1];
+  c.idx = (double *)m[2];
+  HIPCHK(hipMemcpyAsync(c.table, actions, bytes[0], hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(c.act, 0, bytes[1], h->stream));
+  hipLaunchKernelGGL(k_fill_d, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, h->stream, c.idx, NP, -1.0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's table is read)
+  h->dec = c;
+  return 0;
+}
+
+extern "C" int aigar_decide(aigar_handle *h, const void *q, const double *explore, const double *u, int32_t *idx_out,
+                            double *val_out, double *act_out) {
+  if (need_dec(h, "decide")) return -1;
+  if (!q || !explore || !idx_out || !val_out) return fail("decide: null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  launch_decide(h->d, h->stream, h->dec, q, explore, u, idx_out, val_out, act_out);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int aigar_env_step_q(aigar_handle *h, const void *q, const double *explore, const double *u,
+                                int enable_split, int skip, const aigar_reward_params *p, double *reward_out,
+                                void *obs_out, int dtype, int32_t *idx_out, double *val_out) {
+  if (need_dec(h, "env_step_q")) return -1;
+  if (!q || !explore || !p || !reward_out || !obs_out || !idx_out || !val_out) return fail("env_step_q: null argument");
+  aigar_handle::EnvKey k{};
+  k.act = h->dec.act;
+  k.n_act = 4;
+  k.q = q;
+  k.explore = explore;
+  k.u = u;
+  k.idx_out = idx_out;
+  k.val_out = val_out;
+  k.dec = h->dec;
+  k.exp_act = h->dec.idx;
+  k.exp_n_act = 1;
+  return env_step_keyed(h, k, enable_split, skip, p, reward_out, obs_out, dtype);
+}
+
+extern "C" int aigar_warnings(aigar_handle *h, int arena, uint32_t *out) {
+  if (!h || !out) return fail("null argument");
+  if (arena < 0 || arena >= h->d.A) return fail("arena out of range");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  ArenaCtl c;
+  HIPCHK(hipMemcpyAsync(&c, h->d.ctl + arena, sizeof c, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  *out = c.warn;
   return 0;
 }
 

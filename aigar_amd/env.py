@@ -52,12 +52,25 @@ device tensors, uniform or prioritized with importance weights, and
 `memory=True` reads MEMORY_CAPACITY, PRIORITIZED_EXP_REPLAY_ENABLED, MEMORY_ALPHA,
 MEMORY_BETA and MEMORY_BATCH_LEN from `parameters`; a dict (capacity, prioritized,
 alpha, beta, batch, seed) overrides them.  It is never switched on by `parameters` alone.
+
+Q-learning (`discrete=True` or a dict; qLearning.py:208-243, network.py:26-65): the learner's
+network gives one value per discrete action, and `step_q(q)` makes the reference's decideMove
+for every live NN player on the device, inside the decision's graph: the e-Greedy coin, the
+Boltzmann draw or argmax, then the row of the action table as the 4-value action.  `actions` is
+the table, `explore` the device tensor [epsilon, temperature] the decision reads (write it, or
+call `set_exploration`, to follow a decay schedule: no re-capture), `action_idx` and
+`action_value` the chosen indices and the reference's qValues entries (NaN when exploring, the
+probability under Boltzmann).  With a replay memory the stored action row is [index, 0, 0, 0]
+(bot.py:206).  `discrete=True` reads NUM_ACTIONS, SQUARE_ACTIONS, EXPLORATION_STRATEGY, EPSILON
+and TEMPERATURE from `parameters`; a dict (num_actions, square, strategy, seed) overrides them.
+All players of one decision see the same epsilon and temperature; the decay schedule stays
+with the caller.  It is never switched on by `parameters` alone.
 """
 import collections
 
 import numpy as np
 
-from . import _abi
+from . import _abi, actions as _actions
 from ._lib import Stepper
 from .model import obs_masks, pixel_params
 
@@ -68,7 +81,7 @@ Batch = collections.namedtuple("Batch", "s a r s2 done w idx")
 class AgarVecEnv:
     def __init__(self, n_players, parameters=None, n_arenas=1, virus=None, field_size=0, max_pellets=-1.0,
                  max_viruses=-1.0, device=0, torch_stream=True, roles=None, reset_limit=None, desync=True, seed=0,
-                 score=False, pixels=None, pixel_dtype=None, memory=None):
+                 score=False, pixels=None, pixel_dtype=None, memory=None, discrete=None):
         import torch
         self.torch = torch
         self.parameters = parameters
@@ -149,6 +162,92 @@ class AgarVecEnv:
             self.memory = m
             self.stepper.exp_config(m["capacity"], prioritized=m["prioritized"], alpha=m["alpha"], beta=m["beta"],
                                     dtype=self.obs.dtype, seed=m["seed"])
+
+        self.discrete = None
+        if discrete:  # (explicit only, as memory=)
+            dd = {"num_actions": int(g("NUM_ACTIONS", 25)), "square": bool(g("SQUARE_ACTIONS", True)),
+                  "strategy": g("EXPLORATION_STRATEGY", "e-Greedy"), "seed": self.seed}
+            if isinstance(discrete, dict):
+                unknown = set(discrete) - set(dd)
+                if unknown:
+                    raise ValueError("discrete: unknown keys %s" % sorted(unknown))
+                dd.update(discrete)
+            if dd["strategy"] not in _abi.STRATEGIES:
+                raise ValueError("discrete: strategy must be one of %s" % sorted(_abi.STRATEGIES))
+            self._table = _actions.discrete_actions(dd["num_actions"], dd["square"], self.enable_split,
+                                                    bool(g("ENABLE_EJECT", False)))
+            dd["n_out"] = int(self._table.shape[0])
+            self.discrete = dd
+            self.actions = torch.as_tensor(self._table, device=self.dev)
+            self.explore = torch.tensor([float(g("EPSILON", 0.0)), float(g("TEMPERATURE", 0.0))], dtype=torch.float64,
+                                        device=self.dev)
+            self._q = {}  # dtype -> persistent Q buffer (the decision graph is keyed by its address)
+            self._u = torch.empty((self.NP, 3), dtype=torch.float64, device=self.dev)
+            self._idx = torch.empty(self.NP, dtype=torch.int32, device=self.dev)
+            self._val = torch.empty(self.NP, dtype=torch.float64, device=self.dev)
+            self.action_idx = self.action_value = None
+            self._act_q = torch.zeros((self.NP, 4), dtype=torch.float64, device=self.dev)  # step_q_calls' chosen rows
+            self._q_dtype = None
+            self._decide_dtype(torch.float32)
+
+    def _decide_dtype(self, dtype):
+        """(Re)configure the selection for Q rows of dtype (the kernel is built per dtype)."""
+        if dtype is not self._q_dtype:
+            self.stepper.decide_config(self._table, self.discrete["strategy"], dtype, self.discrete["seed"])
+            self._q_dtype = dtype
+
+    def set_exploration(self, epsilon=None, temperature=None):
+        """Write the decision's epsilon and / or temperature (the device tensor `explore`)."""
+        self._need_discrete()
+        if epsilon is not None:
+            self.explore[0] = float(epsilon)
+        if temperature is not None:
+            self.explore[1] = float(temperature)
+
+    def _need_discrete(self):
+        if self.discrete is None:
+            raise RuntimeError("AgarVecEnv was created without discrete=")
+
+    def _q_buffers(self, q, u):
+        torch = self.torch
+        self._need_discrete()
+        if not isinstance(q, torch.Tensor):
+            q = torch.as_tensor(np.asarray(q), device=self.dev)
+        if q.dtype not in (torch.float32, torch.float64):
+            raise ValueError("step_q: q must be float32 or float64, got %s" % q.dtype)
+        if tuple(q.shape) != (self.NP, self.discrete["n_out"]):
+            raise ValueError("step_q: q must be [%d, %d], got %s" % (self.NP, self.discrete["n_out"], tuple(q.shape)))
+        buf = self._q.get(q.dtype)
+        if buf is None:
+            buf = self._q[q.dtype] = torch.empty((self.NP, self.discrete["n_out"]), dtype=q.dtype, device=self.dev)
+        buf.copy_(q)
+        self._decide_dtype(q.dtype)
+        if u is not None:
+            self._u.copy_(torch.as_tensor(u, dtype=torch.float64, device=self.dev))
+            u = self._u
+        return buf, u
+
+    def step_q(self, q, u=None):
+        """q: [n_players, n_out] float32 / float64 device tensor of action values (rows of
+        dead and non-NN players are ignored) -> (obs, reward, alive, done) as `step`; the
+        selection and the decision are one graph replay.  u: [n_players, 3] draws in [0, 1)
+        (coin, explore index, Boltzmann draw), None: the device's own.  Leaves fresh clones in
+        `action_idx` (int32, -1 where nobody decided) and `action_value`."""
+        buf, u = self._q_buffers(q, u)
+        self.stepper.env_step_q(buf, self.explore, self._r, self.obs, self._idx, self._val, u=u,
+                                enable_split=self.enable_split, skip=self.skip, params=self.reward_params)
+        self.action_idx, self.action_value = self._idx.clone(), self._val.clone()
+        return self._after_decision()
+
+    def step_q_calls(self, q, u=None):
+        """The same decision as separate calls (decide, then `step_calls`); without the
+        episode bookkeeping."""
+        buf, u = self._q_buffers(q, u)
+        # (persistent, as the handle's own buffer in step_q: a player that does not decide
+        # keeps its last chosen row, and moves by it if it respawns on a skipped tick)
+        self.stepper.decide(buf, self.explore, self._idx, self._val, u=u, act=self._act_q)
+        self.action_idx, self.action_value = self._idx.clone(), self._val.clone()
+        return self.step_calls(self._act_q)
 
     def sample(self, batch=None, u=None):
         """One mini-batch of the replay memory as device tensors (s, a, r, s2, done, w, idx):
@@ -306,6 +405,10 @@ class AgarVecEnv:
             buf = self._act[n] = torch.empty((self.NP, n), dtype=torch.float64, device=self.dev)
         buf.copy_(act)
         self.stepper.env_step(buf, self._r, self.obs, self.enable_split, self.skip, self.reward_params)
+        return self._after_decision()
+
+    def _after_decision(self):
+        torch = self.torch
         reward = self._r.clone()
         if self._scored:
             self._ret += torch.where(self.nn, reward, torch.zeros_like(reward))

@@ -413,6 +413,62 @@ int aigar_exp_sample(aigar_handle *h, int batch, const double *u, void *s, doubl
 int aigar_exp_gather(aigar_handle *h, const int64_t *idx, int batch, void *s, double *a, double *r, void *s2,
                      uint8_t *done);
 int aigar_exp_update_priorities(aigar_handle *h, const int64_t *idx, const double *prio, int n);
+
+/* The Q-learning bots' action selection (qLearning.py:208-243 decideMove; DESIGN.md §4h;
+ * tests/decide_model.py is the specification in plain Python).  The learner's network
+ * gives one value per discrete action; the device turns every live NN player's row
+ * q[n_out] (float32 or float64, widened exactly) into an action index and applies that
+ * row of the action table as a 4-value action of aigar_apply_actions.  All arithmetic is
+ * float64 in the reference's operation order.
+ *
+ * aigar_decide_config: the table actions[n_out][4] (HOST pointer; network.py:26-65,
+ * aigar_amd/actions.py), copied to the device; p NULL: off.  Configuring or
+ * un-configuring drops the captured decision graph.  A tiled handle is refused.
+ *
+ * Per call: explore = {epsilon, temperature} is read from DEVICE memory (a decay schedule
+ * needs no re-capture); all players of a decision see the same two values.  u: DEVICE
+ * [A*B][3] draws in [0, 1), or NULL: u0, u1, u2 are the top 53 bits of the first three
+ * words of Philox keyed by the arena, at (global player, stream 10, the arena's tick, seed).
+ *   strategy 0, e-Greedy: u0 < epsilon explores: idx = floor(u1 * n_out), value NaN;
+ *     else greedy.
+ *   greedy: numpy.argmax, the first index of the maximum; value q[idx].
+ *   strategy 1, Boltzmann (no coin): temperature == 0 is greedy.  Else m = max(q),
+ *     d_i = pow(e, (q_i - m) / temperature) (glibc's pow), s = numpy.sum(d) in numpy's
+ *     pairwise association, p_i = d_i / s, cdf = cumsum(p) left to right, cdf_i /= cdf[n-1],
+ *     k = #{cdf_i <= u2} clamped to n_out - 1, idx = the first j with p_j == p_k; the value
+ *     is p[idx], the probability (the reference rebinds q_Values to the distribution).
+ * Only live NN players decide: a dead or non-NN player gets idx -1, value NaN, and its
+ * action row is left as it is -- in the handle's own action buffer (zeros at config time)
+ * its last chosen row, by which a player that respawns on a skipped tick of the window
+ * moves (bot.py:166-168 holds the bot's current action over the skipped frames).  A live player's row holding a NaN or an infinity is
+ * outside the contract: idx 0, value q[0], and warn bit AIGAR_WARN_Q_NONFINITE of its
+ * arena (aigar_warnings), no error.
+ *
+ * aigar_decide: the selection alone on the handle's stream (all DEVICE pointers): idx_out
+ * [A*B] int32, val_out [A*B], act_out [A*B][4] (may be NULL) gets the chosen rows; no
+ * command is set.  aigar_env_step_q: the selection and then aigar_env_step's whole
+ * decision with the chosen rows as its 4-value actions, one graph replay (re-captured
+ * when a pointer or a parameter changes).  With a replay memory configured the
+ * transition's action row is [idx, 0, 0, 0] (bot.py:206 stores the index).  Both are
+ * error returns without a config. */
+typedef struct aigar_decide_params {
+  int32_t n_out;      /* rows of the action table, 1..1024 */
+  int32_t strategy;   /* 0 e-Greedy, 1 Boltzmann (EXPLORATION_STRATEGY) */
+  int32_t q_dtype;    /* 0 float64, 1 float32 */
+  int32_t pad;
+  uint64_t seed;      /* Philox salt of the own draws */
+} aigar_decide_params;
+int aigar_decide_config(aigar_handle *h, const aigar_decide_params *p, const double *actions);
+int aigar_decide(aigar_handle *h, const void *q, const double *explore, const double *u, int32_t *idx_out,
+                 double *val_out, double *act_out);
+int aigar_env_step_q(aigar_handle *h, const void *q, const double *explore, const double *u, int enable_split, int skip,
+                     const aigar_reward_params *p, double *reward_out, void *obs_out, int dtype, int32_t *idx_out,
+                     double *val_out);
+/* The sticky quirk bits of one arena since its last reset (a host round trip): 1 a virus
+ * made this tick ate, 2 a dead virus was met, 4 a tile observed past its held pellets,
+ * 8 AIGAR_WARN_Q_NONFINITE. */
+#define AIGAR_WARN_Q_NONFINITE 0x8
+int aigar_warnings(aigar_handle *h, int arena, uint32_t *out);
 /* bot.currentAction / bot.lastAction used by the action extras: [A*B][4] each (may be NULL). */
 int aigar_set_actions(aigar_handle *h, const double *cur, const double *prev, int on_device);
 /* Bot.reset (bot.py:125-164) for the players with mask[i] != 0 (NULL: all): the

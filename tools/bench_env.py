@@ -3,7 +3,8 @@
 size with the reference's NN-bot frame skipping (FRAME_SKIP_RATE = 7,
 networkParameters.py:33), one graph replay per decision (env.step) against the
 same decision as separate calls (env.step_calls).  Prints one JSON line.
---memory: the replay memory's cost at the same shape instead (see memory())."""
+--memory: the replay memory's cost at the same shape instead (see memory()).
+--discrete / --discrete-baseline: the Q-learning selection's cost (see discrete())."""
 import json
 import os
 import sys
@@ -106,5 +107,67 @@ def memory(rounds=3, n=40):
     print(json.dumps(out))
 
 
+def discrete(baseline_only=False, rounds=3, n=40):
+    """--discrete: a Q-learning decision at the C3 shape (4096 NN bots, 8 ticks per decision,
+    NUM_ACTIONS 25 with split and eject: 75 outputs), both strategies: `step_q` (the selection
+    inside the decision graph) against `step` with the selection written in torch on the same
+    stream (argmax / multinomial plus a table gather), alternated `rounds` times on envs of the
+    same seed.  --discrete-baseline: the torch variant alone -- it uses nothing of the selection,
+    so it also runs on a build without it (the parent commit's side of the comparison)."""
+    import torch
+    from aigar_amd.env import AgarVecEnv
+    p = parameters()
+    p.ENABLE_EJECT, p.NUM_ACTIONS, p.SQUARE_ACTIONS, p.EPSILON, p.TEMPERATURE = True, 25, True, 0.1, 0.5
+    bots, n_out = 4096, 75
+    q = torch.randn((bots, n_out), dtype=torch.float32, device="cuda") * 2
+    out = {"workload": "C3 AgarVecEnv: 4096 NN bots, FRAME_SKIP_RATE 7, Q rows [4096, 75] float32",
+           "decisions": n, "rounds": rounds}
+    for strategy in ("e-Greedy", "Boltzmann"):
+        p.EXPLORATION_STRATEGY = strategy
+        envs = {"torch": AgarVecEnv(bots, p, field_size=4800, max_pellets=100000.0)}
+        if not baseline_only:
+            envs["step_q"] = AgarVecEnv(bots, p, field_size=4800, max_pellets=100000.0, discrete=True)
+            table = envs["step_q"].actions
+        else:  # (network.py:46-65 for 25 square actions with split and eject)
+            pts = [(c / 5 + 0.1, r / 5 + 0.1) for r in range(5) for c in range(5)]
+            table = torch.tensor([[x, y, s, e] for x, y in pts for s, e in ((0, 0), (1, 0), (0, 1))],
+                                 dtype=torch.float64, device="cuda")
+
+        def torch_step(env):
+            if strategy == "e-Greedy":
+                coin = torch.rand(bots, device="cuda") < p.EPSILON
+                idx = torch.where(coin, torch.randint(n_out, (bots,), device="cuda"), q.argmax(1))
+            else:
+                d = torch.exp((q.double() - q.double().max(1, keepdim=True).values) / p.TEMPERATURE)
+                idx = torch.multinomial(d / d.sum(1, keepdim=True), 1).squeeze(1)
+            return env.step(table[idx])
+
+        run = {"torch": lambda: torch_step(envs["torch"])}
+        if not baseline_only:
+            run["step_q"] = lambda: envs["step_q"].step_q(q)
+        for k, env in envs.items():
+            env.reset(1)
+            for _ in range(5):
+                run[k]()
+        ms = {k: [] for k in envs}
+        for _ in range(rounds):
+            for k in envs:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(n):
+                    run[k]()
+                torch.cuda.synchronize()
+                ms[k].append((time.perf_counter() - t0) / n * 1e3)
+        out[strategy] = {"ms_per_decision": ms, "decisions_per_s": {k: [1e3 / x for x in v] for k, v in ms.items()}}
+        for env in envs.values():
+            env.close()
+    print(json.dumps(out))
+
+
 if __name__ == "__main__":
-    memory() if "--memory" in sys.argv else main()
+    if "--memory" in sys.argv:
+        memory()
+    elif "--discrete" in sys.argv or "--discrete-baseline" in sys.argv:
+        discrete(baseline_only="--discrete-baseline" in sys.argv)
+    else:
+        main()
