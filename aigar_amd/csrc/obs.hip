@@ -1186,7 +1186,8 @@ __global__ void k_policy_random(Dev d, double p_split, double p_eject, uint64_t 
 
 // set_command_point (bot.py:550-577) for external actions act[NP][n_act]
 // (n_act 2, 3 or 4); during skipped frames split/eject are dropped (bot.py:266-267).
-// record: updateValues (bot.py:180-193) -- lastAction <- currentAction <- act.
+// record: updateValues (bot.py:180-193) -- lastAction <- currentAction <- act -- and
+// lastMass <- total mass (bot.py:228-230).
 __global__ void k_apply_actions(Dev d, const double *act, int n_act, int enable_split, int skipping, int record) {
   int gp = GTID;
   if (gp >= d.NP || !d.p_alive[gp]) return;  // makeMove: dead players do not move
@@ -1207,11 +1208,15 @@ __global__ void k_apply_actions(Dev d, const double *act, int n_act, int enable_
   d.p_cmdy[gp] = (double)top + a1 * (double)size;
   d.p_split[gp] = split;
   d.p_eject[gp] = eject;
-  if (record)
+  if (record) {
     for (int k = 0; k < 4; k++) {
       d.o_act_prev[(size_t)gp * 4 + k] = d.o_act_cur[(size_t)gp * 4 + k];
       d.o_act_cur[(size_t)gp * 4 + k] = k < n_act ? ac[k] : 0.0;
     }
+    // the end of move_NN (bot.py:228-230): a bot that decides has a lastMass from then on, so the
+    // first window after a reset is rewarded against the mass at its decision
+    d.o_last_mass[gp] = d.p_mass[gp];
+  }
 }
 void launch_apply_actions(const Dev &d, hipStream_t s, const double *act, int n_act, int enable_split, int skipping,
                           int record) {
@@ -1230,7 +1235,9 @@ __global__ void k_rewards(Dev d, double *out, aigar_reward_params prm, int updat
   const bool alive = d.p_alive[gp];
   const double mass = alive ? d.p_mass[gp] : 0.0, last = d.o_last_mass[gp];
   double r;
-  if (prm.mass_as_reward) {
+  if (mode != 0 && isnan(last)) {
+    r = 0;  // updateRewards adds getReward() only while there is a lastMass (bot.py:167), in either reward mode
+  } else if (prm.mass_as_reward) {
     r = alive ? mass - prm.reward_term : prm.death_term - prm.reward_term;
   } else if (isnan(last)) {
     r = __builtin_nan("");
@@ -1238,7 +1245,6 @@ __global__ void k_rewards(Dev d, double *out, aigar_reward_params prm, int updat
     double rw = alive ? mass - last : -1 * last * prm.death_factor + prm.death_term;
     r = rw * prm.reward_scale - prm.reward_term;
   }
-  if (mode != 0 && isnan(r)) r = 0;
   out[gp] = mode == 2 ? out[gp] + r : r;
   if (update_last && alive) d.o_last_mass[gp] = mass;
 }

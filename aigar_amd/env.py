@@ -15,7 +15,8 @@ actions apply to the NN players only, and only they are observed.
 Per decision (`step`): the NN actions go through set_command_point and are held
 for FRAME_SKIP_RATE + 1 ticks with split/eject dropped on the skipped ticks;
 the reward is the reference's cumulative reward over the window (getReward
-each tick against the lastMass of the previous decision); the observation is
+each tick against the lastMass the player had when it decided, bot.py:228-230;
+nothing for a player without one, bot.py:167); the observation is
 Bot.getStateRepresentation of every NN player (NaN rows for dead players, where
 the reference returns None).
 
@@ -459,19 +460,32 @@ class AgarVecEnv:
         gsplit = bool(getattr(self.parameters, "ENABLE_GREEDY_SPLIT", False)) if self.parameters is not None else False
         for k in range(self.skip + 1):
             if k > 0:  # updateRewards on the skipped frames (bot.py:166-168)
-                self.stepper.rewards(self.reward_params, update_last=False, out=self._r)
-                reward += torch.nan_to_num(self._r)
+                reward += self._reward_term(update_last=False)
             self.stepper.apply_actions(act, self.enable_split, skipping=k > 0, record=k == 0)
             if has_g:
                 self.stepper.policy_greedy(gsplit, greedy)
             if has_r:
                 self.stepper.policy_random_bots()
             self.stepper.step(1)
-        self.stepper.rewards(self.reward_params, update_last=True, out=self._r)
-        reward += torch.nan_to_num(self._r)
+        reward += self._reward_term(update_last=True)
         obs = self.observe()
         alive = ~torch.isnan(obs.view(self.NP, -1)[:, 0]) & self.nn
         return obs, reward, alive
+
+    def _reward_term(self, update_last):
+        """What updateRewards adds for every player (bot.py:167): getReward() while the bot
+        has a lastMass, else 0 -- also with MASS_AS_REWARD, where getReward itself ignores
+        lastMass; who has none shows as NaN in the mass-difference reward."""
+        torch = self.torch
+        prm = self.reward_params
+        known = None
+        if prm.mass_as_reward:
+            plain = _abi.RewardParams(0, 0, prm.reward_term, prm.death_term, prm.death_factor, prm.reward_scale)
+            self.stepper.rewards(plain, update_last=False, out=self._r)
+            known = ~torch.isnan(self._r)
+        self.stepper.rewards(prm, update_last=update_last, out=self._r)
+        r = torch.nan_to_num(self._r)
+        return r if known is None else torch.where(known, r, torch.zeros_like(r))
 
     def close(self):
         self.stepper.close()

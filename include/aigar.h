@@ -207,7 +207,8 @@ int aigar_set_split_likelihood(aigar_handle *h, int arena, const int32_t *lh);
 /* External (learner) actions for every player: act[A*B][n_act], n_act = 2, 3 or 4,
  * mapped through set_command_point (bot.py:550-577).  skipping: a frame-skip
  * frame, split/eject dropped (bot.py:266-267); record: a decision frame, the
- * observation's last / second-last action extras advance (bot.py:180-193). */
+ * observation's last / second-last action extras advance (bot.py:180-193) and
+ * the live NN players' lastMass becomes their total mass (bot.py:228-230). */
 int aigar_apply_actions(aigar_handle *h, const double *act, int n_act, int enable_split, int skipping, int record,
                         int on_device);
 
@@ -228,7 +229,9 @@ int aigar_rewards(aigar_handle *h, double *out, const aigar_reward_params *p, in
  * drives them: act[A*B][n_act] (n_act 2..4, DEVICE pointer) goes through
  * set_command_point (as aigar_apply_actions) and is held for skip + 1 ticks
  * (FRAME_SKIP_RATE; split/eject dropped on the skipped ticks), reward_out[A*B]
- * (DEVICE) gets the window's summed getReward (None counts 0; lastMass advances
+ * (DEVICE) gets the window's summed getReward (nothing is added for a player
+ * without a lastMass, bot.py:167, also when the mass is the reward; lastMass is
+ * set for the live NN players at the decision and advances for every live player
  * at the end), obs_out (DEVICE, as aigar_observe) every bot's observation.  The
  * whole decision is one hipGraph replay (re-captured when a pointer or a
  * parameter changes). */

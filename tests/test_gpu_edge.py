@@ -2,7 +2,7 @@
 where players split repeatedly against the walls, a cell at the mass
 cap (grow stops at 22500, parameters.py:30) and a heavy cell dropped on a virus
 (eatVirus + the 16 - n explosion, field.py:333-370).  Events exact, floats
-within 1e-5 (parity.FTOL)."""
+equal at tolerance parity.FTOL = 0."""
 import math
 
 import numpy as np

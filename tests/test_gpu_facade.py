@@ -63,8 +63,8 @@ def test_model_update_matches_oracle_and_getters():
             if not p.getIsAlive():
                 assert p.getCells() == []
                 continue
-            assert abs(p.getTotalMass() - s[1]) <= 1e-9
-            assert abs(p.getFovSize() - s[4]) <= 1e-9 * s[4]
+            assert p.getTotalMass() == s[1]
+            assert p.getFovSize() == s[4]
             own = [c for c in p.getCells()]
             assert len(own) == int(st["players_i"][p.index][4])
             fp, fs = p.getFovPos(), p.getFovSize()

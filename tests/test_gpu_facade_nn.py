@@ -45,8 +45,8 @@ def params():
         CNN_REPR=False, PELLET_GRID=True, SELF_GRID=True, WALL_GRID=True, ENEMY_GRID=True, VIRUS_GRID=True,
         SELF_GRID_LF=True, ENEMY_GRID_LF=True, EXTRA_INPUT=True, USE_FOVSIZE=True, USE_TOTALMASS=True,
         USE_LAST_ACTION=True, USE_SECOND_LAST_ACTION=True, USE_LAST_FOVSIZE=True, GRID_SQUARES_PER_FOV=11,
-        FRAME_SKIP_RATE=3, GATHER_EXP=True, MASS_AS_REWARD=False, REWARD_TERM=0.0, DEATH_TERM=-40.0,
-        DEATH_FACTOR=1.5, REWARD_SCALE=2.0, ALGORITHM="CACLA", RESET_LIMIT=20000)
+        FRAME_SKIP_RATE=3, GATHER_EXP=True, MASS_AS_REWARD=False, REWARD_TERM=0.3, DEATH_TERM=-40.5,
+        DEATH_FACTOR=1.7, REWARD_SCALE=0.3, ALGORITHM="CACLA", RESET_LIMIT=20000)
 
 
 def test_nn_bots_through_model_update_match_oracle():
@@ -81,7 +81,7 @@ def test_nn_bots_through_model_update_match_oracle():
             if b.lastMass is not None:
                 alive = stats0[i, 0] > 0
                 want = ((stats0[i, 1] - b.lastMass) if alive else (-1 * b.lastMass * p.DEATH_FACTOR + p.DEATH_TERM))
-                assert b.getReward() == pytest.approx(want * p.REWARD_SCALE - p.REWARD_TERM, abs=1e-9), (t, i)
+                assert b.getReward() == want * p.REWARD_SCALE - p.REWARD_TERM, (t, i)
         m.takeBotActions()
         o.policy_greedy(True)  # (the oracle's Greedy moves, for comparison; commands are replaced below)
         greedy_cmd = o.commands()

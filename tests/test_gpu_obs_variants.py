@@ -9,8 +9,7 @@
 The oracle's restatements reproduce the reference's own states bit-exactly
 (tests/test_oracle_golden.py: simple16, cnn42, cnn84, MT mode).  Here the device
 runs the same scenarios re-keyed to Philox and matches the oracle: events
-exact, every bot's state every tick within 1e-5 (fov sizes and view boxes
-exactly equal)."""
+exact, every bot's state every tick equal at tolerance parity.FTOL = 0."""
 import numpy as np
 import pytest
 
@@ -114,7 +113,7 @@ def test_default_grid_overflow_pool(converted):
     """k_observe at the default 11 squares with views of over a thousand pellets
     (the lists leave LDS for the overflow pool): whole-unit pellets take the
     order-free sums from the pool, a view holding a blob-made pellet the ranked
-    creation-order scan.  Pellet channel EXACT, the rest within 1e-5."""
+    creation-order scan.  The pellet channel and the rest of the row at tolerance 0."""
     ch = _abi.OBS_PELLET | _abi.OBS_SELF | _abi.OBS_ENEMY | _abi.OBS_WALL | _abi.OBS_SELF_LF | _abi.OBS_ENEMY_LF
     cfg = make_config(bots=16, field_size=400, max_pellets=4000.0, channels=ch, extras=_abi.EX_FOV | _abi.EX_MASS)
     g, o = _lib.Stepper(cfg), Oracle(cfg)
@@ -156,8 +155,8 @@ def test_pellet_sums_whole_units_and_converted():
     weighs whole units (spawns, 1-3) the sums are scattered into the squares in
     any order (exact: integer sums); a bot that sees a blob-made pellet (14.4)
     keeps the creation-order scan.  Both must give the reference's doubles
-    bit for bit, so the pellet channel is compared EXACTLY here (not within
-    1e-5): a world where the left half of the field holds converted pellets
+    bit for bit, so the pellet channel is compared with array_equal here, whatever
+    parity.FTOL is set to: a world where the left half of the field holds converted pellets
     among the spawned ones, many of them per square, observed as loaded and
     after a few ticks."""
     cfg = make_config(bots=24, field_size=400, max_pellets=4000.0, channels=_abi.OBS_PELLET | _abi.OBS_SELF,

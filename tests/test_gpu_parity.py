@@ -2,9 +2,10 @@
 
 Bar (north_star): events -- every eat / merge / split / explosion / death /
 respawn, with its indices (creation sequence numbers) and its ORDER -- are
-bit-exact; float state within 1e-5 (observed: <= 1e-11); fov sizes exactly
-equal (the device pow is glibc's, bit for bit, so the reference's cols==12
-quirk fires on the same bots); observations within 1e-5 for every bot.
+bit-exact.  Asserted here: float state and every bot's observation equal the
+oracle's at tolerance parity.FTOL = 0 (north_star would allow 1e-5), fov sizes
+included (the device pow is glibc's, bit for bit, so the reference's cols==12
+quirk fires on the same bots).
 """
 import math
 

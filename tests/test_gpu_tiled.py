@@ -8,7 +8,7 @@ all-gathered (in-process device copies here; RCCL in production).  The bar is
 the untiled one: the merged event log (every eat / merge / split / explosion /
 death / respawn, indices and order) equals the oracle's exactly, the merged
 state (replicated part from tile 0, pellets as the union of the owned sets)
-within 1e-5, observations within 1e-5 for every bot.  Small halos force the
+and every bot's observation equal it at tolerance parity.FTOL = 0.  Small halos force the
 cross-tile paths: cells whose reach leaves the held pellets (excluded), the
 taint of cells that share a food with them, and further exchange passes.
 """
@@ -175,7 +175,7 @@ def test_border_crowded_greedy_tiles(tx, ty, flags, seed):
     so contested border foods go through the taint / extra-pass exchange."""
     cfg = make_config(bots=64, virus=True, max_viruses=30, field_size=250,
                       channels=_abi.OBS_PELLET | _abi.OBS_WALL | _abi.OBS_ENEMY, extras=0x3)
-    st = run(cfg, tx, ty, 300, seed, greedy(True), check_every=10, ftol=1e-9, flags=flags)
+    st = run(cfg, tx, ty, 300, seed, greedy(True), check_every=10, ftol=parity.FTOL, flags=flags)
     assert {_abi.EV_CELL_EAT_CELL, _abi.EV_PLAYER_DEATH, _abi.EV_CELL_EAT_PELLET,
             _abi.EV_EXPLODE} <= st["kinds"], st["kinds"]
     if flags:
