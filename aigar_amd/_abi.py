@@ -44,6 +44,7 @@ class PixelParams(C.Structure):
 
 
 EXP_PRIORITIZED = 0x1  # aigar_exp_params.flags
+EXP_EXTRA = 0x2  # ... the tuple's fifth field (CACLA's raw action, SPG's best action)
 
 
 class ExpParams(C.Structure):
@@ -62,6 +63,19 @@ class DecideParams(C.Structure):
     """aigar_decide_params (include/aigar.h): the Q-learning bots' action selection (qLearning.py:208-243)."""
     _fields_ = [("n_out", C.c_int32), ("strategy", C.c_int32), ("q_dtype", C.c_int32), ("pad", C.c_int32),
                 ("seed", C.c_uint64)]
+
+
+NOISE_GAUSSIAN, NOISE_ORN_UHL = 0, 1  # aigar_noise_params.type (NOISE_TYPE)
+NOISE_TYPES = {"Gaussian": NOISE_GAUSSIAN, "Orn-Uhl": NOISE_ORN_UHL}
+NOISE_MAX_T = 16
+WARN_NOISE_NONFINITE = 0x10  # aigar_warnings: a deciding row's mu or the std was not finite (taken as 0)
+WARN_NOISE_EXHAUSTED = 0x20  # aigar_warnings: a pair's attempts were all rejected (the pair is (0.0, 0.0))
+
+
+class NoiseParams(C.Structure):
+    """aigar_noise_params (include/aigar.h): the actor-critic learners' exploration noise (actorCritic.py:922-936)."""
+    _fields_ = [("n_act", C.c_int32), ("type", C.c_int32), ("mu_dtype", C.c_int32), ("store_raw", C.c_int32),
+                ("theta", C.c_double), ("ou_mu", C.c_double), ("dt", C.c_double), ("seed", C.c_uint64)]
 
 
 class RunParams(C.Structure):

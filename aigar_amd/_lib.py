@@ -97,6 +97,11 @@ def load(build_if_missing=False):
         "aigar_decide_config": [vp, C.POINTER(_abi.DecideParams), vp],
         "aigar_decide": [vp, vp, vp, vp, vp, vp, vp],
         "aigar_env_step_q": [vp, vp, vp, vp, i32, i32, C.POINTER(_abi.RewardParams), vp, vp, i32, vp, vp],
+        "aigar_noise_config": [vp, C.POINTER(_abi.NoiseParams)],
+        "aigar_noise": [vp, vp, i32, vp, vp, i32, vp, vp, vp],
+        "aigar_env_step_ac": [vp, vp, vp, vp, i32, i32, i32, C.POINTER(_abi.RewardParams), vp, vp, i32, vp],
+        "aigar_exp_extra_get": [vp, vp, i32, vp, vp],
+        "aigar_exp_extra_set": [vp, vp, vp, i32],
         "aigar_warnings": [vp, i32, C.POINTER(C.c_uint32)],
         "aigar_set_actions": [vp, vp, vp, i32],
         "aigar_reset_bots": [vp, vp, i32],
@@ -112,6 +117,7 @@ def load(build_if_missing=False):
         "aigar_profile": [vp, i32],
         "aigar_kernel_time": [vp, C.c_char_p, dp, C.POINTER(i32)],
         "aigar_selftest_pow": [dp, dp, dp, i32],
+        "aigar_selftest_log": [dp, dp, i32],
         "aigar_selftest_trig": [dp, dp, dp, i32],
         "aigar_counters": [vp, i32, C.POINTER(C.c_int64), i32],
         "aigar_policy_greedy": [vp, i32, vp, i32],
@@ -182,6 +188,7 @@ class Stepper:
         self.pixel_state_shape = None  # (NP, side, side, C) while a pixel state is configured
         self.exp = None  # (state row shape, state dtype name, prioritized) while a replay memory is configured
         self.dec = None  # (n_out, q dtype name) while an action selection is configured
+        self.noi = None  # (n_act, mu dtype name, Orn-Uhl) while an exploration noise is configured
 
     def _chk(self, r):
         if r < 0:
@@ -392,11 +399,12 @@ class Stepper:
         return out
 
     # ---- replay memory (include/aigar.h: aigar_exp_*)
-    def exp_config(self, capacity, prioritized=False, alpha=0.6, beta=0.4, dtype="float64", seed=0):
+    def exp_config(self, capacity, prioritized=False, alpha=0.6, beta=0.4, dtype="float64", seed=0, extra=False):
         """The handle's replay memory (replay_buffer.py): a ring of capacity transitions whose
         states have the handle's current state shape (the pixel state when one is configured,
         else the observation row) in dtype; prioritized: with the sum / min trees.  While it
-        is set every env_step appends the NN players' transitions inside its graph.
+        is set every env_step appends the NN players' transitions inside its graph.  extra:
+        the ring also keeps the tuple's fifth field (exp_extra_get / exp_extra_set).
         exp_config(None) frees it."""
         if not capacity:
             self._chk(self.L.aigar_exp_config(self.h, None))
@@ -405,8 +413,9 @@ class Stepper:
         d = str(dtype).replace("torch.", "").replace("<class 'numpy.", "").replace("'>", "")
         if d not in ("float64", "float32"):
             raise ValueError("exp_config: dtype must be float64 or float32, got %s" % (dtype,))
-        prm = _abi.ExpParams(int(capacity), 0 if d == "float64" else 1, _abi.EXP_PRIORITIZED if prioritized else 0,
-                             float(alpha), float(beta), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        flags = (_abi.EXP_PRIORITIZED if prioritized else 0) | (_abi.EXP_EXTRA if extra else 0)
+        prm = _abi.ExpParams(int(capacity), 0 if d == "float64" else 1, flags, float(alpha), float(beta),
+                             int(seed) & 0xFFFFFFFFFFFFFFFF)
         self._chk(self.L.aigar_exp_config(self.h, C.byref(prm)))
         row = tuple(self.pixel_state_shape[1:]) if self.pixel_state_shape is not None else (self.obs_len,)
         self.exp = (row, d, bool(prioritized))
@@ -495,6 +504,114 @@ class Stepper:
         self._check_dev(idx, (n,), ("int64",), "exp_update_priorities")
         self._check_dev(prio, (n,), ("float64",), "exp_update_priorities")
         self._chk(self.L.aigar_exp_update_priorities(self.h, C.c_void_p(idx.data_ptr()), C.c_void_p(prio.data_ptr()), n))
+
+    def exp_extra_get(self, idx, out=None, valid=None):
+        """The fifth field of the slots idx [batch] (int64 device tensor) into the device tensors
+        out [batch, 4] float64 and valid [batch] uint8 / bool; rows whose index is outside
+        [0, size) are left as they are.  The memory needs extra=True."""
+        self._need_exp("exp_extra_get")
+        batch = int(idx.shape[0])
+        self._check_dev(idx, (batch,), ("int64",), "exp_extra_get")
+        op = vp = None
+        if out is not None:
+            self._check_dev(out, (batch, 4), ("float64",), "exp_extra_get")
+            op = C.c_void_p(out.data_ptr())
+        if valid is not None:
+            self._check_dev(valid, (batch,), ("uint8", "bool"), "exp_extra_get")
+            vp = C.c_void_p(valid.data_ptr())
+        self._chk(self.L.aigar_exp_extra_get(self.h, C.c_void_p(idx.data_ptr()), batch, op, vp))
+
+    def exp_extra_set(self, idx, rows):
+        """ReplayBuffer.update_dones on device tensors idx [n] int64, rows [n, 4] float64: slot
+        idx[j] gets rows[j] and becomes valid (the last of a repeated index wins; indices
+        outside [0, size) are skipped).  The memory needs extra=True."""
+        self._need_exp("exp_extra_set")
+        n = int(idx.shape[0])
+        self._check_dev(idx, (n,), ("int64",), "exp_extra_set")
+        self._check_dev(rows, (n, 4), ("float64",), "exp_extra_set")
+        self._chk(self.L.aigar_exp_extra_set(self.h, C.c_void_p(idx.data_ptr()), C.c_void_p(rows.data_ptr()), n))
+
+    # ---- exploration noise of the actor-critic learners (include/aigar.h: aigar_noise*)
+    def noise_config(self, n_act, kind="Gaussian", mu_dtype="float32", theta=0.15, ou_mu=0.0, dt=0.01, seed=0,
+                     store_raw=False):
+        """The handle's exploration noise (actorCritic.py:922-936): n_act values per action
+        (2..4), kind "Gaussian" or "Orn-Uhl" (or its code), mu_dtype the dtype of the actor's
+        rows, theta / ou_mu / dt the Orn-Uhl parameters, seed the salt of the own draws,
+        store_raw: the replay memory's extra field gets the raw action (CACLA).
+        noise_config(None) turns it off."""
+        if n_act is None:
+            self._chk(self.L.aigar_noise_config(self.h, None))
+            self.noi = None
+            return
+        d = str(mu_dtype).replace("torch.", "").replace("<class 'numpy.", "").replace("'>", "")
+        if d not in ("float64", "float32"):
+            raise ValueError("noise_config: mu_dtype must be float64 or float32, got %s" % (mu_dtype,))
+        k = _abi.NOISE_TYPES[kind] if isinstance(kind, str) else int(kind)
+        prm = _abi.NoiseParams(int(n_act), k, 0 if d == "float64" else 1, int(bool(store_raw)), float(theta),
+                               float(ou_mu), float(dt), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        self._chk(self.L.aigar_noise_config(self.h, C.byref(prm)))
+        self.noi = (int(n_act), d, k == _abi.NOISE_ORN_UHL)
+
+    def _noise_args(self, mu, rows, std, u, what):
+        if self.noi is None:
+            raise RuntimeError("aigar: %s: no exploration noise is configured (noise_config)" % what)
+        n, d, _ = self.noi
+        self._check_dev(mu, (rows, n), (d,), what)
+        self._check_dev(std, (1,), ("float64",), what)
+        up, T = None, 0
+        if u is not None:
+            if u.dim() != 4 or not 1 <= int(u.shape[2]) <= _abi.NOISE_MAX_T:
+                raise ValueError("%s: u must be [rows, 2, T, 2] with T in 1..%d" % (what, _abi.NOISE_MAX_T))
+            T = int(u.shape[2])
+            self._check_dev(u, (rows, 2, T, 2), ("float64",), what)
+            up = C.c_void_p(u.data_ptr())
+        return C.c_void_p(mu.data_ptr()), C.c_void_p(std.data_ptr()), up, T
+
+    def noise(self, mu, std, out, u=None, prev=None, n_exhausted=None):
+        """The perturbation alone on device tensors (aigar_noise): mu [rows, n_act], std [1]
+        float64, u [rows, 2, T, 2] float64 uniforms in [0, 1) (None: the own Philox stream),
+        prev [rows, n_act] float64 the caller's Orn-Uhl state (advanced in place), n_exhausted
+        [1] int64 counter of exhausted pairs; writes out [rows, n_act] float64.  Liveness and
+        roles are ignored."""
+        rows = int(mu.shape[0])
+        mp, sp, up, T = self._noise_args(mu, rows, std, u, "noise")
+        n = self.noi[0]
+        self._check_dev(out, (rows, n), ("float64",), "noise")
+        pp = ep = None
+        if prev is not None:
+            self._check_dev(prev, (rows, n), ("float64",), "noise")
+            pp = C.c_void_p(prev.data_ptr())
+        if n_exhausted is not None:
+            self._check_dev(n_exhausted, (1,), ("int64",), "noise")
+            ep = C.c_void_p(n_exhausted.data_ptr())
+        self._chk(self.L.aigar_noise(self.h, mp, rows, sp, up, T, pp, C.c_void_p(out.data_ptr()), ep))
+
+    def env_step_ac(self, mu, std, reward, obs, u=None, noisy=None, enable_split=True, skip=0, params=None):
+        """One actor-critic decision on device tensors (aigar_env_step_ac): the noise, then
+        env_step with the noisy rows; one graph replay.  noisy [NP, n_act] float64 gets the
+        noisy actions (NaN rows where nobody decided)."""
+        mp, sp, up, T = self._noise_args(mu, self.NP, std, u, "env_step_ac")
+        for t in (reward, obs):
+            if not getattr(t, "is_cuda", False) or not t.is_contiguous():
+                raise ValueError("env_step_ac takes contiguous device tensors")
+        self._check_dev(reward, (self.NP,), ("float64",), "env_step_ac")
+        if self.pixel_state_shape is not None:
+            self._check_out(obs, self.pixel_state_shape, ("float64", "float32"), "env_step_ac")
+        else:
+            self._check_out(obs, (self.NP, self.obs_len), ("float64", "float32"), "env_step_ac")
+        np_ = None
+        if noisy is not None:
+            self._check_dev(noisy, (self.NP, self.noi[0]), ("float64",), "env_step_ac")
+            np_ = C.c_void_p(noisy.data_ptr())
+        prm = params if isinstance(params, _abi.RewardParams) else _abi.RewardParams.from_parameters(params)
+        dt = 0 if str(obs.dtype) == "torch.float64" else 1
+        self._chk(self.L.aigar_env_step_ac(self.h, mp, sp, up, T, int(bool(enable_split)), int(skip), C.byref(prm),
+                                           C.c_void_p(reward.data_ptr()), C.c_void_p(obs.data_ptr()), dt, np_))
+
+    @staticmethod
+    def selftest_log(x):
+        """Device log (glibc's, restated in aigar_math.h) for a host array."""
+        return selftest_log(x)
 
     # ---- action selection of the Q-learning bots (include/aigar.h: aigar_decide*)
     def decide_config(self, actions, strategy="e-Greedy", q_dtype="float32", seed=0):
@@ -791,5 +908,16 @@ def selftest_pow(x, y):
     out = np.zeros_like(x)
     dp = C.POINTER(C.c_double)
     if L.aigar_selftest_pow(x.ctypes.data_as(dp), y.ctypes.data_as(dp), out.ctypes.data_as(dp), len(x)) < 0:
+        raise RuntimeError("aigar: " + L.aigar_last_error().decode())
+    return out
+
+
+def selftest_log(x):
+    """Device log (glibc's, restated in aigar_math.h) for a host array (diagnostics)."""
+    L = load()
+    x = np.ascontiguousarray(x, np.float64)
+    out = np.zeros_like(x)
+    dp = C.POINTER(C.c_double)
+    if L.aigar_selftest_log(x.ctypes.data_as(dp), out.ctypes.data_as(dp), len(x)) < 0:
         raise RuntimeError("aigar: " + L.aigar_last_error().decode())
     return out

@@ -1,5 +1,5 @@
-// aigar_math.h -- pow(x, y) exactly as the reference's glibc computes it, and
-// an exact non-negative fmod, for the stepper (host + device).
+// aigar_math.h -- pow(x, y) and log(x) exactly as the reference's glibc computes
+// them, and an exact non-negative fmod, for the stepper (host + device).
 //
 // Why: the reference's observation grid has a quirk (spatialHashTable.py:19 vs
 // bot.py:389): cols = ceil(fov / (fov / 11)) is 12 instead of 11 for ~3% of
@@ -25,6 +25,7 @@
 #define AIGAR_HD static inline
 #endif
 #include "aigar_glibc_pow_tables.h"
+#include "aigar_glibc_log_tables.h"
 
 namespace aigar_math {
 
@@ -257,6 +258,77 @@ AIGAR_HD double pow_glibc(double x, double y) {
   const double ehi = y * hi;
   const double elo = fma(y, lo, fma(y, hi, -ehi));
   return glibc_exp_inline(ehi, elo);
+}
+
+// ------------------------------------------------------------ glibc log
+// log(x) bit-identical to glibc 2.35 (sysdeps/ieee754/dbl-64/e_log.c) for every positive
+// finite x: numpy's legacy Gaussian calls it (sqrt(-2 * log(r2) / r2), noise.inc).  The
+// same table (aigar_glibc_log_tables.h, dumped from the host's libm by
+// tools/gen/glibc_log_tables.c), the same operation sequence, and a fused multiply-add
+// exactly where the x86-64 FMA variant has one (__ieee754_log_fma, read off its object
+// code with objdump -d; the plain products and sums below are vmulsd / vaddsd / vsubsd
+// there).  Outside the domain: log(0) = -inf, x < 0 and NaN give NaN, log(inf) = inf.
+// tools/gen/check_log.cpp checks the host build against libm's log on > 10^7 inputs
+// (tests/test_log_host.py); tests/test_gpu_noise.py the device.
+#ifdef __HIPCC__
+static __constant__ uint64_t kGlibcLogDev[530] = AIGAR_GLIBC_LOG_DATA;
+#endif
+static const uint64_t kGlibcLogHost[530] = AIGAR_GLIBC_LOG_DATA;
+// __log_data: [0] ln2hi [1] ln2lo [2..6] poly A[0..4] [7..17] poly1 B[0..10] [18 + 2i] {invc, logc}
+AIGAR_HD double glogd(int i) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return as_double(kGlibcLogDev[i]);
+#else
+  return as_double(kGlibcLogHost[i]);
+#endif
+}
+
+AIGAR_HD double log_glibc(double x) {
+  uint64_t ix = as_u64(x);
+  const uint64_t LO = 0x3fee000000000000ull, HI = 0x3ff1090000000000ull;  // 1 - 0x1p-4, 1 + 0x1.09p-4
+  if (ix - LO < HI - LO) {  // near 1: a polynomial in r = x - 1, r - r^2 / 2 as hi + lo
+    if (ix == 0x3ff0000000000000ull) return 0.0;
+    const double r = x - 1.0;
+    const double r2 = r * r;
+    const double r3 = r * r2;
+    const double B0 = glogd(7);  // -0.5
+    const double p1 = fma(r2, glogd(10), fma(r, glogd(9), glogd(8)));     // B1 + r B2 + r2 B3
+    const double p4 = fma(r2, glogd(13), fma(r, glogd(12), glogd(11)));   // B4 + r B5 + r2 B6
+    double p7 = fma(r2, glogd(16), fma(r, glogd(15), glogd(14)));         // B7 + r B8 + r2 B9
+    p7 = fma(r3, glogd(17), p7);                                          // ... + r3 B10
+    const double p = fma(fma(p7, r3, p4), r3, p1);
+    const double t = fma(r, 0x1p27, r);        // r + w, w = r * 2^27
+    const double rhi = fma(-0x1p27, r, t);     // ... - w
+    const double rlo = r - rhi;
+    const double rr = rhi * rhi;
+    const double hi = fma(rr, B0, r);
+    double lo = fma(rr, B0, r - hi);
+    lo = fma(B0 * rlo, rhi + r, lo);
+    return hi + fma(p, r3, lo);
+  }
+  const uint32_t top = (uint32_t)(ix >> 48);
+  if (top - 0x0010u >= 0x7ff0u - 0x0010u) {  // x < 2^-1022, an infinity or a NaN
+    if (ix * 2 == 0) return -__builtin_inf();
+    if (ix == 0x7ff0000000000000ull) return x;
+    if ((top & 0x8000u) || (top & 0x7ff0u) == 0x7ff0u) return __builtin_nan("");
+    ix = as_u64(x * 0x1p52) - (52ull << 52);  // subnormal
+  }
+  // x = 2^k z, z in [OFF, 2 OFF); c near the centre of z's subinterval: log1p(z / c - 1) + log(c) + k ln2
+  const uint64_t OFF = 0x3fe6000000000000ull;
+  const uint64_t tmp = ix - OFF;
+  const int i = (int)((tmp >> 45) & 127);
+  const int k = (int)((int64_t)tmp >> 52);
+  const double z = as_double(ix - (tmp & (0xfffull << 52)));
+  const double invc = glogd(18 + 2 * i), logc = glogd(19 + 2 * i);
+  const double kd = (double)k;
+  const double r = fma(z, invc, -1.0);
+  const double w = fma(kd, glogd(0), logc);
+  const double hi = w + r;
+  const double lo = fma(kd, glogd(1), w - hi + r);
+  const double r2 = r * r;
+  const double r3 = r * r2;
+  const double q = fma(fma(r, glogd(6), glogd(5)), r2, fma(r, glogd(4), glogd(3)));  // A1 + r A2 + r2 (A3 + r A4)
+  return fma(r3, q, fma(r2, glogd(2), lo)) + hi;
 }
 
 }  // namespace aigar_math

@@ -53,6 +53,7 @@ using namespace aigar;
 
 #include "replay.inc"
 #include "decide.inc"
+#include "noise.inc"
 
 static thread_local std::string g_err;
 static int fail(const char *fmt, ...) {
@@ -215,10 +216,20 @@ struct aigar_handle {
     int32_t *idx_out;
     double *val_out;
     Decide dec;
+    // aigar_env_step_ac: the exploration noise in front of the decision (mu null: none)
+    const void *mu;
+    const double *nstd, *nu;
+    double *noisy;
+    const double *exp_extra;  // the transitions' fifth field, [NP][exp_n_act] (null: invalid)
+    int nT, pad;
+    Noise noi;
   } env_key{};
   // aigar_decide_config: the Q-learning bots' action selection (decide.inc; n_out 0: off)
   Decide dec{};
   std::vector<void *> dec_allocs;
+  // aigar_noise_config: the actor-critic learners' exploration noise (noise.inc; n_act 0: off)
+  Noise noi{};
+  std::vector<void *> noi_allocs;
   // aigar_exp_config: the learners' replay memory (replay.inc; cap 0: off)
   Exp exp;
   std::vector<void *> exp_allocs;
@@ -287,6 +298,9 @@ static void free_all(aigar_handle *h) {
   for (void *p : h->dec_allocs) (void)hipFree(p);
   h->dec_allocs.clear();
   h->dec = Decide{};
+  for (void *p : h->noi_allocs) (void)hipFree(p);
+  h->noi_allocs.clear();
+  h->noi = Noise{};
   if (h->d_exp_off) (void)hipFree(h->d_exp_off);
   h->d_exp_off = nullptr;
   h->exp = Exp{};
@@ -656,6 +670,7 @@ extern "C" int aigar_reset(aigar_handle *h, uint64_t seed) {
     HIPCHK(hipMemsetAsync(p, 0, sizeof(double) * NP * GG, h->stream));
   if (h->d_pix_hist) HIPCHK(hipMemsetAsync(h->d_pix_hist, 0, pix_hist_bytes(h), h->stream));
   if (h->exp.cap) HIPCHK(hipMemsetAsync(h->exp.has_old, 0, NP, h->stream));  // Bot.reset: oldState = None
+  if (h->noi.n_act) HIPCHK(hipMemsetAsync(h->noi.ou, 0, sizeof(double) * NP * h->noi.n_act, h->stream));
   if (d.tiled) {  // every tile's history copy is current (all zero)
     HIPCHK(hipMemsetAsync(d.t_holder, 0xFF, sizeof(int) * NP, h->stream));
     HIPCHK(hipMemsetAsync(d.t_obsby, 0xFF, sizeof(int) * NP, h->stream));
@@ -702,6 +717,8 @@ extern "C" int aigar_reset_arenas(aigar_handle *h, const int32_t *arenas, const 
     }
     if (h->exp.cap)
       hipLaunchKernelGGL(k_exp_clear_arenas, dim3(n), dim3(256), 0, h->stream, h->exp.has_old, d.B, h->d_rlist);
+    if (h->noi.n_act)
+      hipLaunchKernelGGL(k_noise_clear_arenas, dim3(n), dim3(256), 0, h->stream, h->noi.ou, d.B * h->noi.n_act, h->d_rlist);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -1262,17 +1279,17 @@ extern "C" int aigar_tile_observers(aigar_handle *h, int32_t *out) {
 // (old state, action, window reward, new row, dead) into the ring in ascending player
 // order, then the new rows are latched -- two launches at the end of the graph.
 static void launch_exp_append(aigar_handle *h, hipStream_t s, const double *act, int n_act, const double *reward,
-                              const void *obs) {
+                              const void *obs, const double *extra) {
   const Exp &e = h->exp;
   const int NP = h->d.NP;
   hipLaunchKernelGGL(k_exp_plan, dim3(1), dim3(kExpPlanThreads), 0, s, e, 0, h->d.p_role, (const uint8_t *)nullptr, NP,
                      e.off);
   if (e.dtype == 0)
     hipLaunchKernelGGL(k_exp_rows<uint64_t>, dim3(NP), dim3(256), 0, s, e, e.off, e.old, e.stride, (const char *)obs, act,
-                       n_act, reward, (const uint8_t *)nullptr, h->d.p_role, 1);
+                       n_act, reward, (const uint8_t *)nullptr, h->d.p_role, 1, extra);
   else
     hipLaunchKernelGGL(k_exp_rows<uint32_t>, dim3(NP), dim3(256), 0, s, e, e.off, e.old, e.stride, (const char *)obs, act,
-                       n_act, reward, (const uint8_t *)nullptr, h->d.p_role, 1);
+                       n_act, reward, (const uint8_t *)nullptr, h->d.p_role, 1, extra);
 }
 static void launch_exp_latch(aigar_handle *h, hipStream_t s, const void *obs, int dtype, const uint8_t *mask) {
   hipLaunchKernelGGL(k_exp_latch, dim3(h->d.NP), dim3(256), 0, s, h->exp, obs, dtype, mask);
@@ -1293,11 +1310,12 @@ static void launch_env_decision(aigar_handle *h, hipStream_t s, const aigar_hand
     (void)launch_observe_pixel_state(h->d, s, k.obs, k.dtype, k.pix.side, k.pix.flags, k.pix.color_seed, h->d_pix_ovf,
                                      nn, k.pix_hist);
   else launch_observe(h->d, s, k.obs, k.dtype, 0, nn);
-  if (k.exp) launch_exp_append(h, s, k.exp_act, k.exp_n_act, k.reward, k.obs);
+  if (k.exp) launch_exp_append(h, s, k.exp_act, k.exp_n_act, k.reward, k.obs, k.exp_extra);
 }
 
-// The decision of aigar_env_step / aigar_env_step_q: the key's common part, then the
-// replay of its graph (k.q: the selection's kernel in front, decide.inc).
+// The decision of aigar_env_step / aigar_env_step_q / aigar_env_step_ac: the key's common
+// part, then the replay of its graph (k.q: the selection's kernel in front, decide.inc;
+// k.mu: the noise's, noise.inc).
 static int env_step_keyed(aigar_handle *h, aigar_handle::EnvKey &k, int enable_split, int skip,
                           const aigar_reward_params *p, double *reward_out, void *obs_out, int dtype) {
   if (skip < 0) return fail("env_step: skip < 0");
@@ -1315,7 +1333,7 @@ static int env_step_keyed(aigar_handle *h, aigar_handle::EnvKey &k, int enable_s
   k.pix = h->pix;
   k.pix_hist = h->d_pix_hist;
   k.exp = h->exp.cap ? h->exp.ctl : nullptr;
-  if (!k.q) {  // (the selection stores the index, [NP][1])
+  if (!k.q && !k.mu) {  // (the selection stores the index, [NP][1]; the noise its noisy rows)
     k.exp_act = k.act;
     k.exp_n_act = k.n_act;
   }
@@ -1327,6 +1345,8 @@ static int env_step_keyed(aigar_handle *h, aigar_handle::EnvKey &k, int enable_s
     hipLaunchKernelGGL(k_step_begin, dim3((h->d.A + 63) / 64), dim3(64), 0, h->stream, h->d);
   auto launch = [&](hipStream_t cs) {
     if (k.q) launch_decide(h->d, cs, k.dec, k.q, k.explore, k.u, k.idx_out, k.val_out, k.dec.act);
+    if (k.mu)
+      launch_noise(h->d, cs, k.noi, k.mu, h->d.NP, 1, k.nstd, k.nu, k.nT, nullptr, k.noisy, nullptr);
     launch_env_decision(h, cs, k);
   };
   if (!h->use_graph) {
@@ -1436,6 +1456,101 @@ extern "C" int aigar_env_step_q(aigar_handle *h, const void *q, const double *ex
   k.dec = h->dec;
   k.exp_act = h->dec.idx;
   k.exp_n_act = 1;
+  return env_step_keyed(h, k, enable_split, skip, p, reward_out, obs_out, dtype);
+}
+
+// ------------------------------------------------------------ exploration noise
+static void noi_free(aigar_handle *h) {
+  for (void *p : h->noi_allocs) (void)hipFree(p);
+  h->noi_allocs.clear();
+  h->noi = Noise{};
+}
+static int need_noi(aigar_handle *h, const char *who) {
+  if (!h) return fail("null handle");
+  if (!h->noi.n_act) return fail("%s: no exploration noise is configured (aigar_noise_config)", who);
+  return 0;
+}
+
+extern "C" int aigar_noise_config(aigar_handle *h, const aigar_noise_params *p) {
+  if (!h) return fail("null handle");
+  if (p) {
+    if (h->d.tiled) return fail("noise_config: a tiled handle has no exploration noise");
+    if (p->n_act < 2 || p->n_act > 4) return fail("noise_config: n_act = %d is outside 2..4", p->n_act);
+    if (p->type != AIGAR_NOISE_GAUSSIAN && p->type != AIGAR_NOISE_ORN_UHL)
+      return fail("noise_config: type must be 0 (Gaussian) or 1 (Orn-Uhl)");
+    if (p->mu_dtype != 0 && p->mu_dtype != 1) return fail("noise_config: mu_dtype must be 0 (float64) or 1 (float32)");
+    if (p->type == AIGAR_NOISE_ORN_UHL &&
+        !(std::isfinite(p->theta) && std::isfinite(p->ou_mu) && p->dt >= 0 && std::isfinite(p->dt)))
+      return fail("noise_config: Orn-Uhl needs finite theta and ou_mu and a finite dt >= 0 (got %g, %g, %g)", p->theta,
+                  p->ou_mu, p->dt);
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));  // (no replay of the graph is pending)
+  if (h->env_graph) (void)hipGraphExecDestroy(h->env_graph);
+  h->env_graph = nullptr;
+  noi_free(h);
+  if (!p) return 0;
+  Noise c{};
+  c.n_act = p->n_act;
+  c.type = p->type;
+  c.mu_dtype = p->mu_dtype;
+  c.store_raw = p->store_raw ? 1 : 0;
+  c.theta = p->theta;
+  c.ou_mu = p->ou_mu;
+  c.dt = p->type == AIGAR_NOISE_ORN_UHL ? p->dt : 0.0;
+  c.seed = p->seed;
+  const size_t bytes = (size_t)h->d.NP * 4 * sizeof(double);
+  void *m[3] = {nullptr, nullptr, nullptr};
+  for (int i = 0; i < 3; i++) {
+    if (hipMalloc(&m[i], bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      noi_free(h);
+      return fail("noise_config: out of device memory");
+    }
+    h->noi_allocs.push_back(m[i]);
+    HIPCHK(hipMemsetAsync(m[i], 0, bytes, h->stream));
+  }
+  c.act = (double *)m[0];
+  c.raw = (double *)m[1];
+  c.ou = (double *)m[2];
+  h->noi = c;
+  return 0;
+}
+
+extern "C" int aigar_noise(aigar_handle *h, const void *mu, int rows, const double *std, const double *u, int T,
+                           double *prev, double *noisy_out, uint64_t *n_exhausted) {
+  if (need_noi(h, "noise")) return -1;
+  if (rows < 0) return fail("noise: rows = %d is negative", rows);
+  if (rows > (1 << 30)) return fail("noise: rows = %d above 2^30", rows);
+  if (rows == 0) return 0;
+  if (!mu || !std || !noisy_out) return fail("noise: null argument");
+  if (u && (T < 1 || T > kNoiseMaxT)) return fail("noise: T = %d is outside 1..%d", T, kNoiseMaxT);
+  if (h->noi.type == AIGAR_NOISE_ORN_UHL && !prev) return fail("noise: an Orn-Uhl config needs the caller's state (prev)");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  launch_noise(h->d, h->stream, h->noi, mu, rows, 0, std, u, u ? T : kNoiseOwnT, prev, noisy_out,
+               (unsigned long long *)n_exhausted);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int aigar_env_step_ac(aigar_handle *h, const void *mu, const double *std, const double *u, int T,
+                                 int enable_split, int skip, const aigar_reward_params *p, double *reward_out,
+                                 void *obs_out, int dtype, double *noisy_out) {
+  if (need_noi(h, "env_step_ac")) return -1;
+  if (!mu || !std || !p || !reward_out || !obs_out) return fail("env_step_ac: null argument");
+  if (u && (T < 1 || T > kNoiseMaxT)) return fail("env_step_ac: T = %d is outside 1..%d", T, kNoiseMaxT);
+  aigar_handle::EnvKey k{};
+  k.act = h->noi.act;
+  k.n_act = h->noi.n_act;
+  k.mu = mu;
+  k.nstd = std;
+  k.nu = u;
+  k.nT = u ? T : kNoiseOwnT;
+  k.noisy = noisy_out;
+  k.noi = h->noi;
+  k.exp_act = h->noi.act;
+  k.exp_n_act = h->noi.n_act;
+  k.exp_extra = h->noi.store_raw ? h->noi.raw : nullptr;
   return env_step_keyed(h, k, enable_split, skip, p, reward_out, obs_out, dtype);
 }
 
@@ -1625,7 +1740,7 @@ extern "C" int aigar_exp_config(aigar_handle *h, const aigar_exp_params *p) {
                   (long long)p->capacity, h->d.NP);
     if (p->capacity > ((int64_t)1 << 30)) return fail("exp_config: capacity %lld above 2^30", (long long)p->capacity);
     if (p->state_dtype != 0 && p->state_dtype != 1) return fail("exp_config: state_dtype must be 0 (float64) or 1 (float32)");
-    if (p->flags & ~AIGAR_EXP_PRIORITIZED) return fail("exp_config: unknown flags 0x%x", p->flags);
+    if (p->flags & ~(AIGAR_EXP_PRIORITIZED | AIGAR_EXP_EXTRA)) return fail("exp_config: unknown flags 0x%x", p->flags);
     if ((p->flags & AIGAR_EXP_PRIORITIZED) && (!(p->alpha >= 0) || !(p->beta > 0)))
       return fail("exp_config: need alpha >= 0 and beta > 0 (got %g, %g)", p->alpha, p->beta);
   }
@@ -1670,7 +1785,12 @@ extern "C" int aigar_exp_config(aigar_handle *h, const aigar_exp_params *p) {
   if (e.prio) {
     e.vsum = (double *)get(2 * (size_t)e.it_cap * sizeof(double));
     e.vmin = (double *)get(2 * (size_t)e.it_cap * sizeof(double));
-    e.last = (int *)get(cap * sizeof(int));
+  }
+  const bool extra = (p->flags & AIGAR_EXP_EXTRA) != 0;
+  if (e.prio || extra) e.last = (int *)get(cap * sizeof(int));
+  if (extra) {
+    e.x = (double *)get(cap * 4 * sizeof(double));
+    e.xv = (uint8_t *)get(cap);
   }
   e.ctl = (ExpCtl *)get(sizeof(ExpCtl));
   e.old = (char *)get(NP * e.stride);
@@ -1689,8 +1809,13 @@ extern "C" int aigar_exp_config(aigar_handle *h, const aigar_exp_params *p) {
   HIPCHK(hipMemsetAsync(e.done, 0, cap, h->stream));
   HIPCHK(hipMemsetAsync(e.old, 0, NP * e.stride, h->stream));
   HIPCHK(hipMemsetAsync(e.has_old, 0, NP, h->stream));
-  if (e.prio)
+  if (e.last)
     hipLaunchKernelGGL(k_exp_fill_i, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, h->stream, e.last, cap, -1);
+  if (e.x) {  // no slot has a fifth field: NaN, invalid
+    hipLaunchKernelGGL(k_fill_d, dim3((unsigned)((cap * 4 + 255) / 256)), dim3(256), 0, h->stream, e.x, cap * 4,
+                       __builtin_nan(""));
+    HIPCHK(hipMemsetAsync(e.xv, 0, cap, h->stream));
+  }
   const size_t ni = e.prio ? 2 * (size_t)e.it_cap : 1;
   hipLaunchKernelGGL(k_exp_init, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, h->stream, e);
   HIPCHK(hipGetLastError());
@@ -1764,10 +1889,10 @@ extern "C" int aigar_exp_add(aigar_handle *h, const void *s, const double *a, co
                      h->d_exp_off);
   if (e.dtype == 0)
     hipLaunchKernelGGL(k_exp_rows<uint64_t>, dim3(n), dim3(256), 0, h->stream, e, h->d_exp_off, (const char *)s, row,
-                       (const char *)s2, a, 4, r, done, (const uint8_t *)nullptr, 0);
+                       (const char *)s2, a, 4, r, done, (const uint8_t *)nullptr, 0, (const double *)nullptr);
   else
     hipLaunchKernelGGL(k_exp_rows<uint32_t>, dim3(n), dim3(256), 0, h->stream, e, h->d_exp_off, (const char *)s, row,
-                       (const char *)s2, a, 4, r, done, (const uint8_t *)nullptr, 0);
+                       (const char *)s2, a, 4, r, done, (const uint8_t *)nullptr, 0, (const double *)nullptr);
   hipError_t er = hipGetLastError();
   if (stage) {
     (void)hipStreamSynchronize(h->stream);
@@ -1819,6 +1944,31 @@ extern "C" int aigar_exp_update_priorities(aigar_handle *h, const int64_t *idx, 
   if (!idx || !prio) return fail("exp_update_priorities: null argument");
   HIPCHK(hipSetDevice(h->cfg.device));
   hipLaunchKernelGGL(k_exp_update, dim3(1), dim3(kExpPlanThreads), 0, h->stream, h->exp, idx, prio, n);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int aigar_exp_extra_get(aigar_handle *h, const int64_t *idx, int batch, double *out, uint8_t *valid) {
+  if (need_exp(h, "exp_extra_get")) return -1;
+  if (!h->exp.x) return fail("exp_extra_get: the replay memory has no extra field (AIGAR_EXP_EXTRA)");
+  if (batch < 0) return fail("exp_extra_get: batch = %d", batch);
+  if (batch == 0) return 0;
+  if (!idx) return fail("exp_extra_get: null idx");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  hipLaunchKernelGGL(k_exp_extra_get, dim3((unsigned)(((size_t)batch * 4 + 255) / 256)), dim3(256), 0, h->stream, h->exp,
+                     idx, batch, out, valid);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int aigar_exp_extra_set(aigar_handle *h, const int64_t *idx, const double *rows, int n) {
+  if (need_exp(h, "exp_extra_set")) return -1;
+  if (!h->exp.x) return fail("exp_extra_set: the replay memory has no extra field (AIGAR_EXP_EXTRA)");
+  if (n < 0) return fail("exp_extra_set: n = %d is negative", n);
+  if (n == 0) return 0;
+  if (!idx || !rows) return fail("exp_extra_set: null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  hipLaunchKernelGGL(k_exp_extra_set, dim3(1), dim3(kExpPlanThreads), 0, h->stream, h->exp, idx, rows, n);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1925,6 +2075,9 @@ extern "C" int aigar_reset_bots(aigar_handle *h, const uint8_t *mask, int on_dev
   }
   if (h->exp.cap)  // Bot.reset: oldState = None (bot.py:186)
     hipLaunchKernelGGL(k_exp_clear_bots, dim3((h->d.NP + 255) / 256), dim3(256), 0, h->stream, h->exp.has_old, h->d.NP, m);
+  if (h->noi.n_act)  // the Orn-Uhl state restarts with the bot (actorCritic.py:1121-1123)
+    hipLaunchKernelGGL(k_noise_clear_bots, dim3((h->d.NP + 255) / 256), dim3(256), 0, h->stream, h->noi.ou, h->d.NP,
+                       h->noi.n_act, m);
   HIPCHK(hipGetLastError());
   if (mask && !on_device) HIPCHK(hipStreamSynchronize(h->stream));  // caller may reuse its buffer
   return 0;
@@ -2405,6 +2558,8 @@ extern "C" int aigar_load_state(aigar_handle *h, int arena, const aigar_state *s
     HIPCHK(hipMemsetAsync(h->d_pix_hist + p0 * LL, 0, sizeof(uint32_t) * B * LL, h->stream));
   }
   if (h->exp.cap) HIPCHK(hipMemsetAsync(h->exp.has_old + p0, 0, B, h->stream));
+  if (h->noi.n_act)
+    HIPCHK(hipMemsetAsync(h->noi.ou + p0 * h->noi.n_act, 0, sizeof(double) * B * h->noi.n_act, h->stream));
   if (d.tiled) {
     HIPCHK(hipMemsetAsync(d.t_holder, 0xFF, sizeof(int) * d.NP, h->stream));
     HIPCHK(hipMemsetAsync(d.t_obsby, 0xFF, sizeof(int) * d.NP, h->stream));
@@ -2555,6 +2710,26 @@ extern "C" int aigar_selftest_pow(const double *x, const double *y, double *out,
   HIPCHK(hipMemcpy(out, dz, sizeof(double) * n, hipMemcpyDeviceToHost));
   (void)hipFree(dx);
   (void)hipFree(dy);
+  (void)hipFree(dz);
+  return 0;
+}
+
+__global__ void k_selftest_log(const double *x, double *out, int n) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = aigar_math::log_glibc(x[i]);
+}
+
+extern "C" int aigar_selftest_log(const double *x, double *out, int n) {
+  if (!x || !out || n < 0) return fail("null argument");
+  double *dx = nullptr, *dz = nullptr;
+  size_t b = sizeof(double) * (size_t)(n > 0 ? n : 1);
+  HIPCHK(hipMalloc(&dx, b));
+  HIPCHK(hipMalloc(&dz, b));
+  HIPCHK(hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_selftest_log, dim3((n + 255) / 256), dim3(256), 0, 0, dx, dz, n);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(out, dz, sizeof(double) * n, hipMemcpyDeviceToHost));
+  (void)hipFree(dx);
   (void)hipFree(dz);
   return 0;
 }

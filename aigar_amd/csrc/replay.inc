@@ -19,6 +19,7 @@
 //   k_exp_draw    one thread per draw: u -> index and importance weight
 //   k_exp_fetch   one workgroup per sampled row: the rows out
 //   k_exp_update  one workgroup: priorities -> leaves (last occurrence wins), ancestors
+//   k_exp_extra_get / k_exp_extra_set  the fifth field of given slots out / in (last occurrence wins)
 
 struct ExpCtl {  // device-resident state of the ring
   int64_t size, next, added, calls;
@@ -38,7 +39,9 @@ struct Exp {
   double *a = nullptr, *r = nullptr;  // [cap][4], [cap]
   uint8_t *done = nullptr;            // [cap]
   double *vsum = nullptr, *vmin = nullptr;  // [2 * it_cap]
-  int *last = nullptr;                // [cap] scratch of k_exp_update, -1 between calls
+  int *last = nullptr;                // [cap] scratch of k_exp_update / k_exp_extra_set, -1 between calls
+  double *x = nullptr;                // [cap][4] the tuple's fifth field (AIGAR_EXP_EXTRA; null: none)
+  uint8_t *xv = nullptr;              // [cap] ... and whether the slot has one (0: the reference's None, x is NaN)
   ExpCtl *ctl = nullptr;
   char *old = nullptr;        // [NP][stride] every player's old state (Bot.oldState)
   uint8_t *has_old = nullptr;  // [NP]
@@ -147,11 +150,12 @@ __device__ __forceinline__ void exp_copy_row(void *dst, const void *src, int L) 
 // afterwards the new row becomes the old state of every NN player (none if dead).
 // latch = 0 (aigar_exp_add): caller rows [n][L], caller done.  States move as their
 // bit patterns (NaN payloads included), in units of the element: the caller's rows
-// are aligned to no more than that.
+// are aligned to no more than that.  xtra: [n][n_act] the slot's fifth field (null: none,
+// the slot's extra is NaN and invalid); only a memory with the extra field keeps it.
 template <class W>
 __global__ void __launch_bounds__(256) k_exp_rows(Exp e, const int *off, const char *s, size_t s_stride, const char *s2,
                                                   const double *act, int n_act, const double *rew, const uint8_t *done,
-                                                  const uint8_t *role, int latch) {
+                                                  const uint8_t *role, int latch, const double *xtra) {
   const int i = blockIdx.x;
   const ExpCtl *ctl = e.ctl;
   const int o = off[i];
@@ -164,6 +168,11 @@ __global__ void __launch_bounds__(256) k_exp_rows(Exp e, const int *off, const c
     if (threadIdx.x < 4) e.a[slot * 4 + threadIdx.x] = (int)threadIdx.x < n_act ? act[(size_t)i * n_act + threadIdx.x] : 0.0;
     if (threadIdx.x == 4) e.r[slot] = rew[i];
     if (threadIdx.x == 5) e.done[slot] = latch ? (dead ? 1 : 0) : (done[i] ? 1 : 0);
+    if (e.x) {
+      const int t = (int)threadIdx.x - 8;
+      if (t >= 0 && t < 4) e.x[slot * 4 + t] = xtra ? (t < n_act ? xtra[(size_t)i * n_act + t] : 0.0) : __builtin_nan("");
+      if (t == 4) e.xv[slot] = xtra ? 1 : 0;
+    }
   }
   if (!latch || role[i] != AIGAR_ROLE_NN) return;
   // (each thread reads old[j] above before it writes old[j] here: same thread, same j)
@@ -357,6 +366,42 @@ __global__ void __launch_bounds__(kExpPlanThreads) k_exp_update(Exp e, const int
       const double m0 = e.vmin[2 * k], m1 = e.vmin[2 * k + 1];
       e.vmin[k] = (m1 < m0) ? m1 : m0;
     }
+  }
+  __syncthreads();
+  for (int j = t; j < n; j += kExpPlanThreads) {  // the scratch is -1 again for the next call
+    const int64_t i = idx[j];
+    if (i >= 0 && i < size) e.last[i] = -1;
+  }
+}
+
+// The fifth field of the slots idx[k] into row k of out / valid (each may be null); an
+// index outside [0, size) leaves row k as it is.  One thread per (k, value).
+__global__ void __launch_bounds__(256) k_exp_extra_get(Exp e, const int64_t *idx, int batch, double *out, uint8_t *valid) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x, k = g >> 2, t = g & 3;
+  if (k >= batch) return;
+  const int64_t i = idx[k];
+  if (i < 0 || i >= e.ctl->size) return;
+  if (out) out[(size_t)k * 4 + t] = e.x[i * 4 + t];
+  if (valid && t == 0) valid[k] = e.xv[i];
+}
+
+// ReplayBuffer.update_dones (replay_buffer.py:197-209) for n entries in one workgroup: slot
+// idx[j] gets rows[j] and becomes valid.  An index outside [0, size) is skipped; of several
+// entries with one index the last wins (the largest position: an atomic max, whose result
+// no order among the atomics changes), as in k_exp_update.
+__global__ void __launch_bounds__(kExpPlanThreads) k_exp_extra_set(Exp e, const int64_t *idx, const double *rows, int n) {
+  const int t = threadIdx.x;
+  const int64_t size = e.ctl->size;
+  for (int j = t; j < n; j += kExpPlanThreads) {
+    const int64_t i = idx[j];
+    if (i >= 0 && i < size) atomicMax(&e.last[i], j);
+  }
+  __syncthreads();
+  for (int j = t; j < n; j += kExpPlanThreads) {
+    const int64_t i = idx[j];
+    if (i < 0 || i >= size || e.last[i] != j) continue;
+    for (int v = 0; v < 4; v++) e.x[i * 4 + v] = rows[(size_t)j * 4 + v];
+    e.xv[i] = 1;
   }
   __syncthreads();
   for (int j = t; j < n; j += kExpPlanThreads) {  // the scratch is -1 again for the next call

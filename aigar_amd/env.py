@@ -66,6 +66,21 @@ probability under Boltzmann).  With a replay memory the stored action row is [in
 and TEMPERATURE from `parameters`; a dict (num_actions, square, strategy, seed) overrides them.
 All players of one decision see the same epsilon and temperature; the decay schedule stays
 with the caller.  It is never switched on by `parameters` alone.
+
+Actor-critic learners (`continuous=True` or a dict; actorCritic.py:922-966, CACLA / DPG / SPG):
+the learner's actor gives n_act = 2 + ENABLE_SPLIT + ENABLE_EJECT numbers in [0, 1] per player,
+and `step_ac(mu)` makes the reference's applyNoise for every live NN player on the device, inside
+the decision's graph: numpy's legacy Gaussian or the Ornstein-Uhlenbeck recurrence (one state per
+player, cleared with the bot's history), the clip to [0, 1], then the move by the noisy action,
+which stays in `noisy_action` (NaN rows where nobody decided).  `noise_std` is the device tensor
+[std] the decision reads (write it, or call `set_noise`, to follow AC_NOISE_DECAY: no re-capture).
+`perturb(actions)` is the noise alone on any rows (SPG's offline exploration).  With a replay
+memory the stored action is the noisy one and the tuple's fifth field (bot.py:206-216) is kept:
+the raw action when ALGORITHM is "CACLA", else empty until `update_actions(idx, actions)` writes
+the best sampled action back (replay_buffer.py update_dones); `sample_extra(idx)` reads it.
+`continuous=True` reads NOISE_TYPE, ORN_UHL_THETA / MU / DT, GAUSSIAN_NOISE and ALGORITHM from
+`parameters`; a dict (noise, theta, mu, dt, std, store_raw, seed) overrides them.  It excludes
+`discrete=` and is never switched on by `parameters` alone.
 """
 import collections
 
@@ -82,8 +97,10 @@ Batch = collections.namedtuple("Batch", "s a r s2 done w idx")
 class AgarVecEnv:
     def __init__(self, n_players, parameters=None, n_arenas=1, virus=None, field_size=0, max_pellets=-1.0,
                  max_viruses=-1.0, device=0, torch_stream=True, roles=None, reset_limit=None, desync=True, seed=0,
-                 score=False, pixels=None, pixel_dtype=None, memory=None, discrete=None):
+                 score=False, pixels=None, pixel_dtype=None, memory=None, discrete=None, continuous=None):
         import torch
+        if continuous and discrete:
+            raise ValueError("continuous= and discrete= exclude each other (one learner decides per env)")
         self.torch = torch
         self.parameters = parameters
         g = (lambda n, dflt: getattr(parameters, n, dflt)) if parameters is not None else (lambda n, dflt: dflt)
@@ -162,7 +179,7 @@ class AgarVecEnv:
                 m.update(memory)
             self.memory = m
             self.stepper.exp_config(m["capacity"], prioritized=m["prioritized"], alpha=m["alpha"], beta=m["beta"],
-                                    dtype=self.obs.dtype, seed=m["seed"])
+                                    dtype=self.obs.dtype, seed=m["seed"], extra=bool(continuous))
 
         self.discrete = None
         if discrete:  # (explicit only, as memory=)
@@ -190,6 +207,165 @@ class AgarVecEnv:
             self._act_q = torch.zeros((self.NP, 4), dtype=torch.float64, device=self.dev)  # step_q_calls' chosen rows
             self._q_dtype = None
             self._decide_dtype(torch.float32)
+
+        self.continuous = None
+        if continuous:  # (explicit only, as memory=)
+            cc = {"noise": g("NOISE_TYPE", "Gaussian"), "theta": float(g("ORN_UHL_THETA", 0.15)),
+                  "mu": float(g("ORN_UHL_MU", 0)), "dt": float(g("ORN_UHL_DT", 0.01)),
+                  "std": float(g("GAUSSIAN_NOISE", 1.0)), "store_raw": g("ALGORITHM", "CACLA") == "CACLA",
+                  "seed": self.seed}
+            if isinstance(continuous, dict):
+                unknown = set(continuous) - set(cc)
+                if unknown:
+                    raise ValueError("continuous: unknown keys %s" % sorted(unknown))
+                cc.update(continuous)
+            if cc["noise"] not in _abi.NOISE_TYPES:
+                raise ValueError("continuous: noise must be one of %s" % sorted(_abi.NOISE_TYPES))
+            cc["n_act"] = 2 + int(self.enable_split) + int(bool(g("ENABLE_EJECT", False)))
+            self.continuous = cc
+            self.noise_std = torch.tensor([cc["std"]], dtype=torch.float64, device=self.dev)
+            # the persistent actor-output buffer (the decision graph is keyed by its address): always
+            # float64, so a float32 mu is widened exactly by the copy into it and the handle's noise
+            # is configured once, here -- no call reconfigures it (that would restart the Orn-Uhl
+            # state and drop the captured graph)
+            self._mu = torch.empty((self.NP, cc["n_act"]), dtype=torch.float64, device=self.dev)
+            self._nu = {}  # T -> persistent draw buffer
+            self._noisy = torch.empty((self.NP, cc["n_act"]), dtype=torch.float64, device=self.dev)
+            self.noisy_action = None
+            # step_ac_calls' twin of the handle's buffers: the held rows and the Orn-Uhl state
+            self._act_ac = torch.zeros((self.NP, cc["n_act"]), dtype=torch.float64, device=self.dev)
+            self._ou_ac = torch.zeros((self.NP, cc["n_act"]), dtype=torch.float64, device=self.dev)
+            self.stepper.noise_config(cc["n_act"], cc["noise"], torch.float64, theta=cc["theta"], ou_mu=cc["mu"],
+                                      dt=cc["dt"], seed=cc["seed"], store_raw=cc["store_raw"])
+
+    def _need_continuous(self):
+        if self.continuous is None:
+            raise RuntimeError("AgarVecEnv was created without continuous=")
+
+    def set_noise(self, std):
+        """Write the decision's noise level (the device tensor `noise_std`)."""
+        self._need_continuous()
+        self.noise_std[0] = float(std)
+
+    def _mu_buffers(self, mu, u, what):
+        torch = self.torch
+        self._need_continuous()
+        n = self.continuous["n_act"]
+        if not isinstance(mu, torch.Tensor):
+            mu = torch.as_tensor(np.asarray(mu), device=self.dev)
+        if mu.dtype not in (torch.float32, torch.float64):
+            raise ValueError("%s: mu must be float32 or float64, got %s" % (what, mu.dtype))
+        if tuple(mu.shape) != (self.NP, n):
+            raise ValueError("%s: mu must be [%d, %d], got %s" % (what, self.NP, n, tuple(mu.shape)))
+        buf = self._mu
+        buf.copy_(mu)  # (float32 -> float64: exact)
+        if u is not None:
+            u = torch.as_tensor(u, dtype=torch.float64, device=self.dev)
+            if u.dim() != 4 or tuple(u.shape[:2]) != (self.NP, 2) or int(u.shape[3]) != 2:
+                raise ValueError("%s: u must be [%d, 2, T, 2], got %s" % (what, self.NP, tuple(u.shape)))
+            ub = self._nu.get(int(u.shape[2]))
+            if ub is None:
+                ub = self._nu[int(u.shape[2])] = torch.empty(tuple(u.shape), dtype=torch.float64, device=self.dev)
+            ub.copy_(u)
+            u = ub
+        return buf, u
+
+    def step_ac(self, mu, u=None):
+        """mu: [n_players, n_act] float32 / float64 device tensor of the actor's outputs (rows of
+        dead and non-NN players are ignored; float32 is widened exactly, and either dtype may
+        follow the other) -> (obs, reward, alive, done) as `step`; the noise and the decision
+        are one graph replay.  u: [n_players, 2, T, 2] uniforms in [0, 1) (row,
+        pair, attempt, {ua, ub}; T <= 16), None: the device's own.  Leaves a fresh clone of the
+        noisy actions in `noisy_action` (NaN rows where nobody decided)."""
+        buf, u = self._mu_buffers(mu, u, "step_ac")
+        self.stepper.env_step_ac(buf, self.noise_std, self._r, self.obs, u=u, noisy=self._noisy,
+                                 enable_split=self.enable_split, skip=self.skip, params=self.reward_params)
+        self.noisy_action = self._noisy.clone()
+        return self._after_decision()
+
+    def step_ac_calls(self, mu, u=None):
+        """The same decision as separate calls (noise, then `step_calls`); without the episode
+        bookkeeping and the replay memory's fifth field.  This path keeps its own Orn-Uhl state
+        (`_ou_ac`), cleared by `reset` and at an episode's end, not by direct stepper calls."""
+        torch = self.torch
+        buf, u = self._mu_buffers(mu, u, "step_ac_calls")
+        # who decides: the live NN players, as the kernel tests it
+        alive = self.stepper.player_stats()[:, 0] != 0
+        deciding = torch.as_tensor(alive, device=self.dev) & self.nn
+        ou = self._ou_ac.clone()
+        out = torch.empty_like(self._noisy)
+        self.stepper.noise(buf, self.noise_std, out, u=u, prev=ou if self.stepper.noi[2] else None)
+        d2 = deciding[:, None]
+        self._ou_ac = torch.where(d2, ou, self._ou_ac)
+        self._act_ac = torch.where(d2, out, self._act_ac)
+        self.noisy_action = torch.where(d2, out, torch.full_like(out, float("nan")))
+        return self.step_calls(self._act_ac)
+
+    def perturb(self, actions, std=None, u=None, prev=None):
+        """The noise alone (aigar_noise) on any rows: actions [rows, n_act] float32 / float64 ->
+        a fresh float64 tensor of noisy actions.  std: a float or a [1] float64 device tensor
+        (None: `noise_std`); u: [rows, 2, T, 2] uniforms (None: the device's own); prev: the
+        caller's [rows, n_act] float64 Orn-Uhl state, advanced in place (needed for Orn-Uhl).
+        Liveness and roles are ignored, and nothing of the decision is touched: not the players'
+        Orn-Uhl state, not the captured graph.  The device's own draws depend on (row, pair,
+        attempt, tick, seed) alone: a second call before the next decision gives row r the same
+        normals, and so does the decision itself for rows below n_players -- pass u, or put the
+        batches into one call as further rows."""
+        torch = self.torch
+        self._need_continuous()
+        a = actions if isinstance(actions, torch.Tensor) else torch.as_tensor(np.asarray(actions), device=self.dev)
+        if a.dtype not in (torch.float32, torch.float64):
+            raise ValueError("perturb: actions must be float32 or float64, got %s" % a.dtype)
+        if a.dim() != 2 or int(a.shape[1]) != self.continuous["n_act"]:
+            raise ValueError("perturb: actions must be [rows, %d], got %s" % (self.continuous["n_act"], tuple(a.shape)))
+        a = a.to(device=self.dev, dtype=torch.float64).contiguous()  # (float32 -> float64: exact)
+        if std is None:
+            std = self.noise_std
+        elif not isinstance(std, torch.Tensor):
+            std = torch.tensor([float(std)], dtype=torch.float64, device=self.dev)
+        if u is not None:
+            u = torch.as_tensor(u, dtype=torch.float64, device=self.dev).contiguous()
+        out = torch.empty(tuple(a.shape), dtype=torch.float64, device=self.dev)
+        if self._mem_sync:
+            torch.cuda.synchronize(self.dev)
+        self.stepper.noise(a, std, out, u=u, prev=prev)
+        if self._mem_sync:
+            self.stepper.sync()
+        return out
+
+    def sample_extra(self, idx):
+        """(extra [batch, 4] float64, valid [batch] bool) of the memory slots idx: the tuple's
+        fifth field -- CACLA's raw action, or what `update_actions` wrote; NaN and False where
+        the slot has none (the reference's None) or idx is outside [0, size)."""
+        if self.memory is None or self.continuous is None:
+            raise RuntimeError("AgarVecEnv was created without memory= and continuous=")
+        torch = self.torch
+        idx = torch.as_tensor(idx, dtype=torch.int64, device=self.dev).contiguous()
+        extra = torch.full((int(idx.shape[0]), 4), float("nan"), dtype=torch.float64, device=self.dev)
+        valid = torch.zeros(int(idx.shape[0]), dtype=torch.bool, device=self.dev)
+        if self._mem_sync:
+            torch.cuda.synchronize(self.dev)
+        self.stepper.exp_extra_get(idx, extra, valid)
+        if self._mem_sync:
+            self.stepper.sync()
+        return extra, valid
+
+    def update_actions(self, idx, actions):
+        """The trainer's write-back of the best sampled actions (aigar.py:1079-1086,
+        replay_buffer.py update_dones): slot idx[j] gets actions[j] ([n, n_act] or [n, 4],
+        padded with zeros) as its fifth field; the last of a repeated index wins."""
+        if self.memory is None or self.continuous is None:
+            raise RuntimeError("AgarVecEnv was created without memory= and continuous=")
+        torch = self.torch
+        idx = torch.as_tensor(idx, dtype=torch.int64, device=self.dev).contiguous()
+        a = torch.as_tensor(actions, dtype=torch.float64, device=self.dev)
+        rows = torch.zeros((int(idx.shape[0]), 4), dtype=torch.float64, device=self.dev)
+        rows[:, :a.shape[1]] = a
+        if self._mem_sync:
+            torch.cuda.synchronize(self.dev)
+        self.stepper.exp_extra_set(idx, rows)
+        if self._mem_sync:
+            self.stepper.sync()  # (rows is freed when this returns)
 
     def _decide_dtype(self, dtype):
         """(Re)configure the selection for Q rows of dtype (the kernel is built per dtype)."""
@@ -304,6 +480,8 @@ class AgarVecEnv:
         with several arenas, the desynchronising warm-up (aigar.py:833-837)."""
         seed = self.seed if seed is None else int(seed)
         self.stepper.reset(seed)
+        if self.continuous is not None:
+            self._ou_ac.zero_()
         self.age[:] = 0
         self._resets = 0
         if self.desync:
@@ -387,6 +565,8 @@ class AgarVecEnv:
             self.last_return = torch.where(ended_t & self.nn, self._ret, self.last_return)
             self._ret = torch.where(ended_t, torch.zeros_like(self._ret), self._ret)
         self.stepper.reset_arenas(ended, seeds)  # one call, on the device
+        if self.continuous is not None:  # (step_ac_calls' twin of the handle's Orn-Uhl state restarts too)
+            self._ou_ac = torch.where(ended_t[:, None], torch.zeros_like(self._ou_ac), self._ou_ac)
         done[ended_t] = True
         # the new episodes' first states (NN players of the reset arenas)
         nn_reset = (mask & (self.roles == _abi.ROLE_NN)).astype(np.uint8)

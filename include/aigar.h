@@ -400,6 +400,7 @@ int aigar_observe_pixel_state(aigar_handle *h, void *out, int dtype, int on_devi
  * itself and every given priority, overwritten duplicates included.  Entries with
  * prio <= 0 or an index outside [0, size) are skipped.  Nothing happens in uniform mode. */
 #define AIGAR_EXP_PRIORITIZED 0x1   /* PRIORITIZED_EXP_REPLAY_ENABLED */
+#define AIGAR_EXP_EXTRA       0x2   /* the tuple's fifth field (aigar_exp_extra_get / _set) */
 typedef struct aigar_exp_params {
   int64_t capacity;     /* MEMORY_CAPACITY: transitions kept, a ring; >= n_arenas * bots_per_arena */
   int32_t state_dtype;  /* 0 float64, 1 float32: how states are stored and handed out            */
@@ -467,10 +468,118 @@ int aigar_decide(aigar_handle *h, const void *q, const double *explore, const do
 int aigar_env_step_q(aigar_handle *h, const void *q, const double *explore, const double *u, int enable_split, int skip,
                      const aigar_reward_params *p, double *reward_out, void *obs_out, int dtype, int32_t *idx_out,
                      double *val_out);
+/* The actor-critic learners' exploration noise (actorCritic.py:922-966 applyNoise /
+ * decideMove; tests/noise_model.py is the specification in plain Python).
+ * The learner's actor gives n_act = 2..4 numbers in [0, 1] per player; the device perturbs
+ * every live NN player's row mu[n_act] (float32 or float64, widened exactly) with Gaussian
+ * or Ornstein-Uhlenbeck noise, clips it to [0, 1] and moves the player by it.  All
+ * arithmetic is float64 in the reference's operation order; the only fused multiply-adds
+ * are inside glibc's log (aigar_selftest_log).
+ *
+ * A standard-normal pair is numpy's legacy Gaussian (RandomState.normal, the polar
+ * method): attempt t takes two uniforms (ua, ub) on numpy's 53-bit grid, x1 = 2 ua - 1,
+ * x2 = 2 ub - 1, r2 = x1 x1 + x2 x2; it is rejected unless r2 < 1 and r2 != 0; else
+ * f = sqrt(-2 log(r2) / r2) and the pair is (f x2, f x1), in numpy's order.  Values 0 and
+ * 1 of a row take pair 0, values 2 and 3 pair 1; an odd n_act drops its leftover normal
+ * (numpy would carry it into the next call).  At most T <= 16 attempts are made per pair;
+ * a pair that exhausts them is (0.0, 0.0) and the row's arena gets the sticky bit
+ * AIGAR_WARN_NOISE_EXHAUSTED (with own draws: about 2e-11 per pair).
+ *   type 0, Gaussian:  a_i = mu_i + std z_i.
+ *   type 1, Orn-Uhl:   noise_i = prev_i + theta (ou_mu - prev_i) dt + std sqrt(dt) z_i in
+ *     Python's left-to-right association; prev_i = noise_i; a_i = mu_i + noise_i.
+ *   Both end with numpy.clip(a, 0, 1) (a -0.0 stays -0.0, as numpy leaves it).
+ * std is ONE double read from DEVICE memory at every call / replay (a decay schedule is a
+ * write by the caller, no re-capture); all players of a decision see the same std.
+ * Outside the contract, no error: a NaN or an infinity in a deciding row's mu is taken as
+ * 0.0, a std that is negative, NaN or infinite as 0.0, an Orn-Uhl state that would become
+ * NaN or infinite (a huge std, a non-finite prev of the caller) restarts at 0.0 with no noise
+ * for that value, and the row's arena gets the sticky bit AIGAR_WARN_NOISE_NONFINITE.  (A
+ * Gaussian mu + std z that overflows is clipped to 0 or 1 like any other value.)
+ *
+ * Draws.  u: DEVICE [rows][2][T][2] uniforms in [0, 1) (row, pair, attempt, {ua, ub}), T
+ * given in the call (1..16); or NULL: the device's own, T = 16: attempts 2 b and 2 b + 1
+ * of (row, pair) are the top 53 bits of words {0, 1} and {2, 3} of Philox4x64-10 keyed by
+ * the arena's key at the counter (row, 11 | pair << 8 | b << 16, the arena's tick, seed);
+ * 11 is the stream word ST_NOISE.  Row r belongs to arena (r / bots_per_arena) % n_arenas
+ * (the player's arena when rows = n_arenas * bots_per_arena).  Nothing in the counter names
+ * the call: own draws depend on (row, pair, attempt, tick, seed) alone, so two aigar_noise
+ * calls between two ticks give row r the same normals, and so does an aigar_noise call and
+ * the aigar_env_step_ac that follows it at the same tick, for rows below A*B.  A caller that
+ * perturbs several batches per step (SPG's offline exploration) passes its own u, or gives
+ * each batch other rows of one larger call.
+ *
+ * Differences from the reference (the device's choice first): the Orn-Uhl state is per
+ * player, the reference keeps one on the shared learner; the stored raw action is the
+ * actor's own output in float64, the reference's Orn-Uhl branch adds the noise into the
+ * array it later stores as "raw" (and rounds to float32 in a float32 array); the
+ * critic-guided OCACLA_ONLINE_SAMPLES stay with the caller, who has aigar_noise for them.
+ *
+ * aigar_noise_config: p NULL turns it off.  Allocates the handle's action, raw-action and
+ * Orn-Uhl buffers ([A*B][n_act] each, zeros) and drops the captured decision graph; a
+ * tiled handle is refused.  The Orn-Uhl state is zero at config time and cleared wherever
+ * the bots' history is: aigar_reset, aigar_reset_arenas, aigar_load_state,
+ * aigar_reset_bots (actorCritic.py:1121-1123).
+ *
+ * mu_dtype holds for aigar_noise and aigar_env_step_ac alike, and configuring again restarts
+ * the Orn-Uhl state: a caller with rows of both dtypes configures float64 once and widens its
+ * float32 rows (exact), as AgarVecEnv does.
+ *
+ * aigar_noise: the perturbation alone, stream-ordered, all DEVICE pointers, on any rows
+ * >= 0 of mu [rows][n_act] into noisy_out [rows][n_act]; it ignores liveness and roles
+ * (SPG's offline exploration, actorCritic.py:892-896, calls it on [batch x samples]
+ * rows).  prev: the caller's Orn-Uhl state [rows][n_act], advanced in place; NULL with an
+ * Orn-Uhl config is an error (ignored with a Gaussian config).  n_exhausted (may be NULL):
+ * a DEVICE uint64 counter that every exhausted pair increments.
+ *
+ * aigar_env_step_ac: the noise for every live NN player and then aigar_env_step's whole
+ * decision with the noisy rows as its n_act-value actions, one graph replay (re-captured
+ * when a pointer or a parameter changes).  A dead or non-NN player keeps its row of the
+ * handle's action buffer and its Orn-Uhl state; its noisy_out row (may be NULL;
+ * [A*B][n_act]) is NaN.  With a replay memory the transition's action row is the noisy
+ * action padded with zeros; with AIGAR_EXP_EXTRA see there.  All three are error returns
+ * without a config. */
+#define AIGAR_NOISE_GAUSSIAN 0   /* NOISE_TYPE == "Gaussian" */
+#define AIGAR_NOISE_ORN_UHL  1   /* NOISE_TYPE == "Orn-Uhl"  */
+typedef struct aigar_noise_params {
+  int32_t n_act;      /* values per action: 2 + ENABLE_SPLIT + ENABLE_EJECT, 2..4         */
+  int32_t type;       /* AIGAR_NOISE_*                                                   */
+  int32_t mu_dtype;   /* 0 float64, 1 float32                                            */
+  int32_t store_raw;  /* the replay memory's extra field gets the raw action (CACLA)     */
+  double theta;       /* ORN_UHL_THETA                                                   */
+  double ou_mu;       /* ORN_UHL_MU                                                      */
+  double dt;          /* ORN_UHL_DT (>= 0)                                               */
+  uint64_t seed;      /* Philox salt of the own draws                                    */
+} aigar_noise_params;
+int aigar_noise_config(aigar_handle *h, const aigar_noise_params *p);
+int aigar_noise(aigar_handle *h, const void *mu, int rows, const double *std, const double *u, int T, double *prev,
+                double *noisy_out, uint64_t *n_exhausted);
+int aigar_env_step_ac(aigar_handle *h, const void *mu, const double *std, const double *u, int T, int enable_split,
+                      int skip, const aigar_reward_params *p, double *reward_out, void *obs_out, int dtype,
+                      double *noisy_out);
+/* The replay memory's fifth field (bot.py:206-216; replay_buffer.py:197-209 update_dones;
+ * aigar.py:1079-1086).  With AIGAR_EXP_EXTRA in aigar_exp_params.flags the ring also keeps
+ * extra[capacity][4] doubles and a valid byte per slot.  aigar_env_step_ac's transition
+ * then carries a = the noisy action padded with zeros and, when the noise config has
+ * store_raw (CACLA), extra = the raw action padded with zeros, valid; without store_raw
+ * (SPG, DPG) the slot's extra is invalid: NaN, valid 0 -- the reference's None.  Every
+ * other add (aigar_env_step, aigar_env_step_q, aigar_exp_add) leaves the extra invalid.  A
+ * ring wrap overwrites a slot's extra together with its transition; aigar_exp_config
+ * clears them.  aigar_exp_sample, aigar_exp_gather and a memory without the flag are
+ * unchanged.  Both calls below take DEVICE pointers, are stream-ordered and are error
+ * returns on a memory without the flag.
+ * aigar_exp_extra_get: out[batch][4] and valid[batch] (each may be NULL) of the slots
+ * idx[batch]; rows whose index is outside [0, size) are left untouched.
+ * aigar_exp_extra_set (update_dones): slot idx[j] gets rows[j][4] and becomes valid, j < n
+ * <= capacity; of several entries with one index the last in order wins; indices outside
+ * [0, size) are skipped. */
+int aigar_exp_extra_get(aigar_handle *h, const int64_t *idx, int batch, double *out, uint8_t *valid);
+int aigar_exp_extra_set(aigar_handle *h, const int64_t *idx, const double *rows, int n);
 /* The sticky quirk bits of one arena since its last reset (a host round trip): 1 a virus
  * made this tick ate, 2 a dead virus was met, 4 a tile observed past its held pellets,
- * 8 AIGAR_WARN_Q_NONFINITE. */
+ * 8 AIGAR_WARN_Q_NONFINITE, 16 AIGAR_WARN_NOISE_NONFINITE, 32 AIGAR_WARN_NOISE_EXHAUSTED. */
 #define AIGAR_WARN_Q_NONFINITE 0x8
+#define AIGAR_WARN_NOISE_NONFINITE 0x10
+#define AIGAR_WARN_NOISE_EXHAUSTED 0x20
 int aigar_warnings(aigar_handle *h, int arena, uint32_t *out);
 /* bot.currentAction / bot.lastAction used by the action extras: [A*B][4] each (may be NULL). */
 int aigar_set_actions(aigar_handle *h, const double *cur, const double *prev, int on_device);
@@ -642,6 +751,8 @@ int aigar_counters(aigar_handle *h, int arena, int64_t *out, int n);
 /* Diagnostics: evaluate the device's pow (aigar_math.h: glibc 2.35's pow, bit
  * for bit) on host arrays of n (x, y) pairs -- used by the parity tests. */
 int aigar_selftest_pow(const double *x, const double *y, double *out, int n);
+/* out[i] = log(x[i]) as the device computes it (glibc 2.35's, restated in aigar_math.h); host arrays. */
+int aigar_selftest_log(const double *x, double *out, int n);
 
 /* Diagnostics: evaluate the device's trig (aigar_glibc_trig.h: glibc 2.35's
  * __ieee754_atan2_fma / __sin_fma / __cos_fma, bit for bit) on host arrays:

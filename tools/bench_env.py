@@ -4,7 +4,8 @@ size with the reference's NN-bot frame skipping (FRAME_SKIP_RATE = 7,
 networkParameters.py:33), one graph replay per decision (env.step) against the
 same decision as separate calls (env.step_calls).  Prints one JSON line.
 --memory: the replay memory's cost at the same shape instead (see memory()).
---discrete / --discrete-baseline: the Q-learning selection's cost (see discrete())."""
+--discrete / --discrete-baseline: the Q-learning selection's cost (see discrete()).
+--continuous / --continuous-baseline gaussian|ou: the exploration noise's cost (see continuous())."""
 import json
 import os
 import sys
@@ -164,8 +165,73 @@ def discrete(baseline_only=False, rounds=3, n=40):
     print(json.dumps(out))
 
 
+def continuous(kind, baseline_only=False, rounds=3, n=40):
+    """--continuous gaussian|ou: an actor-critic decision at the C3 shape (4096 NN bots, 8 ticks
+    per decision, 3 values per action): `step_ac` (the noise inside the decision graph) against
+    `step` with the perturbation written in torch on the same stream (torch.randn, the Orn-Uhl
+    update, clamp), alternated `rounds` times on envs of the same seed.  --continuous-baseline:
+    the torch variant alone -- it uses nothing of the noise, so it also runs on a build without
+    it (the parent commit's side of the comparison)."""
+    import torch
+    from aigar_amd.env import AgarVecEnv
+    p = parameters()
+    p.NOISE_TYPE = {"gaussian": "Gaussian", "ou": "Orn-Uhl"}[kind]
+    p.GAUSSIAN_NOISE, p.ORN_UHL_THETA, p.ORN_UHL_MU, p.ORN_UHL_DT, p.ALGORITHM = 0.3, 0.15, 0.0, 0.01, "CACLA"
+    bots, n_act = 4096, 3
+    mu = torch.rand((bots, n_act), dtype=torch.float32, device="cuda")
+    out = {"workload": "C3 AgarVecEnv: 4096 NN bots, FRAME_SKIP_RATE 7, actor rows [4096, 3] float32, %s noise" % p.NOISE_TYPE,
+           "decisions": n, "rounds": rounds}
+    envs = {"torch": AgarVecEnv(bots, p, field_size=4800, max_pellets=100000.0)}
+    if not baseline_only:
+        envs["step_ac"] = AgarVecEnv(bots, p, field_size=4800, max_pellets=100000.0, continuous=True)
+    prev = torch.zeros((bots, n_act), dtype=torch.float64, device="cuda")
+    std, sq = p.GAUSSIAN_NOISE, p.ORN_UHL_DT ** 0.5
+
+    def torch_step(env):
+        z = torch.randn((bots, n_act), dtype=torch.float64, device="cuda")
+        if kind == "gaussian":
+            a = mu.double() + std * z
+        else:
+            prev.add_(p.ORN_UHL_THETA * (p.ORN_UHL_MU - prev) * p.ORN_UHL_DT + std * sq * z)
+            a = mu.double() + prev
+        return env.step(a.clamp_(0.0, 1.0))
+
+    run = {"torch": lambda: torch_step(envs["torch"])}
+    if not baseline_only:
+        run["step_ac"] = lambda: envs["step_ac"].step_ac(mu)
+    for k, env in envs.items():
+        env.reset(1)
+        for _ in range(5):
+            run[k]()
+    ms = {k: [] for k in envs}
+    for _ in range(rounds):
+        for k in envs:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                run[k]()
+            torch.cuda.synchronize()
+            ms[k].append((time.perf_counter() - t0) / n * 1e3)
+    out["ms_per_decision"] = ms
+    out["decisions_per_s"] = {k: [1e3 / x for x in v] for k, v in ms.items()}
+    for env in envs.values():
+        env.close()
+    print(json.dumps(out))
+
+
+def _kind(flag):
+    k = sys.argv[sys.argv.index(flag) + 1] if len(sys.argv) > sys.argv.index(flag) + 1 else ""
+    if k not in ("gaussian", "ou"):
+        sys.exit("%s takes gaussian or ou" % flag)
+    return k
+
+
 if __name__ == "__main__":
-    if "--memory" in sys.argv:
+    if "--continuous" in sys.argv:
+        continuous(_kind("--continuous"))
+    elif "--continuous-baseline" in sys.argv:
+        continuous(_kind("--continuous-baseline"), baseline_only=True)
+    elif "--memory" in sys.argv:
         memory()
     elif "--discrete" in sys.argv or "--discrete-baseline" in sys.argv:
         discrete(baseline_only="--discrete-baseline" in sys.argv)
