@@ -44,7 +44,8 @@ namespace aigar {
 struct ArenaCtl {
   int64_t seq_next;  // next Cell creation sequence number
   int64_t tick;      // completed Field.update() calls since reset
-  int64_t tick_sp;   // the tick spawnStuff runs in (k_pel_update advances tick beside its respawns)
+  int64_t tick_sp;   // the tick spawnStuff runs in (tick itself advances in the tick's last launch: k_spawn_plan's
+                     // arena block once its events are pushed; tiled ticks: k_pel_update, beside its respawns)
   uint64_t key0, key1, ctr_pellet, ctr_virus;
   int64_t seq_base_upd;  // seq_next before updatePlayers' creations (this tick)
   int64_t seq_base_spawn;
@@ -73,8 +74,9 @@ struct ArenaCtl {
   uint32_t scan_epoch[2];  // decoupled look-back epoch per scan slot (grows every launch)
   int scan_ticket[2];      // slot 0: pellet rebuilds, slot 1: cell grid (may run concurrently)
   int src_n_stage;  // reset: the staged records the row build places
-  int n_kill;      // buffer pellets killed this tick (kill_list; sorted + unique after k_spawn_plan)
-  int pu_nconv;   // the closing update: this tick's blob conversions (staged records 0 .. pu_nconv - 1)
+  int n_kill;      // buffer pellets killed this tick (kill_list)
+  int pu_nconv;   // the closing update (written by pellet_close_prep: k_pp_active's arena blocks, tiled ticks k_spawn_plan):
+                  // this tick's blob conversions (staged records 0 .. pu_nconv - 1)
   int pu_nsp, pu_spec;  // the closing update: this tick's pellet spawns, drawn ahead (spec_*) or staged (pn)
   uint32_t dirty;     // DIRTY_*: a virus / blob died this tick (k_spawn_plan compacts)
   int food_undone[3];  // cells that failed reservation round r (index r % 3)
@@ -274,7 +276,7 @@ struct Dev {
   // observation overflow pool (bots that see more objects than their LDS lists hold)
   int OBcap;
   unsigned long long *ob_used;  // {observe call epoch:32 | overflow slots taken:32}
-  uint32_t *ob_epoch;  // device-side epoch for graph-replayed observes (bumped by k_player_fov)
+  uint32_t *ob_epoch;  // device-side epoch for graph-replayed observes (bumped by the tick's last launch and by k_player_fov)
   int64_t *ob_seq;
   double *ob_m, *ob_r;
   uint32_t *ob_mask;

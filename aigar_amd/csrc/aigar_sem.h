@@ -160,6 +160,33 @@ AIGAR_D double np_sum(const double *a, int n) {
   for (; i < n; i++) res += a[i];
   return res;
 }
+// np_sum fed one term at a time, in order, the count known: the same additions
+// in the same order without the array (term k of n goes where np_sum's loops
+// take a[k] from: the running sum below 8 terms; else one of the 8 accumulators,
+// first as its start and in the blocks of 8 as an addend, or the tail behind
+// the accumulators' pairwise sum).  k is a constant wherever add is called
+// (unrolled loops), so the state stays in registers.
+struct NpAcc {
+  double r[8], res;
+  AIGAR_D double pairs() const { return ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7])); }
+  AIGAR_D void add(int k, int n, double v) {
+    if (n < 8) {
+      if (k == 0) res = 0.;
+      res += v;
+    } else if (k < 8) {
+      r[k] = v;
+    } else if (k < n - (n % 8)) {
+      r[k & 7] += v;
+    } else {
+      if (k == n - (n % 8)) res = pairs();
+      res += v;
+    }
+  }
+  AIGAR_D double sum(int n) const {
+    if (n < 8) return n ? res : 0.;
+    return (n % 8) ? res : pairs();
+  }
+};
 
 // Python round(v, 3) (bot.py:450): round-half-even of the exact binary value
 // to a multiple of 1/1000, returned as the double nearest to k/1000 (what

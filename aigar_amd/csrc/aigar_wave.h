@@ -174,27 +174,51 @@ struct Fov {
   double fx, fy, fs, mass, rmax;
   int n;
 };
-__device__ inline Fov player_fov(const Dev &d, int gp) {
-  const int NP = d.NP;
-  Fov f;
-  int n = d.p_ncells[gp];
-  f.n = n;
-  double ms[kMaxCells], xs[kMaxCells], ys[kMaxCells];
+// The one place the FOV arithmetic lives, whoever holds the cells: cell(k, x, y,
+// m, r) gives list row k's cell (from memory, from the caller's registers, from
+// LDS).  The three sums are np_sum's, fed term by term (NpAcc: no arrays).
+template <class Cell>
+__device__ __forceinline__ Fov player_fov_of(const Dev &d, int n, Cell cell) {
+  NpAcc am, ax, ay;
+  am.res = ax.res = ay.res = 0.;
   double rb = -1;
-  for (int k = 0; k < n; k++) {
-    size_t ci = (size_t)d.p_list[k * NP + gp] * NP + gp;
-    double m = d.c_m[ci], r = d.c_r[ci];
-    ms[k] = m;
-    xs[k] = d.c_x[ci] * m;
-    ys[k] = d.c_y[ci] * m;
-    if (k == 0 || r > rb) rb = r;
+#pragma unroll
+  for (int k = 0; k < kMaxCells; k++) {
+    if (k < n) {
+      double x, y, m, r;
+      cell(k, x, y, m, r);
+      am.add(k, n, m);
+      ax.add(k, n, x * m);
+      ay.add(k, n, y * m);
+      if (k == 0 || r > rb) rb = r;
+    }
   }
-  f.mass = n ? np_sum(ms, n) : 0.0;
+  Fov f;
+  f.n = n;
+  f.mass = n ? am.sum(n) : 0.0;
   f.fs = aigar_math::pow_glibc(rb, 0.475) * d.pow_n032[n] * 35;  // (table: same glibc pow values)
-  f.fx = np_sum(xs, n) / f.mass;
-  f.fy = np_sum(ys, n) / f.mass;
+  f.fx = ax.sum(n) / f.mass;
+  f.fy = ay.sum(n) / f.mass;
   f.rmax = rb;
   return f;
+}
+__device__ inline Fov player_fov(const Dev &d, int gp) {
+  const int NP = d.NP;
+  const int n = d.p_ncells[gp];
+  return player_fov_of(d, n, [&](int k, double &x, double &y, double &m, double &r) {
+    const size_t ci = (size_t)d.p_list[k * NP + gp] * NP + gp;
+    x = d.c_x[ci];
+    y = d.c_y[ci];
+    m = d.c_m[ci];
+    r = d.c_r[ci];
+  });
+}
+// a live player's FOV cache entry
+__device__ __forceinline__ void fov_store(const Dev &d, int gp, const Fov &f) {
+  d.p_fx[gp] = f.fx;
+  d.p_fy[gp] = f.fy;
+  d.p_fs[gp] = f.fs;
+  d.p_mass[gp] = f.mass;
 }
 // per-player FOV cache, refreshed once the world state of a tick is final
 __device__ inline void store_player_fov(const Dev &d, int gp) {

@@ -25,10 +25,19 @@
 //                             parallel activity test; its serial pass (one wavefront per
 //                             arena walks the active players in order: live-list semantics
 //                             incl. skip-after-removal, re-activating neighbours on growth)
-//                             opens k_spawn_plan
+//                             opens k_spawn_plan.  Untiled ticks: the player waves also store
+//                             the FOV cache (from the cells before the pass), and one more
+//                             block per arena closes the pellet bookkeeping (spawn counts,
+//                             staged spawns), final since the eat phase
 //   k_spawn_plan/all          spawnStuff               field.py:256-313
-//   k_pel_update              closing pellet update: the bucket rows whose pellets changed are
-//                             rewritten; extra blocks respawn players (FOV cache) and spawn viruses
+//                             untiled ticks, the tick's last launch: + the closing pellet
+//                             update's row blocks behind the arena blocks (beside the pp
+//                             pass: they share no word with it); the arena block then respawns
+//                             players, spawns viruses and stores the FOV cache entries of the
+//                             players the pp pass changed or that respawned
+//   k_pel_update              (tiled ticks only) closing pellet update: the bucket rows whose
+//                             pellets changed are rewritten; extra blocks respawn players (FOV
+//                             cache) and spawn viruses
 // "last block" = the block that draws the last ticket (last_block): an idle
 // serial pass then costs a ticket, not a dependent launch.
 #include <hip/hip_runtime.h>
@@ -3365,9 +3374,10 @@ __device__ __forceinline__ void occ_rebuild_dirty(const Dev &d, int a, const uin
 
 // one wavefront per player: cells with an overlapping enemy cell at phase start
 // (+ the player's cells into the spawn occupancy)
-__device__ __forceinline__ void pp_active_own(const Dev &d PT_PARAMS) {
+// (nblocks: the grid's player blocks; k_pp_active's grid may hold others behind them)
+__device__ __forceinline__ void pp_active_own(const Dev &d, int nblocks PT_PARAMS) {
   const int lane = threadIdx.x & 63;
-  const int gp = xcd_block(blockIdx.x, gridDim.x) * 4 + (threadIdx.x >> 6);
+  const int gp = xcd_block(blockIdx.x, nblocks) * 4 + (threadIdx.x >> 6);
   // C4, device-bounded eat passes: the tick may go on only if no owned cell is undone
   if (d.tiled && gp == 0 && lane == 0 && d.ctl[0].n_undone_glob != 0) atomicOr(&d.ctl[0].err, ERR_TILE_PASSES);
   if (gp >= d.NP) return;
@@ -3476,12 +3486,24 @@ __device__ __forceinline__ void pp_active_own(const Dev &d PT_PARAMS) {
     else set_err(d, a, ERR_WORK_CAP);
   }
 }
-__global__ void __launch_bounds__(256) k_pp_active(Dev d) {
-  FLOOR(6);
-  PT_BEGIN(3);
-  pp_active_own(d PT_ARGS);
-}
 
+// The players whose cell list, mass or radius the pp pass changed, eater and
+// eaten: a bitmap in the LDS of k_spawn_plan's block, which stores their FOV
+// cache entries again once the pass is over (k_pp_active stored every live
+// player's from the cells before the pass).  Bit p % FOVM_BITS stands for arena
+// player p: in a larger arena a mark also covers p's aliases, whose recomputed
+// entries are what they were.
+constexpr int FOVM_BITS = 8192;
+__device__ __forceinline__ uint32_t *fov_marks() {
+  __shared__ uint32_t s_fovm[FOVM_BITS / 32];
+  return s_fovm;
+}
+__device__ __forceinline__ void fov_mark(int p) {
+  atomicOr(&fov_marks()[(p & (FOVM_BITS - 1)) >> 5], 1u << (p & 31));
+}
+__device__ __forceinline__ bool fov_marked(int p) {
+  return (fov_marks()[(p & (FOVM_BITS - 1)) >> 5] >> (p & 31)) & 1u;
+}
 // removes cell e (pool index) from its player's list; returns true if the player died
 __device__ __forceinline__ bool remove_cell(const Dev &d, int a, size_t e, uint64_t &order, bool writer = true) {
   const int NP = d.NP;
@@ -3716,6 +3738,10 @@ __device__ __forceinline__ void pp_turns(const Dev &d, int a, uint32_t *pend, co
           pr = mr;
         }
         rmax = fmax(rmax, mr);
+        if (lane == 0) {  // eater and eaten: their FOV cache entries are stored again
+          fov_mark((int)(g % NP) - a * B);
+          fov_mark((int)(v % NP) - a * B);
+        }
         remove_cell(d, a, v, order, lane == 0);
         // re-activate every later turn whose outcome the growth of g may change
         const int gpl = (int)(g % NP);
@@ -3903,6 +3929,8 @@ __device__ __forceinline__ void pp_group_turns(const Dev &d, int a, uint32_t *pe
         if (lane == 0) {
           tab.m[gi] = m;
           tab.r[gi] = mr;
+          fov_mark((int)(g % NP) - a * B);  // eater and eaten: their FOV cache entries are stored again
+          fov_mark((int)(tab.e[vi] % NP) - a * B);
         }
         remove(vi, order);
         PA_T(4);
@@ -4414,20 +4442,61 @@ struct SpawnIn {
   int n_pel, n_pel_eaten, n_pnew, n_pel_glob, n_eaten_glob, n_vir;
   int64_t seq_next, tick, stat3, stat5;
   uint64_t ctr_pellet, ctr_virus;
+  int n_spawn_p;  // (spawn_in_rest only: the pellet part's result)
 };
 __device__ __forceinline__ SpawnIn spawn_in(const ArenaCtl &c) {
   return SpawnIn{c.n_pel,    c.n_pel_eaten, c.n_pnew,    c.n_pel_glob, c.n_eaten_glob, c.n_vir,
-                 c.seq_next, c.tick,        c.stat[3],   c.stat[5],    c.ctr_pellet,   c.ctr_virus};
+                 c.seq_next, c.tick,        c.stat[3],   c.stat[5],    c.ctr_pellet,   c.ctr_virus, 0};
 }
+// The untiled tick closes its pellet bookkeeping early (k_pp_active's arena
+// blocks: spawn_counts_pel, pellet_close_prep; nothing after the eat phase
+// touches a pellet), so the row blocks can run beside the pp pass.  Each half
+// loads only its own fields: the pellet half a launch before the row blocks,
+// the rest in k_spawn_plan, which must not read the words the row blocks of its
+// own launch change (n_pel) -- seq_next stays untouched in between.
+__device__ __forceinline__ SpawnIn spawn_in_pel(const ArenaCtl &c) {
+  SpawnIn in{};
+  in.n_pel = c.n_pel;
+  in.n_pel_eaten = c.n_pel_eaten;
+  in.n_pnew = c.n_pnew;
+  in.n_pel_glob = c.n_pel_glob;
+  in.n_eaten_glob = c.n_eaten_glob;
+  in.seq_next = c.seq_next;
+  in.stat3 = c.stat[3];
+  in.stat5 = c.stat[5];
+  in.ctr_pellet = c.ctr_pellet;
+  return in;
+}
+__device__ __forceinline__ SpawnIn spawn_in_rest(const ArenaCtl &c) {
+  SpawnIn in{};
+  in.n_vir = c.n_vir;
+  in.seq_next = c.seq_next;
+  in.tick = c.tick;
+  in.ctr_virus = c.ctr_virus;
+  in.n_spawn_p = c.n_spawn_p;
+  return in;
+}
+__device__ __forceinline__ int spawn_counts_pel(const Dev &d, int a, int init, const SpawnIn &in);
+__device__ __forceinline__ int spawn_counts_rest(const Dev &d, int a, int init, int n_resp, int n_wait, const SpawnIn &in,
+                                                  int kp);
 __device__ __forceinline__ void spawn_counts(const Dev &d, int a, int init, int n_resp, int n_wait, const SpawnIn &in);
 // ---------------------------------------------------- closing pellet update
 // Pellets never move and only a few change per tick (eaten, spawned, converted
 // from blobs): the closing update (k_pel_update) rewrites only the bucket rows
-// those touch, each into its other home.  Step 1, by the arena's block of
-// k_spawn_plan after the spawn counts: this tick's pellet spawns are staged
+// those touch, each into its other home.  Step 1, by a block of the arena's after
+// the pellet spawn counts (untiled ticks: of k_pp_active's launch, a launch ahead
+// of the row blocks; tiled ticks: k_spawn_plan's): this tick's pellet spawns are staged
 // (spawnPellets, field.py:303-313) -- the first kSpawnAhead were drawn by
 // k_players' arena block already (spec_*) -- and the tick's pellet bookkeeping closes.
 __device__ void spawn_pellet_at(const Dev &d, int a, int j, double *px, double *py);
+// one thread: the bookkeeping words (after the staging: spawn_pellet_at reads n_pnew)
+__device__ __forceinline__ void pellet_close_words(ArenaCtl &c, int nconv, int nsp) {
+  c.pu_nconv = nconv;
+  c.pu_nsp = nsp;
+  c.pu_spec = nsp <= kSpawnAhead ? 1 : 0;
+  c.n_pnew = 0;
+  c.n_pel_eaten = 0;  // (n_pel: the rewritten rows add their change)
+}
 __device__ __forceinline__ void pellet_close_prep(const Dev &d, int a) {
   ArenaCtl &c = d.ctl[a];
   const int nconv = c.n_pnew, nsp = c.n_spawn_p;
@@ -4435,20 +4504,72 @@ __device__ __forceinline__ void pellet_close_prep(const Dev &d, int a) {
   if (!spec)  // into the staging list after the conversions (pn[nconv + j])
     for (int j = threadIdx.x; j < nsp; j += blockDim.x) spawn_pellet_at(d, a, j, nullptr, nullptr);
   __syncthreads();  // (spawn_pellet_at reads n_pnew)
-  if (threadIdx.x == 0) {
-    c.pu_nconv = nconv;
-    c.pu_nsp = nsp;
-    c.pu_spec = spec ? 1 : 0;
-    c.n_pnew = 0;
-    c.n_pel_eaten = 0;  // (n_pel: the rewritten rows add their change)
+  if (threadIdx.x == 0) pellet_close_words(c, nconv, nsp);
+}
+// k_pp_active (pp_active_own above), here for the spawn counts it closes.
+// close (untiled ticks; the tiled ones close in k_spawn_plan and k_pel_update):
+// behind the player blocks the grid holds two more kinds, which share no word
+// with them or with each other.
+//  - One block per arena closes the tick's pellet bookkeeping -- the pellet half
+//    of the spawn counts, then pellet_close_prep -- so the closing update's row
+//    blocks can run in the next launch, beside the pp pass.
+//  - One thread per player stores the FOV cache entry of a live player from
+//    the cells before the pp pass (player_fov), which changes only the few
+//    players it marks; k_spawn_plan's block stores those again.  rmax_cell is
+//    not fed here (the player waves read it): it bounds every live cell's
+//    radius since the cell grid's build.  (In the player waves themselves the
+//    FOV arithmetic was not hidden under the grid test's loads: +2.2 us.)
+__global__ void __launch_bounds__(256) k_pp_active(Dev d, int close) {
+  FLOOR(6);
+  PT_BEGIN(3);
+  const int nblocks = close ? (d.NP + 3) / 4 : (int)gridDim.x;
+  if ((int)blockIdx.x >= nblocks + d.A) {
+    const int gp = (blockIdx.x - nblocks - d.A) * 256 + threadIdx.x;
+    if (gp < d.NP && d.p_alive[gp]) fov_store(d, gp, player_fov(d, gp));
+    PT_MARK(3, 4);
+    return;
   }
+  if ((int)blockIdx.x >= nblocks) {
+    const int a = blockIdx.x - nblocks;
+    if (threadIdx.x == 0) (void)spawn_counts_pel(d, a, 0, spawn_in_pel(d.ctl[a]));
+    __syncthreads();
+    pellet_close_prep(d, a);
+    PT_MARK(3, 5);
+    return;
+  }
+  pp_active_own(d, nblocks PT_ARGS);
 }
 // pp (tick only): playerPlayerOverlap's serial pass first, by wave 0 of the
 // arena's block (its pending bitmap in the dynamic LDS)
-// close (tick only): then the closing pellet update's step 1 (pellet_close_prep)
+// close 1 (tiled ticks): then the closing pellet update's step 1 (pellet_close_prep);
+// k_pel_update follows
+// close 2 (untiled ticks: the tick's last launch; the pellet bookkeeping was
+// closed by k_food_commit's fold block): the grid's blocks after the arenas'
+// are the closing update's row blocks (pel_row_update, one per bucket row and
+// arena, on the first PU_T threads with the launch's dynamic LDS), which share
+// no word with the arena blocks -- they run beside the pp pass; the arena's
+// block then finishes spawnStuff itself: the player respawns, the virus
+// spawns, the FOV cache entries of the respawned players and of those the pp
+// pass marked (fov_mark; k_pp_active stored everybody's before the pass), the
+// observe epoch and the tick count.
+constexpr int PU_T = 256;  // threads of a row block (the first PU_T of a wider block: the others leave at once)
+struct PelRowLds;
+__device__ __forceinline__ void pel_row_update(const Dev &d, int a, int r, PelRowLds &L PT_PARAMS);
+__device__ __forceinline__ void spawn_virus(const Dev &d, int gi);
+__device__ __forceinline__ void spawn_player(const Dev &d, int gp, int j, int init, double *ox = nullptr,
+                                             double *oy = nullptr);
 __global__ void __launch_bounds__(1024) k_spawn_plan(Dev d, int init, int64_t *scr_k, int *scr_v, int pp,
                                                      int close) {
   FLOOR(7);
+  if (close == 2 && (int)blockIdx.x >= d.A) {
+    if (threadIdx.x >= PU_T) return;  // (left before any barrier: the row's barriers count the four waves that stay)
+    extern __shared__ __align__(16) unsigned char row_lds[];
+    PT_BEGIN(8);
+    const int rb = blockIdx.x - d.A, ra = rb / d.cols;
+    pel_row_update(d, ra, rb - ra * d.cols, *reinterpret_cast<PelRowLds *>(row_lds) PT_ARGS);
+    PT_MARK(8, 3);
+    return;
+  }
   __shared__ int sflag[1024];
   __shared__ int gcnt[SG_CAP + 1];
   PT_BEGIN(5);
@@ -4458,6 +4579,7 @@ __global__ void __launch_bounds__(1024) k_spawn_plan(Dev d, int init, int64_t *s
     __shared__ uint32_t s_odirty[OCC_DW];
     const bool defer = d.occ_words <= OCC_DW * 32;
     for (int i = threadIdx.x; i < OCC_DW; i += blockDim.x) s_odirty[i] = 0;
+    for (int i = threadIdx.x; i < FOVM_BITS / 32; i += blockDim.x) fov_marks()[i] = 0;
     __syncthreads();
     // (the barrier's workgroup release waits for wave 0's count atomics; the
     // rebuild reads the counts at device scope, from L2)
@@ -4551,7 +4673,11 @@ __global__ void __launch_bounds__(1024) k_spawn_plan(Dev d, int init, int64_t *s
   // what k_pel_update's player threads read
   int n_resp = 0, n_wait = 0;
   SpawnIn sin{};
-  if (tid == 0) sin = spawn_in(c);  // (spawn_counts' fields: their round overlaps the partition's)
+  // (spawn_counts' fields: their round overlaps the partition's; close 2: only the
+  // half that is left, none of the words this launch's row blocks change)
+  if (tid == 0) sin = close == 2 ? spawn_in_rest(c) : spawn_in(c);
+  uint32_t ob_ep = 0;  // (the observe epoch rides the same round: its bump below is then a store)
+  if (tid == 0 && close == 2 && a == 0) ob_ep = *d.ob_epoch;
   if (!init) {
     const int nd = c.n_dead;
     int *dl = d.dead + (size_t)a * d.B, *rl = d.resp_slot + (size_t)a * d.B;
@@ -4568,16 +4694,57 @@ __global__ void __launch_bounds__(1024) k_spawn_plan(Dev d, int init, int64_t *s
       const int rw = block_rank(i < nd && !rsp, sflag, &tw);  // (every read of this chunk is done)
       if (i < nd) rl[p] = rsp ? n_resp + rr : -1;
       if (i < nd && !rsp) dl[n_wait + rw] = p;  // (n_wait + rw <= i: never ahead of an unread entry)
+      if (close == 2 && i < nd && rsp) fov_mark(p);  // (respawns below: its FOV cache entry with it)
       n_resp += tr;
       n_wait += tw;
     }
   }
-  if (tid == 0) spawn_counts(d, a, init, n_resp, n_wait, sin);
+  __shared__ int s_kv;
+  if (tid == 0) {
+    if (close == 2) {
+      s_kv = spawn_counts_rest(d, a, init, n_resp, n_wait, sin, sin.n_spawn_p);
+      c.tick = sin.tick + 1;  // (the tick's last launch; nothing in it reads the word from here on)
+      if (a == 0) *d.ob_epoch = 0x80000000u | ((ob_ep + 1) & 0x7FFFFFFFu);  // (as fov_cache_thread's)
+    } else {
+      spawn_counts(d, a, init, n_resp, n_wait, sin);
+    }
+  }
   __syncthreads();
   PT_MARK(5, 4);
-  if (close) {
+  if (close == 1) {
     __syncthreads();
     pellet_close_prep(d, a);
+  }
+  if (close == 2) {
+    // the rest of spawnStuff on the world the pp pass left (occupancy rebuilt
+    // above): one thread per virus spawn, one per marked player -- a dead one
+    // with a respawn slot respawns (spawn_player), then its thread stores the
+    // FOV cache entry of the end-of-tick state (as respawn_fov_thread: the
+    // respawn and its entry are one thread's work)
+    for (int j = tid; j < s_kv; j += T) spawn_virus(d, a * d.Vcap + j);
+    for (int p = tid; p < d.B; p += T) {
+      if (!fov_marked(p)) continue;
+      const int gp = a * d.B + p;
+      const bool alive = d.p_alive[gp];
+      const int j = d.resp_slot[gp];  // (one round with the liveness; only a dead player's is read)
+      Fov f;
+      if (alive) {
+        f = player_fov(d, gp);
+      } else {
+        if (j < 0) continue;  // (eaten whole by this tick's pp pass, or waiting)
+        double x, y;
+        spawn_player(d, gp, j, 0, &x, &y);
+        // (the one cell it has now, from the registers: no load behind its stores)
+        f = player_fov_of(d, 1, [&](int, double &cx, double &cy, double &cm, double &cr) {
+          cx = x;
+          cy = y;
+          cm = kStartMass;
+          cr = radius_of(kStartMass);
+        });
+      }
+      fov_store(d, gp, f);
+      if (f.rmax > 0) atomic_max_pos(&c.rmax_cell, f.rmax);
+    }
   }
   PT_MARK(5, 5);
 }
@@ -4588,11 +4755,16 @@ __global__ void __launch_bounds__(1024) k_spawn_plan(Dev d, int init, int64_t *s
 // and the stores (read-modify-writes of the struct in place cost a round each: a
 // load after a store to the same struct cannot move above it)
 __device__ __forceinline__ void spawn_counts(const Dev &d, int a, int init, int n_resp, int n_wait, const SpawnIn &in) {
+  const int kp = spawn_counts_pel(d, a, init, in);
+  (void)spawn_counts_rest(d, a, init, n_resp, n_wait, in, kp);
+}
+// the pellet half (spawnPellets); returns the spawn count
+__device__ __forceinline__ int spawn_counts_pel(const Dev &d, int a, int init, const SpawnIn &in) {
   ArenaCtl &c = d.ctl[a];
   const int n_pel = in.n_pel, n_pel_eaten = in.n_pel_eaten, n_pnew = in.n_pnew;
-  const int n_pel_glob = in.n_pel_glob, n_eaten_glob = in.n_eaten_glob, n_vir = in.n_vir;
-  const int64_t seq_next = in.seq_next, tick = in.tick, stat3 = in.stat3, stat5 = in.stat5;
-  const uint64_t ctr_pellet = in.ctr_pellet, ctr_virus = in.ctr_virus;
+  const int n_pel_glob = in.n_pel_glob, n_eaten_glob = in.n_eaten_glob;
+  const int64_t seq_next = in.seq_next, stat3 = in.stat3, stat5 = in.stat5;
+  const uint64_t ctr_pellet = in.ctr_pellet;
   uint32_t err = 0;
   // spawnPellets: while len(pellets) < maxCollectibleCount
   // (tiles: the global count -- every tile spawns the same global list and keeps what it holds)
@@ -4603,6 +4775,26 @@ __device__ __forceinline__ void spawn_counts(const Dev &d, int a, int init, int 
     err |= ERR_PELLET_CAP;
     kp = max(0, min(d.Pcap - alive_p, d.Pcap - n_pnew));
   }
+  if (err) set_err(d, a, err);
+  c.seq_base_spawn = seq_next;  // (spawn j's sequence number; viruses and players follow at + n_spawn_p (+ n_spawn_v))
+  c.ctr_pellet_base = ctr_pellet;
+  c.ctr_pellet = ctr_pellet + kp;
+  c.n_spawn_p = kp;
+  c.n_pel_glob = alive_p + kp;
+  if (!init) {  // diagnostics: pellets eaten / respawned this tick (whole arena)
+    c.stat[3] = stat3 + (d.tiled ? n_eaten_glob : n_pel_eaten);
+    c.stat[5] = stat5 + kp;
+  }
+  return kp;
+}
+// the rest (spawnViruses, spawnPlayers) and the tick's sequence numbers; kp: the pellet half's count
+__device__ __forceinline__ int spawn_counts_rest(const Dev &d, int a, int init, int n_resp, int n_wait, const SpawnIn &in,
+                                                  int kp) {
+  ArenaCtl &c = d.ctl[a];
+  const int n_vir = in.n_vir;
+  const int64_t seq_next = in.seq_next, tick = in.tick;
+  const uint64_t ctr_virus = in.ctr_virus;
+  uint32_t err = 0;
   // spawnViruses
   int kv = 0;
   if (d.virus_enabled && (double)n_vir < d.max_viruses) kv = (int)ceil(d.max_viruses) - n_vir;
@@ -4613,16 +4805,7 @@ __device__ __forceinline__ void spawn_counts(const Dev &d, int a, int init, int 
   // spawnPlayers: deadPlayers in order, respawnTime == 0 (init: every player, in order)
   const int np = init ? d.B : n_resp;
   c.dirty = 0;
-  if (err) c.err |= err;
-  c.seq_base_spawn = seq_next;
-  c.ctr_pellet_base = ctr_pellet;
-  c.ctr_pellet = ctr_pellet + kp;
-  c.n_spawn_p = kp;
-  c.n_pel_glob = alive_p + kp;
-  if (!init) {  // diagnostics: pellets eaten / respawned this tick (whole arena)
-    c.stat[3] = stat3 + (d.tiled ? n_eaten_glob : n_pel_eaten);
-    c.stat[5] = stat5 + kp;
-  }
+  if (err) set_err(d, a, err);
   c.ctr_virus_base = ctr_virus;
   c.ctr_virus = ctr_virus + kv;
   c.vir_base_spawn = n_vir;
@@ -4635,6 +4818,7 @@ __device__ __forceinline__ void spawn_counts(const Dev &d, int a, int init, int 
   c.n_spawn_pl = np;
   // (at initialize() players already own seqs 0..B-1)
   c.seq_next = seq_next + kp + kv + (init ? 0 : np);
+  return kv;
 }
 
 __global__ void k_pnew_commit(Dev d) {
@@ -4711,8 +4895,8 @@ __device__ __forceinline__ void spawn_virus(const Dev &d, int gi) {
   d.v_flags[o] = F_ALIVE;  // addVirus: not hashed until the next rebuild
 }
 __global__ void k_spawn_viruses(Dev d) { spawn_virus(d, GTID); }
-// player gp (= arena a's player p) spawns j-th in spawnPlayers' order
-__device__ __forceinline__ void spawn_player(const Dev &d, int gp, int j, int init) {
+// player gp (= arena a's player p) spawns j-th in spawnPlayers' order (its position also to *ox, *oy)
+__device__ __forceinline__ void spawn_player(const Dev &d, int gp, int j, int init, double *ox, double *oy) {
   const int a = gp / d.B, p = gp - a * d.B;
   ArenaCtl &c = d.ctl[a];
   const int NP = d.NP;
@@ -4743,6 +4927,10 @@ __device__ __forceinline__ void spawn_player(const Dev &d, int gp, int j, int in
   d.p_alive[gp] = 1;
   d.p_respawn[gp] = 0;
   if (!init) ev_push_at(d, a, c.tick_sp, PH_SPAWN, (uint64_t)j, 10, p, seq);
+  if (ox) {
+    *ox = x;
+    *oy = y;
+  }
 }
 __global__ void k_spawn_players(Dev d, int init) {  // Field.initialize: every player, in order
   const int gp = GTID;
@@ -4787,7 +4975,7 @@ __device__ __forceinline__ int block_excl1(int v, int *wsum, int &total) {
   __syncthreads();
   int before = 0;
   total = 0;
-  for (int k = 0; k < (int)(blockDim.x >> 6); k++) {
+  for (int k = 0; k < PU_T >> 6; k++) {
     before += k < w ? wsum[k] : 0;
     total += wsum[k];
   }
@@ -4798,7 +4986,7 @@ __device__ __forceinline__ int block_excl1(int v, int *wsum, int &total) {
 // in thread order, and p[0..3], four per thread (thread t holds items 4t .. 4t+3);
 // tp = p's total.  wsum: 8 entries.
 __device__ __forceinline__ void block_scan_pair(int &a, int64_t *p, int64_t *wsum, int64_t &tp) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = blockDim.x >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = PU_T >> 6;
   const int sa = a;
   const int64_t sp = p[0] + p[1] + p[2] + p[3];
   int ia = sa;
@@ -4836,20 +5024,41 @@ __device__ __forceinline__ void block_scan_pair(int &a, int64_t *p, int64_t *wsu
 constexpr int PU_JREC = 64;  // joining records per row kept whole in LDS (beyond: loaded again)
 constexpr int PU_LDS = 512;  // row slots whose records the update parks in LDS (longer rows: two rounds)
 constexpr int PU_K = PU_LDS / 256;  // consecutive slots per thread
-__device__ void pel_row_update(const Dev &d, int a, int r PT_PARAMS) {
-  __shared__ int s_flag[3];
-  __shared__ int s_sj[PU_ROW_STG];
-  __shared__ short s_sbx[PU_ROW_STG];
-  __shared__ PelRec s_jrec[PU_JREC];
-  __shared__ int s_jcol[PU_JREC];
-  __shared__ PelRec s_rec[PU_LDS];
-  __shared__ int s_rcol[PU_LDS];
-  __shared__ int s_ost[kPelRowCols + 1];  // the row's old bucket starts (absolute slots)
-  __shared__ int s_live[kPelRowCols], s_stc[kPelRowCols];  // per bucket: survivors, joining records
-  __shared__ int s_lpre[kPelRowCols], s_nofs[kPelRowCols];  // survivors before the bucket; its new start - row base
-  __shared__ int wsum[4];
-  __shared__ int64_t wsum2[8];
-  __shared__ short s_slotb[PU_LDS];  // a parked suffix slot's old bucket
+// a row block's LDS: k_pel_update's own; in k_spawn_plan's launch, whose blocks
+// carry the pp pass's static LDS, the launch's dynamic LDS (which a row block
+// does not use otherwise), so the row blocks add nothing to the static size
+struct PelRowLds {
+  PelRec s_jrec[PU_JREC];
+  PelRec s_rec[PU_LDS];
+  int64_t wsum2[8];
+  int s_flag[3];
+  int s_sj[PU_ROW_STG];
+  int s_jcol[PU_JREC];
+  int s_rcol[PU_LDS];
+  int s_ost[kPelRowCols + 1];  // the row's old bucket starts (absolute slots)
+  int s_live[kPelRowCols], s_stc[kPelRowCols];  // per bucket: survivors, joining records
+  int s_lpre[kPelRowCols], s_nofs[kPelRowCols];  // survivors before the bucket; its new start - row base
+  int wsum[4];
+  short s_sbx[PU_ROW_STG];
+  short s_slotb[PU_LDS];  // a parked suffix slot's old bucket
+};
+// (the first PU_T threads of the block, all of them; any others have left it)
+__device__ __forceinline__ void pel_row_update(const Dev &d, int a, int r, PelRowLds &L PT_PARAMS) {
+  auto &s_flag = L.s_flag;
+  auto &s_sj = L.s_sj;
+  auto &s_sbx = L.s_sbx;
+  auto &s_jrec = L.s_jrec;
+  auto &s_jcol = L.s_jcol;
+  auto &s_rec = L.s_rec;
+  auto &s_rcol = L.s_rcol;
+  auto &s_ost = L.s_ost;
+  auto &s_live = L.s_live;
+  auto &s_stc = L.s_stc;
+  auto &s_lpre = L.s_lpre;
+  auto &s_nofs = L.s_nofs;
+  auto &wsum = L.wsum;
+  auto &wsum2 = L.wsum2;
+  auto &s_slotb = L.s_slotb;
   const int tid = threadIdx.x, C = d.cols;
   ArenaCtl &c = d.ctl[a];
   const int nconv = c.pu_nconv, nst = nconv + c.pu_nsp, spec = c.pu_spec;
@@ -4864,7 +5073,7 @@ __device__ void pel_row_update(const Dev &d, int a, int r PT_PARAMS) {
     s_flag[0] = s_flag[1] = 0;
     s_flag[2] = INT_MAX;  // the row's first changed slot
   }
-  for (int bx = tid; bx <= C; bx += blockDim.x) {
+  for (int bx = tid; bx <= C; bx += PU_T) {
     s_ost[bx] = e0[bx];
     if (bx < C) s_stc[bx] = 0;
   }
@@ -4913,9 +5122,9 @@ __device__ void pel_row_update(const Dev &d, int a, int r PT_PARAMS) {
     }
   };
   kill(kill0);
-  for (int t = tid + blockDim.x; t < nk; t += blockDim.x) kill(kl[t]);
+  for (int t = tid + PU_T; t < nk; t += PU_T) kill(kl[t]);
   if (bx0 >= 0) stage(tid, bx0, rec0, col0);
-  for (int j = tid + blockDim.x; j < nst; j += blockDim.x) {
+  for (int j = tid + PU_T; j < nst; j += PU_T) {
     PelRec rec;
     int col;
     const int bx = staged(j, rec, col);
@@ -4931,12 +5140,12 @@ __device__ void pel_row_update(const Dev &d, int a, int r PT_PARAMS) {
   const bool over = ns_all > PU_ROW_STG;  // (uniform)
   const int ns = over ? 0 : ns_all;
   // a join goes behind its bucket's survivors: the row changes from that bucket's old end
-  for (int k = tid; k < ns; k += blockDim.x) {
+  for (int k = tid; k < ns; k += PU_T) {
     atomicAdd(&s_stc[s_sbx[k]], 1);
     atomicMin(&s_flag[2], s_ost[s_sbx[k] + 1]);
   }
   if (over) {
-    for (int j = tid; j < nst; j += blockDim.x) {
+    for (int j = tid; j < nst; j += PU_T) {
       PelRec rec;
       int col;
       const int bx = staged(j, rec, col);
@@ -5003,7 +5212,7 @@ __device__ void pel_row_update(const Dev &d, int a, int r PT_PARAMS) {
     }
     // meanwhile, with LDS alone: every suffix slot's old bucket (scattered by
     // bucket: buckets are a few slots long), the survivors before f
-    for (int bx = tid; bx < C; bx += blockDim.x) {
+    for (int bx = tid; bx < C; bx += PU_T) {
       const int s0 = s_ost[bx], s1 = s_ost[bx + 1];
       for (int i = max(s0, f); i < s1; i++) s_slotb[i - f] = (short)bx;
       s_live[bx] = max(0, min(s1, f) - s0);
@@ -5056,15 +5265,15 @@ __device__ void pel_row_update(const Dev &d, int a, int r PT_PARAMS) {
         }
       }
   } else {  // (longer rows: the same in chunks of 256 slots, the records loaded after the count)
-    for (int bx = tid; bx < C; bx += blockDim.x) s_live[bx] = 0;
+    for (int bx = tid; bx < C; bx += PU_T) s_live[bx] = 0;
     __syncthreads();
-    for (int i = lo + tid; i < hi; i += blockDim.x)
+    for (int i = lo + tid; i < hi; i += PU_T)
       if (!d.pel_dead[D0 + i]) atomicAdd(&s_live[bucket_of(i)], 1);
     __syncthreads();
     total = bucket_scans();
     // survivors: slot i of bucket bx -> nb + new start + (survivors of bx before i)
     int carry = 0;
-    for (int c0 = lo; c0 < hi; c0 += blockDim.x) {
+    for (int c0 = lo; c0 < hi; c0 += PU_T) {
       const int i = c0 + tid;
       bool live = false;
       if (i < hi) live = !d.pel_dead[D0 + i];
@@ -5086,7 +5295,7 @@ __device__ void pel_row_update(const Dev &d, int a, int r PT_PARAMS) {
     }
   }
   // joining records: behind the bucket's survivors, in staging order
-  for (int k = tid; k < ns; k += blockDim.x) {
+  for (int k = tid; k < ns; k += PU_T) {
     const int j = s_sj[k], bx = s_sbx[k];
     int rk = 0;
     for (int q = 0; q < ns; q++) rk += s_sbx[q] == bx && s_sj[q] < j;
@@ -5113,8 +5322,8 @@ __device__ void pel_row_update(const Dev &d, int a, int r PT_PARAMS) {
     // (s_lpre, free once the survivors are placed) + its bucket mates earlier in
     // its chunk (s_sbx, free once the list is dropped)
     __syncthreads();
-    for (int bx = tid; bx < C; bx += blockDim.x) s_lpre[bx] = 0;
-    for (int c0 = 0; c0 < nst; c0 += blockDim.x) {
+    for (int bx = tid; bx < C; bx += PU_T) s_lpre[bx] = 0;
+    for (int c0 = 0; c0 < nst; c0 += PU_T) {
       const int j = c0 + tid;
       PelRec rec;
       int col = -1, bx = -1;
@@ -5135,7 +5344,7 @@ __device__ void pel_row_update(const Dev &d, int a, int r PT_PARAMS) {
       __syncthreads();
     }
   }
-  for (int bx = tid; bx < C; bx += blockDim.x) {
+  for (int bx = tid; bx < C; bx += PU_T) {
     const int st = nb + min(s_nofs[bx], d.PR);
     if (st != s_ost[bx]) e0[bx] = st;  // (in place: the starts up to f's bucket stay)
   }
@@ -5160,7 +5369,8 @@ __global__ void __launch_bounds__(256) k_pel_update(Dev d, int nbF) {
   }
   const int a = blockIdx.x / d.cols, r = blockIdx.x - a * d.cols;
   if (r == 0 && threadIdx.x == 0) d.ctl[a].tick += 1;  // (nothing in this launch reads it)
-  pel_row_update(d, a, r PT_ARGS);
+  __shared__ PelRowLds s_rows;
+  pel_row_update(d, a, r, s_rows PT_ARGS);
   PT_MARK(8, 3);
 }
 
@@ -5289,14 +5499,18 @@ void launch_tick_pre(const Dev &d, hipStream_t s, int64_t *scr_k, int *scr_v, co
   else
     hipLaunchKernelGGL(k_merge_vb, dim3(nblk(d.NP, 256) + d.A), dim3(256), 0, s, d, scr_k, scr_v, 0);
 }
+static size_t pp_lds_bytes(const Dev &d) {  // k_spawn_plan's pending bitmaps (one per parallel pp group wave) and player owners
+  return sizeof(uint32_t) * ((d.B + 31) / 32) * PPG_WAVES + (d.B <= PP_LOWN_MAX ? sizeof(int) * d.B : 0);
+}
 // the phases after it: playerPlayerOverlap, spawnStuff, closing rebuild (field.py:233-313)
+// (the tiled ticks' sequence: several eat passes precede it, and the global pellet
+// counts arrive by exchange, so the pellet bookkeeping closes in k_spawn_plan and
+// the closing update is a launch of its own)
 void launch_tick_post(const Dev &d, hipStream_t s, int64_t *scr_k, int *scr_v) {
-  hipLaunchKernelGGL(k_pp_active, dim3(nblk(d.NP, 4)), dim3(256), 0, s, d);
+  hipLaunchKernelGGL(k_pp_active, dim3(nblk(d.NP, 4)), dim3(256), 0, s, d, 0);
   // playerPlayerOverlap's serial pass + spawnStuff's plan + the end-of-tick virus
   // grid + the closing pellet update's sorted kill / join lists (and the pellet spawns)
-  hipLaunchKernelGGL(k_spawn_plan, dim3(d.A), dim3(1024),
-                     sizeof(uint32_t) * ((d.B + 31) / 32) * PPG_WAVES + (d.B <= PP_LOWN_MAX ? sizeof(int) * d.B : 0), s, d, 0,
-                     scr_k, scr_v, 1, 1);  // (pending bitmaps: one per parallel pp group wave)
+  hipLaunchKernelGGL(k_spawn_plan, dim3(d.A), dim3(1024), pp_lds_bytes(d), s, d, 0, scr_k, scr_v, 1, 1);
   // the closing pellet update (survivors U joining staged records -> the new
   // current buffer) + the rest of spawnStuff as extra blocks: player respawns
   // with the FOV cache, virus spawns (fused into the pellet threads the FOV
@@ -5309,8 +5523,21 @@ void launch_score_sample(const Dev &d, hipStream_t s);
 void launch_tick(const Dev &d, hipStream_t s, int rounds, int64_t *scr_k, int *scr_v, const RandomPolicy *rp) {
   if (d.sc) launch_score_sample(d, s);  // AIGAR_FLAG_SCORE: the mass sample of Model.update's start (bot.py:253)
   launch_tick_pre(d, s, scr_k, scr_v, rp);
+  if (d.tiled) {
+    launch_food(d, s, rounds, Scratch{scr_k, scr_v}, 0, 1);
+    launch_tick_post(d, s, scr_k, scr_v);
+    return;
+  }
+  // the untiled tick ends in two launches: behind k_pp_active's player blocks one
+  // block per arena closes the pellet bookkeeping (final since the eat phase) and
+  // one thread per player stores the FOV cache; k_spawn_plan's grid then holds the closing
+  // update's row blocks behind the arena blocks (the longest: first), which finish
+  // spawnStuff themselves.  A row block's LDS is the launch's dynamic LDS, which
+  // the arena blocks need for the pp pass anyway: the larger of the two.
   launch_food(d, s, rounds, Scratch{scr_k, scr_v}, 0, 1);
-  launch_tick_post(d, s, scr_k, scr_v);
+  hipLaunchKernelGGL(k_pp_active, dim3(nblk(d.NP, 4) + d.A + nblk(d.NP, 256)), dim3(256), 0, s, d, 1);
+  hipLaunchKernelGGL(k_spawn_plan, dim3(d.A + d.A * d.cols), dim3(1024), std::max(pp_lds_bytes(d), sizeof(PelRowLds)),
+                     s, d, 0, scr_k, scr_v, 1, 2);
 }
 
 // ------------------------------------------------------------ C4 tile passes
