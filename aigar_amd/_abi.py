@@ -78,6 +78,19 @@ class NoiseParams(C.Structure):
                 ("theta", C.c_double), ("ou_mu", C.c_double), ("dt", C.c_double), ("seed", C.c_uint64)]
 
 
+NET_MAX_LAYERS, NET_MAX_UNITS, NET_MAX_IN = 5, 256, 16384  # aigar_net_params' bounds
+ACT_LINEAR, ACT_RELU, ACT_SIGMOID, ACT_ELU, ACT_TANH = 0, 1, 2, 3, 4  # (elu and tanh are refused)
+ACTIVATIONS = {"linear": ACT_LINEAR, "relu": ACT_RELU, "sigmoid": ACT_SIGMOID, "elu": ACT_ELU, "tanh": ACT_TANH}
+NET_HEAD_Q, NET_HEAD_ACTOR = 0, 1  # aigar_env_step_net's head
+NET_HEADS = {"q": NET_HEAD_Q, "actor": NET_HEAD_ACTOR}
+
+
+class NetParams(C.Structure):
+    """aigar_net_params (include/aigar.h): the learners' acting network (network.py:207-241)."""
+    _fields_ = [("n_layers", C.c_int32), ("n_in", C.c_int32), ("x_dtype", C.c_int32), ("hidden_act", C.c_int32),
+                ("out_act", C.c_int32), ("pad", C.c_int32), ("units", C.c_int32 * 8)]
+
+
 class RunParams(C.Structure):
     """aigar_run_params (include/aigar.h): the policy replayed inside aigar_run's step graph."""
     _fields_ = [("policy", C.c_int32), ("greedy_split", C.c_int32), ("p_split", C.c_double),

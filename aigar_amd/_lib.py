@@ -100,6 +100,12 @@ def load(build_if_missing=False):
         "aigar_noise_config": [vp, C.POINTER(_abi.NoiseParams)],
         "aigar_noise": [vp, vp, i32, vp, vp, i32, vp, vp, vp],
         "aigar_env_step_ac": [vp, vp, vp, vp, i32, i32, i32, C.POINTER(_abi.RewardParams), vp, vp, i32, vp],
+        "aigar_net_config": [vp, C.POINTER(_abi.NetParams)],
+        "aigar_net_set_weights": [vp, i32, vp, vp, i32],
+        "aigar_net_forward": [vp, vp, i32, i32, vp],
+        "aigar_net_output": [vp, vp],
+        "aigar_env_step_net": [vp, i32, vp, vp, i32, i32, i32, C.POINTER(_abi.RewardParams), vp, vp, i32, vp, vp, vp,
+                               i32],
         "aigar_exp_extra_get": [vp, vp, i32, vp, vp],
         "aigar_exp_extra_set": [vp, vp, vp, i32],
         "aigar_warnings": [vp, i32, C.POINTER(C.c_uint32)],
@@ -189,6 +195,7 @@ class Stepper:
         self.exp = None  # (state row shape, state dtype name, prioritized) while a replay memory is configured
         self.dec = None  # (n_out, q dtype name) while an action selection is configured
         self.noi = None  # (n_act, mu dtype name, Orn-Uhl) while an exploration noise is configured
+        self.net = None  # (n_in, units, state dtype name) while an acting network is configured
 
     def _chk(self, r):
         if r < 0:
@@ -612,6 +619,109 @@ class Stepper:
     def selftest_log(x):
         """Device log (glibc's, restated in aigar_math.h) for a host array."""
         return selftest_log(x)
+
+    # ---- the learners' acting network (include/aigar.h: aigar_net*)
+    def net_config(self, spec, x_dtype="float64"):
+        """The handle's acting network: spec is (n_in, units, hidden, out) -- the state
+        length, the outputs of every dense layer, and the activations by name or code
+        (aigar_amd.net.mlp_spec) -- x_dtype the dtype of the decision's states.  The weights
+        are zero until net_set_weights.  net_config(None) turns it off."""
+        if spec is None:
+            self._chk(self.L.aigar_net_config(self.h, None))
+            self.net = None
+            return
+        n_in, units, hidden, out = spec
+        units = [int(v) for v in units]
+        d = str(x_dtype).replace("torch.", "").replace("<class 'numpy.", "").replace("'>", "")
+        if d not in ("float64", "float32"):
+            raise ValueError("net_config: x_dtype must be float64 or float32, got %s" % (x_dtype,))
+        if len(units) > 8:
+            raise ValueError("net_config: %d layers, at most %d" % (len(units), _abi.NET_MAX_LAYERS))
+        code = lambda a: _abi.ACTIVATIONS[a] if isinstance(a, str) else int(a)
+        prm = _abi.NetParams(len(units), int(n_in), 0 if d == "float64" else 1, code(hidden), code(out), 0)
+        for i, v in enumerate(units):
+            prm.units[i] = v
+        self._chk(self.L.aigar_net_config(self.h, C.byref(prm)))
+        self.net = (int(n_in), tuple(units), d)
+
+    def _need_net(self, what):
+        if getattr(self, "net", None) is None:
+            raise RuntimeError("aigar: %s: no acting network is configured (net_config)" % what)
+        return self.net
+
+    def net_set_weights(self, weights):
+        """The trainer's weight push: weights is a list of (W [in, out], b [out]) per layer,
+        float32, numpy arrays or device tensors (stream-ordered; no re-capture)."""
+        n_in, units, _ = self._need_net("net_set_weights")
+        if len(weights) != len(units):
+            raise ValueError("net_set_weights: %d layers given, the network has %d" % (len(weights), len(units)))
+        for l, (W, b) in enumerate(weights):
+            shape = (units[l - 1] if l else n_in, units[l])
+            if isinstance(W, np.ndarray) or not hasattr(W, "data_ptr"):
+                W, b = np.ascontiguousarray(W, np.float32), np.ascontiguousarray(b, np.float32)
+            self._check_out(W, shape, ("float32",), "net_set_weights")
+            self._check_out(b, (shape[1],), ("float32",), "net_set_weights")
+            (wp, on), (bp, on_b) = _ptr(W), _ptr(b)
+            if on != on_b:
+                raise ValueError("net_set_weights: W and b both numpy arrays or both device tensors")
+            self._chk(self.L.aigar_net_set_weights(self.h, l, wp, bp, on))
+
+    def net_forward(self, x, out):
+        """The network alone on device tensors (aigar_net_forward): x [rows, n_in] float64 /
+        float32 -> out [rows, n_out] float64.  Liveness and roles are ignored; a row whose
+        first value is a NaN comes out NaN."""
+        n_in, units, _ = self._need_net("net_forward")
+        rows = int(x.shape[0])
+        self._check_dev(x, (rows, n_in), ("float64", "float32"), "net_forward")
+        self._check_dev(out, (rows, units[-1]), ("float64",), "net_forward")
+        self._chk(self.L.aigar_net_forward(self.h, C.c_void_p(x.data_ptr()), 0 if str(x.dtype) == "torch.float64" else 1,
+                                           rows, C.c_void_p(out.data_ptr())))
+
+    def net_output(self, out):
+        """A copy of the handle's output buffer (the last decision's Q values / mu) into the
+        device tensor out [NP, n_out] float64."""
+        _, units, _ = self._need_net("net_output")
+        self._check_dev(out, (self.NP, units[-1]), ("float64",), "net_output")
+        self._chk(self.L.aigar_net_output(self.h, C.c_void_p(out.data_ptr())))
+
+    def env_step_net(self, head, explore, reward, obs, idx=None, val=None, u=None, noisy=None, enable_split=True,
+                     skip=0, params=None, n_decisions=1):
+        """n_decisions whole decisions with the network in front (aigar_env_step_net), one
+        graph replay each: head "q" (explore [epsilon, temperature], u [NP, 3], idx / val as
+        env_step_q) or "actor" (explore [std], u [NP, 2, T, 2], noisy as env_step_ac).  obs
+        must hold the current states: the network reads it, the decision rewrites it."""
+        self._need_net("env_step_net")
+        hd = _abi.NET_HEADS[head] if isinstance(head, str) else int(head)
+        for t in (reward, obs):
+            if not getattr(t, "is_cuda", False) or not t.is_contiguous():
+                raise ValueError("env_step_net takes contiguous device tensors")
+        self._check_dev(reward, (self.NP,), ("float64",), "env_step_net")
+        self._check_out(obs, (self.NP, self.obs_len), ("float64", "float32"), "env_step_net")
+        up, T, ip, vp, np_ = None, 0, None, None, None
+        if hd == _abi.NET_HEAD_Q:
+            self._check_dev(explore, (2,), ("float64",), "env_step_net")
+            self._check_dev(idx, (self.NP,), ("int32",), "env_step_net")
+            self._check_dev(val, (self.NP,), ("float64",), "env_step_net")
+            ip, vp = C.c_void_p(idx.data_ptr()), C.c_void_p(val.data_ptr())
+            if u is not None:
+                self._check_dev(u, (self.NP, 3), ("float64",), "env_step_net")
+                up = C.c_void_p(u.data_ptr())
+        else:
+            self._check_dev(explore, (1,), ("float64",), "env_step_net")
+            if u is not None:
+                if u.dim() != 4 or not 1 <= int(u.shape[2]) <= _abi.NOISE_MAX_T:
+                    raise ValueError("env_step_net: u must be [NP, 2, T, 2] with T in 1..%d" % _abi.NOISE_MAX_T)
+                T = int(u.shape[2])
+                self._check_dev(u, (self.NP, 2, T, 2), ("float64",), "env_step_net")
+                up = C.c_void_p(u.data_ptr())
+            if noisy is not None:
+                self._check_dev(noisy, (self.NP, self.net[1][-1]), ("float64",), "env_step_net")
+                np_ = C.c_void_p(noisy.data_ptr())
+        prm = params if isinstance(params, _abi.RewardParams) else _abi.RewardParams.from_parameters(params)
+        dt = 0 if str(obs.dtype) == "torch.float64" else 1
+        self._chk(self.L.aigar_env_step_net(self.h, hd, C.c_void_p(explore.data_ptr()), up, T, int(bool(enable_split)),
+                                            int(skip), C.byref(prm), C.c_void_p(reward.data_ptr()),
+                                            C.c_void_p(obs.data_ptr()), dt, ip, vp, np_, int(n_decisions)))
 
     # ---- action selection of the Q-learning bots (include/aigar.h: aigar_decide*)
     def decide_config(self, actions, strategy="e-Greedy", q_dtype="float32", seed=0):

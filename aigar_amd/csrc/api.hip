@@ -54,6 +54,7 @@ using namespace aigar;
 #include "replay.inc"
 #include "decide.inc"
 #include "noise.inc"
+#include "net.inc"
 
 static thread_local std::string g_err;
 static int fail(const char *fmt, ...) {
@@ -223,6 +224,8 @@ struct aigar_handle {
     const double *exp_extra;  // the transitions' fifth field, [NP][exp_n_act] (null: invalid)
     int nT, pad;
     Noise noi;
+    // aigar_env_step_net: the acting network in front of either (n_layers 0: none)
+    Net net;
   } env_key{};
   // aigar_decide_config: the Q-learning bots' action selection (decide.inc; n_out 0: off)
   Decide dec{};
@@ -230,6 +233,10 @@ struct aigar_handle {
   // aigar_noise_config: the actor-critic learners' exploration noise (noise.inc; n_act 0: off)
   Noise noi{};
   std::vector<void *> noi_allocs;
+  // aigar_net_config: the learners' acting network (net.inc; n_layers 0: off)
+  Net net{};
+  std::vector<void *> net_allocs;
+  float *net_stage = nullptr;  // aigar_net_set_weights' staging of host weights (one of net_allocs)
   // aigar_exp_config: the learners' replay memory (replay.inc; cap 0: off)
   Exp exp;
   std::vector<void *> exp_allocs;
@@ -301,6 +308,10 @@ static void free_all(aigar_handle *h) {
   for (void *p : h->noi_allocs) (void)hipFree(p);
   h->noi_allocs.clear();
   h->noi = Noise{};
+  for (void *p : h->net_allocs) (void)hipFree(p);
+  h->net_allocs.clear();
+  h->net = Net{};
+  h->net_stage = nullptr;
   if (h->d_exp_off) (void)hipFree(h->d_exp_off);
   h->d_exp_off = nullptr;
   h->exp = Exp{};
@@ -1317,7 +1328,8 @@ static void launch_env_decision(aigar_handle *h, hipStream_t s, const aigar_hand
 // part, then the replay of its graph (k.q: the selection's kernel in front, decide.inc;
 // k.mu: the noise's, noise.inc).
 static int env_step_keyed(aigar_handle *h, aigar_handle::EnvKey &k, int enable_split, int skip,
-                          const aigar_reward_params *p, double *reward_out, void *obs_out, int dtype) {
+                          const aigar_reward_params *p, double *reward_out, void *obs_out, int dtype,
+                          int n_decisions = 1) {
   if (skip < 0) return fail("env_step: skip < 0");
   if (dtype != 0 && dtype != 1) return fail("dtype must be 0 (float64) or 1 (float32)");
   HIPCHK(hipSetDevice(h->cfg.device));
@@ -1344,13 +1356,14 @@ static int env_step_keyed(aigar_handle *h, aigar_handle::EnvKey &k, int enable_s
   if (h->d.flags & AIGAR_FLAG_EVENTS)  // the event log holds the window's ticks
     hipLaunchKernelGGL(k_step_begin, dim3((h->d.A + 63) / 64), dim3(64), 0, h->stream, h->d);
   auto launch = [&](hipStream_t cs) {
+    if (k.net.n_layers) launch_net(cs, k.net, k.obs, h->d.NP, k.net.y, h->d.p_alive, h->d.p_role);
     if (k.q) launch_decide(h->d, cs, k.dec, k.q, k.explore, k.u, k.idx_out, k.val_out, k.dec.act);
     if (k.mu)
       launch_noise(h->d, cs, k.noi, k.mu, h->d.NP, 1, k.nstd, k.nu, k.nT, nullptr, k.noisy, nullptr);
     launch_env_decision(h, cs, k);
   };
   if (!h->use_graph) {
-    launch(h->stream);
+    for (int i = 0; i < n_decisions; i++) launch(h->stream);
   } else {
     if (!h->env_graph || memcmp(&h->env_key, &k, sizeof k) != 0) {
       if (h->env_graph) (void)hipGraphExecDestroy(h->env_graph);
@@ -1359,7 +1372,7 @@ static int env_step_keyed(aigar_handle *h, aigar_handle::EnvKey &k, int enable_s
       h->env_key = k;
     }
     Mark m(h, "env_step");
-    HIPCHK(hipGraphLaunch(h->env_graph, h->stream));
+    for (int i = 0; i < n_decisions; i++) HIPCHK(hipGraphLaunch(h->env_graph, h->stream));
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -1552,6 +1565,189 @@ extern "C" int aigar_env_step_ac(aigar_handle *h, const void *mu, const double *
   k.exp_n_act = h->noi.n_act;
   k.exp_extra = h->noi.store_raw ? h->noi.raw : nullptr;
   return env_step_keyed(h, k, enable_split, skip, p, reward_out, obs_out, dtype);
+}
+
+// ------------------------------------------------------------ acting network
+static void net_free(aigar_handle *h) {
+  for (void *p : h->net_allocs) (void)hipFree(p);
+  h->net_allocs.clear();
+  h->net = Net{};
+  h->net_stage = nullptr;
+}
+static int need_net(aigar_handle *h, const char *who) {
+  if (!h) return fail("null handle");
+  if (!h->net.n_layers) return fail("%s: no acting network is configured (aigar_net_config)", who);
+  return 0;
+}
+static const char *net_act_name(int a) {
+  switch (a) {
+    case AIGAR_ACT_LINEAR: return "linear";
+    case AIGAR_ACT_RELU: return "relu";
+    case AIGAR_ACT_SIGMOID: return "sigmoid";
+    case AIGAR_ACT_ELU: return "elu";
+    case AIGAR_ACT_TANH: return "tanh";
+  }
+  return "unknown";
+}
+
+extern "C" int aigar_net_config(aigar_handle *h, const aigar_net_params *p) {
+  if (p) {  // (before the handle: a bad set has its own message)
+    if (p->n_layers < 1 || p->n_layers > kNetMaxLayers)
+      return fail("net_config: n_layers = %d is outside 1..%d", p->n_layers, kNetMaxLayers);
+    if (p->n_in < 1 || p->n_in > kNetMaxIn) return fail("net_config: n_in = %d is outside 1..%d", p->n_in, kNetMaxIn);
+    for (int l = 0; l < p->n_layers; l++)
+      if (p->units[l] < 1 || p->units[l] > kNetMaxUnits)
+        return fail("net_config: layer %d has %d units, outside 1..%d", l, p->units[l], kNetMaxUnits);
+    if (p->x_dtype != 0 && p->x_dtype != 1) return fail("net_config: x_dtype must be 0 (float64) or 1 (float32)");
+    if (p->hidden_act != AIGAR_ACT_RELU && p->hidden_act != AIGAR_ACT_LINEAR)
+      return fail("net_config: hidden activation %d (%s) is not supported: relu or linear", p->hidden_act,
+                  net_act_name(p->hidden_act));
+    if (p->out_act != AIGAR_ACT_LINEAR && p->out_act != AIGAR_ACT_SIGMOID)
+      return fail("net_config: output activation %d (%s) is not supported: linear or sigmoid", p->out_act,
+                  net_act_name(p->out_act));
+  }
+  if (!h) return fail("null handle");
+  if (p && h->d.tiled) return fail("net_config: a tiled handle has no acting network");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));  // (no replay of the graph is pending)
+  if (h->env_graph) (void)hipGraphExecDestroy(h->env_graph);
+  h->env_graph = nullptr;
+  net_free(h);
+  if (!p) return 0;
+  Net c{};
+  c.n_layers = p->n_layers;
+  c.x_dtype = p->x_dtype;
+  c.hid_act = p->hidden_act;
+  c.out_act = p->out_act;
+  size_t stage = 0;
+  auto alloc = [&](size_t bytes) -> void * {
+    void *m = nullptr;
+    if (hipMalloc(&m, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+    h->net_allocs.push_back(m);
+    (void)hipMemsetAsync(m, 0, bytes, h->stream);
+    return m;
+  };
+  bool ok = true;
+  for (int l = 0; l < c.n_layers && ok; l++) {
+    c.in[l] = l ? p->units[l - 1] : p->n_in;
+    c.out[l] = p->units[l];
+    const size_t ip = net_in_pad(c.in[l]), op = net_out_pad(c.out[l]);
+    c.w[l] = (float *)alloc(ip * op * sizeof(float));
+    c.b[l] = (float *)alloc(op * sizeof(float));
+    ok = c.w[l] && c.b[l];
+    stage = std::max(stage, (size_t)c.in[l] * c.out[l] + c.out[l]);
+  }
+  if (ok) ok = (c.y = (double *)alloc((size_t)h->d.NP * c.out[c.n_layers - 1] * sizeof(double))) != nullptr;
+  if (ok) ok = (h->net_stage = (float *)alloc(stage * sizeof(float))) != nullptr;
+  if (!ok) {
+    net_free(h);
+    return fail("net_config: out of device memory");
+  }
+  HIPCHK(hipGetLastError());
+  h->net = c;
+  return 0;
+}
+
+extern "C" int aigar_net_set_weights(aigar_handle *h, int layer, const float *W, const float *b, int on_device) {
+  if (need_net(h, "net_set_weights")) return -1;
+  const Net &c = h->net;
+  if (layer < 0 || layer >= c.n_layers) return fail("net_set_weights: layer %d is outside 0..%d", layer, c.n_layers - 1);
+  if (!W || !b) return fail("net_set_weights: null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const int in = c.in[layer], out = c.out[layer];
+  const size_t nw = (size_t)in * out;
+  if (!on_device) {
+    HIPCHK(hipMemcpyAsync(h->net_stage, W, nw * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->net_stage + nw, b, (size_t)out * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    W = h->net_stage;
+    b = h->net_stage + nw;
+  }
+  const int ip = net_in_pad(in), op = net_out_pad(out);
+  const size_t n = (size_t)ip * op;
+  hipLaunchKernelGGL(k_net_pack, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, h->stream, W, b,
+                     c.w[layer], c.b[layer], in, out, ip, op);
+  HIPCHK(hipGetLastError());
+  if (!on_device) HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's arrays are read, the staging is free)
+  return 0;
+}
+
+extern "C" int aigar_net_forward(aigar_handle *h, const void *x, int x_dtype, int rows, double *out) {
+  if (need_net(h, "net_forward")) return -1;
+  if (!x || !out) return fail("net_forward: null argument");
+  if (x_dtype != 0 && x_dtype != 1) return fail("net_forward: x_dtype must be 0 (float64) or 1 (float32)");
+  if (rows < 1 || rows > (1 << 30)) return fail("net_forward: rows = %d is outside 1..2^30", rows);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  Net c = h->net;
+  c.x_dtype = x_dtype;
+  launch_net(h->stream, c, x, rows, out, nullptr, nullptr);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int aigar_net_output(aigar_handle *h, double *out) {
+  if (need_net(h, "net_output")) return -1;
+  if (!out) return fail("net_output: null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const size_t bytes = (size_t)h->d.NP * h->net.out[h->net.n_layers - 1] * sizeof(double);
+  HIPCHK(hipMemcpyAsync(out, h->net.y, bytes, hipMemcpyDeviceToDevice, h->stream));
+  return 0;
+}
+
+extern "C" int aigar_env_step_net(aigar_handle *h, int head, const double *explore, const double *u, int T,
+                                  int enable_split, int skip, const aigar_reward_params *p, double *reward_out,
+                                  void *obs_out, int dtype, int32_t *idx_out, double *val_out, double *noisy_out,
+                                  int n_decisions) {
+  if (need_net(h, "env_step_net")) return -1;
+  if (head != AIGAR_NET_HEAD_Q && head != AIGAR_NET_HEAD_ACTOR)
+    return fail("env_step_net: head must be 0 (Q) or 1 (actor)");
+  if (!explore || !p || !reward_out || !obs_out) return fail("env_step_net: null argument");
+  if (n_decisions < 1) return fail("env_step_net: n_decisions = %d is below 1", n_decisions);
+  const Net &c = h->net;
+  const int n_out = c.out[c.n_layers - 1];
+  if (h->pix.side) return fail("env_step_net: the acting network takes no pixel state");
+  if (c.in[0] != h->d.L)
+    return fail("env_step_net: the network has %d inputs, the state %d values", c.in[0], h->d.L);
+  if (dtype != c.x_dtype) return fail("env_step_net: dtype %d differs from the network's x_dtype %d", dtype, c.x_dtype);
+  aigar_handle::EnvKey k{};
+  k.net = c;
+  if (head == AIGAR_NET_HEAD_Q) {
+    if (need_dec(h, "env_step_net")) return -1;
+    if (h->dec.q_dtype != 0) return fail("env_step_net: the action selection's q_dtype must be 0 (float64)");
+    if (h->dec.n_out != n_out)
+      return fail("env_step_net: the network has %d outputs, the action selection %d", n_out, h->dec.n_out);
+    if (!idx_out || !val_out) return fail("env_step_net: null argument");
+    k.act = h->dec.act;
+    k.n_act = 4;
+    k.q = c.y;
+    k.explore = explore;
+    k.u = u;
+    k.idx_out = idx_out;
+    k.val_out = val_out;
+    k.dec = h->dec;
+    k.exp_act = h->dec.idx;
+    k.exp_n_act = 1;
+  } else {
+    if (need_noi(h, "env_step_net")) return -1;
+    if (h->noi.mu_dtype != 0) return fail("env_step_net: the exploration noise's mu_dtype must be 0 (float64)");
+    if (h->noi.n_act != n_out)
+      return fail("env_step_net: the network has %d outputs, the exploration noise n_act = %d", n_out, h->noi.n_act);
+    if (u && (T < 1 || T > kNoiseMaxT)) return fail("env_step_net: T = %d is outside 1..%d", T, kNoiseMaxT);
+    k.act = h->noi.act;
+    k.n_act = h->noi.n_act;
+    k.mu = c.y;
+    k.nstd = explore;
+    k.nu = u;
+    k.nT = u ? T : kNoiseOwnT;
+    k.noisy = noisy_out;
+    k.noi = h->noi;
+    k.exp_act = h->noi.act;
+    k.exp_n_act = h->noi.n_act;
+    k.exp_extra = h->noi.store_raw ? h->noi.raw : nullptr;
+  }
+  return env_step_keyed(h, k, enable_split, skip, p, reward_out, obs_out, dtype, n_decisions);
 }
 
 extern "C" int aigar_warnings(aigar_handle *h, int arena, uint32_t *out) {

@@ -81,12 +81,25 @@ the best sampled action back (replay_buffer.py update_dones); `sample_extra(idx)
 `continuous=True` reads NOISE_TYPE, ORN_UHL_THETA / MU / DT, GAUSSIAN_NOISE and ALGORITHM from
 `parameters`; a dict (noise, theta, mu, dt, std, store_raw, seed) overrides them.  It excludes
 `discrete=` and is never switched on by `parameters` alone.
+
+The acting network (`network=True` or a spec, with `discrete=` or `continuous=`):
+the learner's acting MLP runs on the device in front of the selection or the noise, inside the
+decision's graph, so a decision needs nothing from the host: `step_net()` is `step_q(q_network(obs))`
+or `step_ac(actor(obs))` with the network evaluated by the device from `obs`, the buffer the last
+decision (or `reset` / `observe`) left the states in; `collect(n)` is n such decisions back to back,
+split only where an episode ends; `set_weights(weights)` is the trainer's push (no re-capture) and
+`net_output` a clone of the last decision's Q values or mu.  `network=True` builds the spec from
+`parameters` (aigar_amd.net.mlp_spec: Q_LAYERS / CACLA_ACTOR_LAYERS / DPG_ACTOR_LAYERS and the
+activations; what the device cannot evaluate is refused there); a (n_in, units, hidden, out) tuple
+overrides it.  The weights are zero until the first `set_weights`.  Epsilon, temperature and the
+noise level are read from `explore` / `noise_std` at every decision, so `collect(n)` uses what
+they hold for all n: a decay schedule is written between calls.
 """
 import collections
 
 import numpy as np
 
-from . import _abi, actions as _actions
+from . import _abi, actions as _actions, net as _net
 from ._lib import Stepper
 from .model import obs_masks, pixel_params
 
@@ -97,7 +110,7 @@ Batch = collections.namedtuple("Batch", "s a r s2 done w idx")
 class AgarVecEnv:
     def __init__(self, n_players, parameters=None, n_arenas=1, virus=None, field_size=0, max_pellets=-1.0,
                  max_viruses=-1.0, device=0, torch_stream=True, roles=None, reset_limit=None, desync=True, seed=0,
-                 score=False, pixels=None, pixel_dtype=None, memory=None, discrete=None, continuous=None):
+                 score=False, pixels=None, pixel_dtype=None, memory=None, discrete=None, continuous=None, network=None):
         import torch
         if continuous and discrete:
             raise ValueError("continuous= and discrete= exclude each other (one learner decides per env)")
@@ -237,6 +250,131 @@ class AgarVecEnv:
             self._ou_ac = torch.zeros((self.NP, cc["n_act"]), dtype=torch.float64, device=self.dev)
             self.stepper.noise_config(cc["n_act"], cc["noise"], torch.float64, theta=cc["theta"], ou_mu=cc["mu"],
                                       dt=cc["dt"], seed=cc["seed"], store_raw=cc["store_raw"])
+
+        self.network = None
+        self._obs_ready = False  # (`obs` holds the current states: what step_net's network reads)
+        if network:  # (explicit only, as memory=)
+            if self.discrete is None and self.continuous is None:
+                raise ValueError("network= needs discrete= or continuous= (the head that follows the network)")
+            if self.pixels is not None:
+                raise ValueError("network=: the device network takes no pixel state")
+            head = "q" if self.discrete is not None else "actor"
+            n_out = self.discrete["n_out"] if self.discrete is not None else self.continuous["n_act"]
+            n_in = int(self.stepper.obs_len)
+            if network is True:
+                spec = _net.mlp_spec(parameters, head, n_in=n_in, n_out=n_out)
+            else:
+                spec = _net.NetSpec(*network)
+                if spec.n_in is None:
+                    spec = spec._replace(n_in=n_in)
+            if spec.n_in != n_in or spec.units[-1] != n_out:
+                raise ValueError("network=: %d inputs and %d outputs, the env has states of %d values and a head "
+                                 "of %d" % (spec.n_in, spec.units[-1], n_in, n_out))
+            self.network = spec
+            self._head = head
+            self.stepper.net_config(spec, self.obs.dtype)
+            if self.discrete is not None:
+                self._decide_dtype(torch.float64)  # (the network's output buffer is float64)
+            self._net_out = torch.empty((self.NP, n_out), dtype=torch.float64, device=self.dev)
+            self.net_output = None
+
+    def _need_network(self):
+        if self.network is None:
+            raise RuntimeError("AgarVecEnv was created without network=")
+
+    def set_weights(self, weights):
+        """The trainer's weight push: a list of (W [in, out], b [out]) float32 per layer as device
+        tensors or arrays, or anything aigar_amd.net.weights_from_torch takes (a torch module or
+        state dict of nn.Linear layers, a flat Keras-layout list).  Takes effect at the next
+        decision; the captured graph stays."""
+        self._need_network()
+        torch = self.torch
+        pairs = isinstance(weights, (list, tuple)) and all(
+            isinstance(p, (list, tuple)) and len(p) == 2 and isinstance(p[0], torch.Tensor) and p[0].is_cuda
+            for p in weights)
+        if pairs:
+            ws = [(W.to(torch.float32).contiguous(), b.to(device=self.dev, dtype=torch.float32).contiguous())
+                  for W, b in weights]
+        else:
+            ws = _net.weights_from_torch(weights)
+        if self._mem_sync:
+            torch.cuda.synchronize(self.dev)
+        self.stepper.net_set_weights(ws)
+        if self._mem_sync:
+            self.stepper.sync()  # (ws is freed when this returns)
+
+    def _net_decisions(self, n, u=None):
+        """n decisions with the network in front, one graph replay each, no host work between."""
+        torch = self.torch
+        self._need_network()
+        if not self._obs_ready:
+            raise RuntimeError("step_net: `obs` does not hold the current states yet: call reset() or observe() first")
+        kw = dict(enable_split=self.enable_split, skip=self.skip, params=self.reward_params, n_decisions=n)
+        if self._head == "q":
+            if u is not None:
+                self._u.copy_(torch.as_tensor(u, dtype=torch.float64, device=self.dev))
+                u = self._u
+            self._decide_dtype(torch.float64)
+            self.stepper.env_step_net("q", self.explore, self._r, self.obs, idx=self._idx, val=self._val, u=u, **kw)
+            self.action_idx, self.action_value = self._idx.clone(), self._val.clone()
+        else:
+            if u is not None:
+                u = torch.as_tensor(u, dtype=torch.float64, device=self.dev)
+                if u.dim() != 4 or tuple(u.shape[:2]) != (self.NP, 2) or int(u.shape[3]) != 2:
+                    raise ValueError("step_net: u must be [%d, 2, T, 2], got %s" % (self.NP, tuple(u.shape)))
+                ub = self._nu.get(int(u.shape[2]))
+                if ub is None:
+                    ub = self._nu[int(u.shape[2])] = torch.empty(tuple(u.shape), dtype=torch.float64, device=self.dev)
+                ub.copy_(u)
+                u = ub
+            self.stepper.env_step_net("actor", self.noise_std, self._r, self.obs, u=u, noisy=self._noisy, **kw)
+            self.noisy_action = self._noisy.clone()
+        self.stepper.net_output(self._net_out)
+        self.net_output = self._net_out.clone()
+
+    def step_net(self, u=None):
+        """One decision with the acting network on the device: the network on `obs`, then the
+        selection (as `step_q`; u [n_players, 3]) or the noise (as `step_ac`; u [n_players, 2,
+        T, 2]) and the decision, one graph replay -> (obs, reward, alive, done).  Leaves
+        `net_output` (the Q values or mu; rows of dead and non-NN players keep what they held)
+        and `action_idx` / `action_value` or `noisy_action` fresh."""
+        self._net_decisions(1, u)
+        return self._after_decision()
+
+    def _run_length(self, left):
+        """Decisions until (and with) the next one that ends an episode, at most left."""
+        if self._scored:
+            return 1  # (the episode returns add every decision's reward on the torch side)
+        if self.reset_limit <= 0:
+            return left
+        per = self.skip + 1
+        room = (self.reset_limit - self.skip + 2) - self.age  # (over: age > limit - skip + 2)
+        need = int(np.min(np.maximum(room, 0) // per)) + 1
+        return max(1, min(left, need))
+
+    def collect(self, n):
+        """n decisions as `step_net()` makes them, with no Python between the graph replays of a
+        run: the runs are split where an arena's episode ends (the arenas' ages are host-side, so
+        the split points are known without a sync), and the ended arenas are reset between runs.
+        The device (worlds, memory, scores, `obs`, Orn-Uhl states) is left exactly as n calls of
+        `step_net()` leave it.  Returns the last decision's (obs, reward, alive, done), done
+        OR-ed over the n decisions.  With score=True every decision is a run of its own."""
+        self._need_network()
+        n = int(n)
+        if n < 1:
+            raise ValueError("collect: n must be at least 1")
+        done_any = None
+        out = None
+        left = n
+        while left:
+            r = self._run_length(left)
+            self._net_decisions(r)
+            if self.reset_limit > 0:
+                self.age += (r - 1) * (self.skip + 1)  # (_after_decision adds the last one's)
+            out = self._after_decision()
+            done_any = out[3] if done_any is None else done_any | out[3]
+            left -= r
+        return out[0], out[1], out[2], done_any
 
     def _need_continuous(self):
         if self.continuous is None:
@@ -536,6 +674,7 @@ class AgarVecEnv:
         return self.obs.clone()
 
     def _observe(self, mask):
+        self._obs_ready = True
         if self.pixels is not None:
             self.stepper.observe_pixel_state(self.obs, mask=mask)
         else:
@@ -594,6 +733,7 @@ class AgarVecEnv:
         if self._scored:
             self._ret += torch.where(self.nn, reward, torch.zeros_like(reward))
         done = self._episode_ends()
+        self._obs_ready = True
         alive = ~torch.isnan(self.obs.view(self.NP, -1)[:, 0]) & self.nn
         return self.obs.clone(), reward, alive, done
 

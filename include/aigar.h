@@ -556,6 +556,77 @@ int aigar_noise(aigar_handle *h, const void *mu, int rows, const double *std, co
 int aigar_env_step_ac(aigar_handle *h, const void *mu, const double *std, const double *u, int T, int enable_split,
                       int skip, const aigar_reward_params *p, double *reward_out, void *obs_out, int dtype,
                       double *noisy_out);
+/* The learners' acting network (network.py:207-241, actorCritic.py:219-330; DESIGN.md §4j;
+ * tests/net_model.py is the specification in plain Python).  An MLP of n_layers dense
+ * layers (1..5: up to four hidden layers and the head), layer l with kernel W[in][out] and
+ * bias b[out] in float32, Keras' layout; units[l] <= 256 outputs each, n_in <= 16384 inputs.
+ * One row: the input rounded once to float32 (a float32 row is taken as it is); per unit
+ * acc = +0.0f, acc = fmaf(x_k, W[k][j], acc) for k = 0, 1, ..., in - 1 as ONE chain, then
+ * y_j = acc + b_j as one float32 add; hidden layers relu (y > 0 ? y : +0.0f) or linear; the
+ * head linear (y widened to float64) or the sigmoid in float64: t = max(-|y|, -750),
+ * z = pow(e, t) (glibc's pow), y >= 0 ? 1 / (1 + z) : z / (1 + z).  A row whose first value
+ * is a NaN is not evaluated: its output row is NaN.  Any other NaN or infinity in a row is
+ * outside the contract: the result is what the arithmetic gives, and the head's
+ * AIGAR_WARN_Q_NONFINITE / AIGAR_WARN_NOISE_NONFINITE handling catches it.  Keras' own
+ * float32 sigmoid and summation order are not reproducible; this definition is the
+ * project's.  Every other activation code is refused.
+ *
+ * aigar_net_config: p NULL turns it off.  Allocates the zero-padded weights (all zero until
+ * aigar_net_set_weights) and the output buffer [A*B][units[n_layers - 1]] float64, and
+ * drops the captured decision graph.  A tiled handle is refused.  The parameters are
+ * checked before the handle, so a bad set is reported with its own message.
+ *
+ * aigar_net_set_weights: layer's W[in][out] and b[out], float32, both host or (on_device)
+ * both DEVICE pointers; stream-ordered (host pointers are read before it returns).  It
+ * re-packs into the handle's own padded copy, which the captured graph reads: no
+ * re-capture, and the next decision uses the new weights.  This is the trainer's push.
+ *
+ * aigar_net_forward: the network alone, stream-ordered, on rows >= 1 rows of the DEVICE
+ * buffer x [rows][n_in] (x_dtype: 0 float64, 1 float32, independent of the config's) into
+ * the DEVICE buffer out [rows][n_out] float64.  Liveness and roles are ignored.
+ *
+ * aigar_env_step_net: the whole decision with the network in front, one graph replay per
+ * decision: the network on obs_out, then aigar_env_step_q's selection (head
+ * AIGAR_NET_HEAD_Q; needs an aigar_decide_config with q_dtype 0 and n_out == the network's
+ * outputs; explore is [epsilon, temperature], u [A*B][3] or NULL, T ignored) or
+ * aigar_env_step_ac's noise (head AIGAR_NET_HEAD_ACTOR; needs an aigar_noise_config with
+ * mu_dtype 0 and n_act == the network's outputs; explore is [std], u [A*B][2][T][2] or
+ * NULL) on the handle's output buffer, then the decision.  The network reads obs_out as the
+ * previous decision, or the caller's aigar_observe, left it, and the decision overwrites it
+ * at its end: THE BUFFER MUST HOLD THE CURRENT STATES BEFORE THE FIRST CALL.  dtype must be
+ * the config's x_dtype and n_in the state length (aigar_obs_len; no pixel state).  Only
+ * live NN players' rows are evaluated; a dead or non-NN player keeps its output row.
+ * idx_out / val_out (head Q) and noisy_out (head actor, may be NULL) as in those calls.
+ * n_decisions >= 1 replays the graph that many times with no host work in between;
+ * explore is read from device memory at every replay (u, if given, is the same draws every
+ * time).  aigar_net_output: a stream-ordered copy of the handle's output buffer (the last
+ * decision's Q values / mu) into the DEVICE buffer out [A*B][n_out] float64. */
+#define AIGAR_NET_MAX_LAYERS 5
+#define AIGAR_NET_MAX_UNITS  256
+#define AIGAR_NET_MAX_IN     16384
+#define AIGAR_ACT_LINEAR  0
+#define AIGAR_ACT_RELU    1
+#define AIGAR_ACT_SIGMOID 2
+#define AIGAR_ACT_ELU     3   /* refused */
+#define AIGAR_ACT_TANH    4   /* refused */
+#define AIGAR_NET_HEAD_Q     0
+#define AIGAR_NET_HEAD_ACTOR 1
+typedef struct aigar_net_params {
+  int32_t n_layers;    /* dense layers, 1..AIGAR_NET_MAX_LAYERS                          */
+  int32_t n_in;        /* the state length, 1..AIGAR_NET_MAX_IN                          */
+  int32_t x_dtype;     /* the decision's state dtype: 0 float64, 1 float32               */
+  int32_t hidden_act;  /* AIGAR_ACT_RELU or AIGAR_ACT_LINEAR                             */
+  int32_t out_act;     /* AIGAR_ACT_LINEAR or AIGAR_ACT_SIGMOID                          */
+  int32_t pad;
+  int32_t units[8];    /* outputs of layer l, 1..AIGAR_NET_MAX_UNITS; [n_layers, 8) unused */
+} aigar_net_params;
+int aigar_net_config(aigar_handle *h, const aigar_net_params *p);
+int aigar_net_set_weights(aigar_handle *h, int layer, const float *W, const float *b, int on_device);
+int aigar_net_forward(aigar_handle *h, const void *x, int x_dtype, int rows, double *out);
+int aigar_net_output(aigar_handle *h, double *out);
+int aigar_env_step_net(aigar_handle *h, int head, const double *explore, const double *u, int T, int enable_split,
+                       int skip, const aigar_reward_params *p, double *reward_out, void *obs_out, int dtype,
+                       int32_t *idx_out, double *val_out, double *noisy_out, int n_decisions);
 /* The replay memory's fifth field (bot.py:206-216; replay_buffer.py:197-209 update_dones;
  * aigar.py:1079-1086).  With AIGAR_EXP_EXTRA in aigar_exp_params.flags the ring also keeps
  * extra[capacity][4] doubles and a valid byte per slot.  aigar_env_step_ac's transition
