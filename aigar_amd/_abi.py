@@ -91,6 +91,16 @@ class NetParams(C.Structure):
                 ("out_act", C.c_int32), ("pad", C.c_int32), ("units", C.c_int32 * 8)]
 
 
+CONV_MAX_LAYERS, CONV_MAX_SIDE, CONV_MAX_CHANNELS, CONV_MAX_KERNEL, CONV_MAX_FILTERS = 3, 128, 8, 8, 64
+
+
+class ConvParams(C.Structure):
+    """aigar_conv_params (include/aigar.h): the conv part of the CNN learners' acting network
+    (network.py:154-183)."""
+    _fields_ = [("side", C.c_int32), ("channels", C.c_int32), ("n_conv", C.c_int32), ("k", C.c_int32 * 3),
+                ("stride", C.c_int32 * 3), ("filters", C.c_int32 * 3)]
+
+
 class RunParams(C.Structure):
     """aigar_run_params (include/aigar.h): the policy replayed inside aigar_run's step graph."""
     _fields_ = [("policy", C.c_int32), ("greedy_split", C.c_int32), ("p_split", C.c_double),

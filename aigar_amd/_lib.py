@@ -104,6 +104,8 @@ def load(build_if_missing=False):
         "aigar_net_set_weights": [vp, i32, vp, vp, i32],
         "aigar_net_forward": [vp, vp, i32, i32, vp],
         "aigar_net_output": [vp, vp],
+        "aigar_net_config_cnn": [vp, C.POINTER(_abi.ConvParams), C.POINTER(_abi.NetParams)],
+        "aigar_net_set_conv_weights": [vp, i32, vp, vp, i32],
         "aigar_env_step_net": [vp, i32, vp, vp, i32, i32, i32, C.POINTER(_abi.RewardParams), vp, vp, i32, vp, vp, vp,
                                i32],
         "aigar_exp_extra_get": [vp, vp, i32, vp, vp],
@@ -196,6 +198,7 @@ class Stepper:
         self.dec = None  # (n_out, q dtype name) while an action selection is configured
         self.noi = None  # (n_act, mu dtype name, Orn-Uhl) while an exploration noise is configured
         self.net = None  # (n_in, units, state dtype name) while an acting network is configured
+        self.conv = None  # (side, channels, convs) while that network has a conv part (n_in: the flattened length)
 
     def _chk(self, r):
         if r < 0:
@@ -624,13 +627,28 @@ class Stepper:
     def net_config(self, spec, x_dtype="float64"):
         """The handle's acting network: spec is (n_in, units, hidden, out) -- the state
         length, the outputs of every dense layer, and the activations by name or code
-        (aigar_amd.net.mlp_spec) -- x_dtype the dtype of the decision's states.  The weights
-        are zero until net_set_weights.  net_config(None) turns it off."""
+        (aigar_amd.net.mlp_spec) -- x_dtype the dtype of the decision's states.  A CnnSpec
+        (aigar_amd.net.cnn_spec: side, channels, convs, n_flat, units, hidden, out) puts its
+        conv layers in front (aigar_net_config_cnn): the states are then images [side, side,
+        channels] and n_in is n_flat.  The weights are zero until net_set_weights.
+        net_config(None) turns it off."""
         if spec is None:
             self._chk(self.L.aigar_net_config(self.h, None))
-            self.net = None
+            self.net = self.conv = None
             return
-        n_in, units, hidden, out = spec
+        cprm = None
+        if hasattr(spec, "convs"):
+            side, channels, convs, n_flat, units, hidden, out = spec
+            convs = tuple(tuple(int(v) for v in c) for c in convs)
+            if not 1 <= len(convs) <= _abi.CONV_MAX_LAYERS or any(len(c) != 3 for c in convs):
+                raise ValueError("net_config: 1..%d conv layers (kernel, stride, filters), got %s"
+                                 % (_abi.CONV_MAX_LAYERS, convs))
+            cprm = _abi.ConvParams(int(side), int(channels), len(convs))
+            for i, (k, s, f) in enumerate(convs):
+                cprm.k[i], cprm.stride[i], cprm.filters[i] = k, s, f
+            n_in = n_flat
+        else:
+            n_in, units, hidden, out = spec
         units = [int(v) for v in units]
         d = str(x_dtype).replace("torch.", "").replace("<class 'numpy.", "").replace("'>", "")
         if d not in ("float64", "float32"):
@@ -641,7 +659,12 @@ class Stepper:
         prm = _abi.NetParams(len(units), int(n_in), 0 if d == "float64" else 1, code(hidden), code(out), 0)
         for i, v in enumerate(units):
             prm.units[i] = v
-        self._chk(self.L.aigar_net_config(self.h, C.byref(prm)))
+        if cprm is not None:
+            self._chk(self.L.aigar_net_config_cnn(self.h, C.byref(cprm), C.byref(prm)))
+            self.conv = (int(side), int(channels), convs)
+        else:
+            self._chk(self.L.aigar_net_config(self.h, C.byref(prm)))
+            self.conv = None
         self.net = (int(n_in), tuple(units), d)
 
     def _need_net(self, what):
@@ -651,11 +674,27 @@ class Stepper:
 
     def net_set_weights(self, weights):
         """The trainer's weight push: weights is a list of (W [in, out], b [out]) per layer,
-        float32, numpy arrays or device tensors (stream-ordered; no re-capture)."""
+        float32, numpy arrays or device tensors (stream-ordered; no re-capture).  With a conv
+        part its layers' (W [k, k, Cin, F], b [F]) come first, then the dense pairs."""
         n_in, units, _ = self._need_net("net_set_weights")
-        if len(weights) != len(units):
-            raise ValueError("net_set_weights: %d layers given, the network has %d" % (len(weights), len(units)))
-        for l, (W, b) in enumerate(weights):
+        convs = self.conv[2] if self.conv is not None else ()
+        if len(weights) != len(convs) + len(units):
+            raise ValueError("net_set_weights: %d layers given, the network has %d"
+                             % (len(weights), len(convs) + len(units)))
+        cin = self.conv[1] if self.conv is not None else 0
+        for l, (W, b) in enumerate(weights[:len(convs)]):
+            k, _, f = convs[l]
+            shape = (k, k, cin, f)
+            cin = f
+            if isinstance(W, np.ndarray) or not hasattr(W, "data_ptr"):
+                W, b = np.ascontiguousarray(W, np.float32), np.ascontiguousarray(b, np.float32)
+            self._check_out(W, shape, ("float32",), "net_set_weights")
+            self._check_out(b, (f,), ("float32",), "net_set_weights")
+            (wp, on), (bp, on_b) = _ptr(W), _ptr(b)
+            if on != on_b:
+                raise ValueError("net_set_weights: W and b both numpy arrays or both device tensors")
+            self._chk(self.L.aigar_net_set_conv_weights(self.h, l, wp, bp, on))
+        for l, (W, b) in enumerate(weights[len(convs):]):
             shape = (units[l - 1] if l else n_in, units[l])
             if isinstance(W, np.ndarray) or not hasattr(W, "data_ptr"):
                 W, b = np.ascontiguousarray(W, np.float32), np.ascontiguousarray(b, np.float32)
@@ -668,11 +707,12 @@ class Stepper:
 
     def net_forward(self, x, out):
         """The network alone on device tensors (aigar_net_forward): x [rows, n_in] float64 /
-        float32 -> out [rows, n_out] float64.  Liveness and roles are ignored; a row whose
-        first value is a NaN comes out NaN."""
+        float32 -> out [rows, n_out] float64 (x [rows, side, side, channels] with a conv
+        part).  Liveness and roles are ignored; a row whose first value is a NaN comes out NaN."""
         n_in, units, _ = self._need_net("net_forward")
         rows = int(x.shape[0])
-        self._check_dev(x, (rows, n_in), ("float64", "float32"), "net_forward")
+        xshape = (rows, n_in) if self.conv is None else (rows, self.conv[0], self.conv[0], self.conv[1])
+        self._check_dev(x, xshape, ("float64", "float32"), "net_forward")
         self._check_dev(out, (rows, units[-1]), ("float64",), "net_forward")
         self._chk(self.L.aigar_net_forward(self.h, C.c_void_p(x.data_ptr()), 0 if str(x.dtype) == "torch.float64" else 1,
                                            rows, C.c_void_p(out.data_ptr())))
@@ -696,7 +736,10 @@ class Stepper:
             if not getattr(t, "is_cuda", False) or not t.is_contiguous():
                 raise ValueError("env_step_net takes contiguous device tensors")
         self._check_dev(reward, (self.NP,), ("float64",), "env_step_net")
-        self._check_out(obs, (self.NP, self.obs_len), ("float64", "float32"), "env_step_net")
+        if self.conv is not None and self.pixel_state_shape is not None:
+            self._check_out(obs, self.pixel_state_shape, ("float64", "float32"), "env_step_net")
+        else:
+            self._check_out(obs, (self.NP, self.obs_len), ("float64", "float32"), "env_step_net")
         up, T, ip, vp, np_ = None, 0, None, None, None
         if hd == _abi.NET_HEAD_Q:
             self._check_dev(explore, (2,), ("float64",), "env_step_net")

@@ -55,6 +55,7 @@ using namespace aigar;
 #include "decide.inc"
 #include "noise.inc"
 #include "net.inc"
+#include "conv.inc"
 
 static thread_local std::string g_err;
 static int fail(const char *fmt, ...) {
@@ -226,6 +227,8 @@ struct aigar_handle {
     Noise noi;
     // aigar_env_step_net: the acting network in front of either (n_layers 0: none)
     Net net;
+    // ... with a conv part in front of it (aigar_net_config_cnn; n_conv 0: none)
+    Conv conv;
   } env_key{};
   // aigar_decide_config: the Q-learning bots' action selection (decide.inc; n_out 0: off)
   Decide dec{};
@@ -237,6 +240,10 @@ struct aigar_handle {
   Net net{};
   std::vector<void *> net_allocs;
   float *net_stage = nullptr;  // aigar_net_set_weights' staging of host weights (one of net_allocs)
+  // aigar_net_config_cnn: the conv part in front of it (conv.inc; n_conv 0: off)
+  Conv conv{};
+  std::vector<void *> conv_allocs;
+  float *conv_stage = nullptr;  // aigar_net_set_conv_weights' staging (one of conv_allocs)
   // aigar_exp_config: the learners' replay memory (replay.inc; cap 0: off)
   Exp exp;
   std::vector<void *> exp_allocs;
@@ -312,6 +319,10 @@ static void free_all(aigar_handle *h) {
   h->net_allocs.clear();
   h->net = Net{};
   h->net_stage = nullptr;
+  for (void *p : h->conv_allocs) (void)hipFree(p);
+  h->conv_allocs.clear();
+  h->conv = Conv{};
+  h->conv_stage = nullptr;
   if (h->d_exp_off) (void)hipFree(h->d_exp_off);
   h->d_exp_off = nullptr;
   h->exp = Exp{};
@@ -1356,7 +1367,14 @@ static int env_step_keyed(aigar_handle *h, aigar_handle::EnvKey &k, int enable_s
   if (h->d.flags & AIGAR_FLAG_EVENTS)  // the event log holds the window's ticks
     hipLaunchKernelGGL(k_step_begin, dim3((h->d.A + 63) / 64), dim3(64), 0, h->stream, h->d);
   auto launch = [&](hipStream_t cs) {
-    if (k.net.n_layers) launch_net(cs, k.net, k.obs, h->d.NP, k.net.y, h->d.p_alive, h->d.p_role);
+    if (k.conv.n_conv) {  // the conv layers on the pixel state, the dense layers on their float32 feature rows
+      launch_conv(cs, k.conv, k.obs, k.dtype, h->d.NP, h->d.p_alive, h->d.p_role);
+      Net dense = k.net;
+      dense.x_dtype = 1;
+      launch_net(cs, dense, k.conv.act[k.conv.n_conv - 1], h->d.NP, k.net.y, h->d.p_alive, h->d.p_role);
+    } else if (k.net.n_layers) {
+      launch_net(cs, k.net, k.obs, h->d.NP, k.net.y, h->d.p_alive, h->d.p_role);
+    }
     if (k.q) launch_decide(h->d, cs, k.dec, k.q, k.explore, k.u, k.idx_out, k.val_out, k.dec.act);
     if (k.mu)
       launch_noise(h->d, cs, k.noi, k.mu, h->d.NP, 1, k.nstd, k.nu, k.nT, nullptr, k.noisy, nullptr);
@@ -1568,11 +1586,16 @@ extern "C" int aigar_env_step_ac(aigar_handle *h, const void *mu, const double *
 }
 
 // ------------------------------------------------------------ acting network
+static int pix_channels(const aigar_pixel_params &p);
 static void net_free(aigar_handle *h) {
   for (void *p : h->net_allocs) (void)hipFree(p);
   h->net_allocs.clear();
   h->net = Net{};
   h->net_stage = nullptr;
+  for (void *p : h->conv_allocs) (void)hipFree(p);
+  h->conv_allocs.clear();
+  h->conv = Conv{};
+  h->conv_stage = nullptr;
 }
 static int need_net(aigar_handle *h, const char *who) {
   if (!h) return fail("null handle");
@@ -1682,8 +1705,115 @@ extern "C" int aigar_net_forward(aigar_handle *h, const void *x, int x_dtype, in
   HIPCHK(hipSetDevice(h->cfg.device));
   Net c = h->net;
   c.x_dtype = x_dtype;
-  launch_net(h->stream, c, x, rows, out, nullptr, nullptr);
+  if (h->conv.n_conv) {  // in slabs of the activation buffers' rows, one after the other on the stream
+    const Conv &cv = h->conv;
+    const size_t img = (size_t)cv.side * cv.side * cv.channels * (x_dtype == 0 ? 8 : 4);
+    const int n_out = c.out[c.n_layers - 1];
+    c.x_dtype = 1;
+    for (int r0 = 0; r0 < rows; r0 += cv.cap) {
+      const int n = std::min(cv.cap, rows - r0);
+      launch_conv(h->stream, cv, (const char *)x + (size_t)r0 * img, x_dtype, n, nullptr, nullptr);
+      launch_net(h->stream, c, cv.act[cv.n_conv - 1], n, out + (size_t)r0 * n_out, nullptr, nullptr);
+    }
+  } else {
+    launch_net(h->stream, c, x, rows, out, nullptr, nullptr);
+  }
   HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// The conv part: the parameter checks (before the handle, each with its own message), the
+// dense part through aigar_net_config, then the conv part's own buffers.
+extern "C" int aigar_net_config_cnn(aigar_handle *h, const aigar_conv_params *cp, const aigar_net_params *p) {
+  if (!cp || !p) return fail("net_config_cnn: null argument");
+  if (cp->side < 1 || cp->side > kConvMaxSide)
+    return fail("net_config_cnn: side = %d is outside 1..%d", cp->side, kConvMaxSide);
+  if (cp->channels < 1 || cp->channels > kConvMaxCh)
+    return fail("net_config_cnn: channels = %d is outside 1..%d", cp->channels, kConvMaxCh);
+  if (cp->n_conv < 1 || cp->n_conv > kConvMax)
+    return fail("net_config_cnn: n_conv = %d is outside 1..%d", cp->n_conv, kConvMax);
+  Conv c{};
+  c.n_conv = cp->n_conv;
+  c.side = cp->side;
+  c.channels = cp->channels;
+  int in = cp->side;
+  for (int l = 0; l < cp->n_conv; l++) {
+    if (cp->k[l] < 1 || cp->k[l] > kConvMaxK)
+      return fail("net_config_cnn: conv layer %d has kernel k = %d, outside 1..%d", l, cp->k[l], kConvMaxK);
+    if (cp->stride[l] < 1 || cp->stride[l] > kConvMaxK)
+      return fail("net_config_cnn: conv layer %d has stride = %d, outside 1..%d", l, cp->stride[l], kConvMaxK);
+    if (cp->filters[l] < 1 || cp->filters[l] > kConvMaxF)
+      return fail("net_config_cnn: conv layer %d has filters = %d, outside 1..%d", l, cp->filters[l], kConvMaxF);
+    if (in < cp->k[l])
+      return fail("net_config_cnn: conv layer %d has no output: its input side %d is below its kernel %d", l, in,
+                  cp->k[l]);
+    c.k[l] = cp->k[l];
+    c.stride[l] = cp->stride[l];
+    c.filters[l] = cp->filters[l];
+    c.osz[l] = in = (in - cp->k[l]) / cp->stride[l] + 1;
+  }
+  const long long flat = (long long)in * in * c.filters[c.n_conv - 1];
+  if (flat > kNetMaxIn)
+    return fail("net_config_cnn: the flattened length %lld (%d x %d x %d) is above %d", flat, in, in,
+                c.filters[c.n_conv - 1], kNetMaxIn);
+  c.n_flat = (int)flat;
+  if (p->n_in != c.n_flat)
+    return fail("net_config_cnn: the dense part's n_in = %d differs from the flattened length %d", p->n_in, c.n_flat);
+  if (aigar_net_config(h, p)) return -1;  // (its own checks; drops the graph and any earlier conv part)
+  c.cap = std::max(h->d.NP, kConvMinRows);
+  size_t stage = 0;
+  auto alloc = [&](size_t bytes) -> void * {
+    void *m = nullptr;
+    if (hipMalloc(&m, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+    h->conv_allocs.push_back(m);
+    (void)hipMemsetAsync(m, 0, bytes, h->stream);
+    return m;
+  };
+  bool ok = true;
+  for (int l = 0; l < c.n_conv && ok; l++) {
+    const size_t K = (size_t)c.k[l] * c.k[l] * (l ? c.filters[l - 1] : c.channels), F = c.filters[l];
+    const size_t Fp = net_out_pad((int)F);
+    c.w[l] = (float *)alloc(conv_k_pad((int)K) * Fp * sizeof(float));
+    c.b[l] = (float *)alloc(Fp * sizeof(float));
+    c.act[l] = (float *)alloc((size_t)c.cap * c.osz[l] * c.osz[l] * F * sizeof(float));
+    ok = c.w[l] && c.b[l] && c.act[l];
+    stage = std::max(stage, K * F + F);
+  }
+  if (ok) ok = (h->conv_stage = (float *)alloc(stage * sizeof(float))) != nullptr;
+  if (!ok) {
+    net_free(h);
+    return fail("net_config_cnn: out of device memory");
+  }
+  HIPCHK(hipGetLastError());
+  h->conv = c;
+  return 0;
+}
+
+extern "C" int aigar_net_set_conv_weights(aigar_handle *h, int layer, const float *W, const float *b, int on_device) {
+  if (need_net(h, "net_set_conv_weights")) return -1;
+  const Conv &c = h->conv;
+  if (!c.n_conv) return fail("net_set_conv_weights: the network has no conv part (aigar_net_config_cnn)");
+  if (layer < 0 || layer >= c.n_conv)
+    return fail("net_set_conv_weights: layer %d is outside 0..%d", layer, c.n_conv - 1);
+  if (!W || !b) return fail("net_set_conv_weights: null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const int K = c.k[layer] * c.k[layer] * (layer ? c.filters[layer - 1] : c.channels), F = c.filters[layer];
+  const size_t nw = (size_t)K * F;
+  if (!on_device) {
+    HIPCHK(hipMemcpyAsync(h->conv_stage, W, nw * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->conv_stage + nw, b, (size_t)F * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    W = h->conv_stage;
+    b = h->conv_stage + nw;
+  }
+  const int Kp = conv_k_pad(K), Fp = net_out_pad(F);
+  const size_t n = (size_t)Kp * Fp;
+  hipLaunchKernelGGL(k_conv_pack, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, h->stream, W, b,
+                     c.w[layer], c.b[layer], K, F, Kp, Fp);
+  HIPCHK(hipGetLastError());
+  if (!on_device) HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's arrays are read, the staging is free)
   return 0;
 }
 
@@ -1707,12 +1837,22 @@ extern "C" int aigar_env_step_net(aigar_handle *h, int head, const double *explo
   if (n_decisions < 1) return fail("env_step_net: n_decisions = %d is below 1", n_decisions);
   const Net &c = h->net;
   const int n_out = c.out[c.n_layers - 1];
-  if (h->pix.side) return fail("env_step_net: the acting network takes no pixel state");
-  if (c.in[0] != h->d.L)
-    return fail("env_step_net: the network has %d inputs, the state %d values", c.in[0], h->d.L);
+  if (h->conv.n_conv) {
+    if (!h->pix.side)
+      return fail("env_step_net: the network's conv part needs a pixel state of side %d and %d channels "
+                  "(aigar_pixel_config)", h->conv.side, h->conv.channels);
+    if (h->pix.side != h->conv.side || pix_channels(h->pix) != h->conv.channels)
+      return fail("env_step_net: the pixel state is %d x %d x %d, the network's conv part takes %d x %d x %d",
+                  h->pix.side, h->pix.side, pix_channels(h->pix), h->conv.side, h->conv.side, h->conv.channels);
+  } else {
+    if (h->pix.side) return fail("env_step_net: the acting network takes no pixel state");
+    if (c.in[0] != h->d.L)
+      return fail("env_step_net: the network has %d inputs, the state %d values", c.in[0], h->d.L);
+  }
   if (dtype != c.x_dtype) return fail("env_step_net: dtype %d differs from the network's x_dtype %d", dtype, c.x_dtype);
   aigar_handle::EnvKey k{};
   k.net = c;
+  k.conv = h->conv;
   if (head == AIGAR_NET_HEAD_Q) {
     if (need_dec(h, "env_step_net")) return -1;
     if (h->dec.q_dtype != 0) return fail("env_step_net: the action selection's q_dtype must be 0 (float64)");

@@ -94,6 +94,11 @@ activations; what the device cannot evaluate is refused there); a (n_in, units, 
 overrides it.  The weights are zero until the first `set_weights`.  Epsilon, temperature and the
 noise level are read from `explore` / `noise_std` at every decision, so `collect(n)` uses what
 they hold for all n: a decay schedule is written between calls.
+With a pixel state (`pixels=` or CNN_REPR and CNN_P_REPR) the network is the reference's CNN
+(DESIGN.md §4k): `network=True` builds a CnnSpec from `parameters` (aigar_amd.net.cnn_spec: CNN_L1/2/3,
+CNN_USE_L1/2/3 and the dense settings above), a CnnSpec overrides it; the conv layers run on the
+device too, in the same graph, and `set_weights` takes the conv pairs first (a torch module of
+nn.Conv2d and nn.Linear layers is converted, aigar_amd.net.cnn_weights_from_torch).
 """
 import collections
 
@@ -256,20 +261,35 @@ class AgarVecEnv:
         if network:  # (explicit only, as memory=)
             if self.discrete is None and self.continuous is None:
                 raise ValueError("network= needs discrete= or continuous= (the head that follows the network)")
-            if self.pixels is not None:
-                raise ValueError("network=: the device network takes no pixel state")
             head = "q" if self.discrete is not None else "actor"
             n_out = self.discrete["n_out"] if self.discrete is not None else self.continuous["n_act"]
             n_in = int(self.stepper.obs_len)
-            if network is True:
-                spec = _net.mlp_spec(parameters, head, n_in=n_in, n_out=n_out)
+            if self.pixels is not None:  # the CNN learner: conv layers on the pixel state
+                if network is True:
+                    spec = _net.cnn_spec(parameters, head, n_out=n_out)
+                elif hasattr(network, "convs") or len(network) == len(_net.CnnSpec._fields):
+                    spec = _net.CnnSpec(*network)
+                else:
+                    raise ValueError("network=: the device network takes no pixel state without a conv part "
+                                     "(a CnnSpec, aigar_amd.net.cnn_spec)")
+                side, channels = self.stepper.pixel_state_shape[1], self.stepper.pixel_state_shape[3]
+                if (spec.side, spec.channels) != (side, channels):
+                    raise ValueError("network=: the conv part takes images %d x %d x %d, the env's pixel state is "
+                                     "%d x %d x %d" % (spec.side, spec.side, spec.channels, side, side, channels))
+                if spec.units[-1] != n_out:
+                    raise ValueError("network=: %d outputs, the env has a head of %d" % (spec.units[-1], n_out))
             else:
-                spec = _net.NetSpec(*network)
-                if spec.n_in is None:
-                    spec = spec._replace(n_in=n_in)
-            if spec.n_in != n_in or spec.units[-1] != n_out:
-                raise ValueError("network=: %d inputs and %d outputs, the env has states of %d values and a head "
-                                 "of %d" % (spec.n_in, spec.units[-1], n_in, n_out))
+                if network is True:
+                    spec = _net.mlp_spec(parameters, head, n_in=n_in, n_out=n_out)
+                elif hasattr(network, "convs"):
+                    raise ValueError("network=: a CnnSpec needs a pixel state (pixels=)")
+                else:
+                    spec = _net.NetSpec(*network)
+                    if spec.n_in is None:
+                        spec = spec._replace(n_in=n_in)
+                if spec.n_in != n_in or spec.units[-1] != n_out:
+                    raise ValueError("network=: %d inputs and %d outputs, the env has states of %d values and a head "
+                                     "of %d" % (spec.n_in, spec.units[-1], n_in, n_out))
             self.network = spec
             self._head = head
             self.stepper.net_config(spec, self.obs.dtype)
@@ -285,8 +305,9 @@ class AgarVecEnv:
     def set_weights(self, weights):
         """The trainer's weight push: a list of (W [in, out], b [out]) float32 per layer as device
         tensors or arrays, or anything aigar_amd.net.weights_from_torch takes (a torch module or
-        state dict of nn.Linear layers, a flat Keras-layout list).  Takes effect at the next
-        decision; the captured graph stays."""
+        state dict of nn.Linear layers, a flat Keras-layout list; with a conv part the conv
+        pairs (W [k, k, Cin, F], b [F]) first, aigar_amd.net.cnn_weights_from_torch).  Takes
+        effect at the next decision; the captured graph stays."""
         self._need_network()
         torch = self.torch
         pairs = isinstance(weights, (list, tuple)) and all(
@@ -295,6 +316,8 @@ class AgarVecEnv:
         if pairs:
             ws = [(W.to(torch.float32).contiguous(), b.to(device=self.dev, dtype=torch.float32).contiguous())
                   for W, b in weights]
+        elif hasattr(self.network, "convs"):
+            ws = _net.cnn_weights_from_torch(weights, self.network)
         else:
             ws = _net.weights_from_torch(weights)
         if self._mem_sync:

@@ -2,9 +2,11 @@
 DESIGN.md §4j): the reference's parameters -> a network specification, and a trainer's
 weights -> the Keras-layout float32 arrays the device takes.
 
-The device evaluates MLPs only: up to five dense layers of at most 256 units, relu or
-linear hidden layers, a linear (Q) or sigmoid (actor) head.  Everything else the reference
-can build is refused here, at configuration, with a message that names the setting."""
+The device evaluates MLPs: up to five dense layers of at most 256 units, relu or linear
+hidden layers, a linear (Q) or sigmoid (actor) head; and, in front of one, the conv layers of
+the reference's CNN over the pixel state (cnn_spec, cnn_weights_from_torch).
+Everything else the reference can build is refused here, at configuration, with a message
+that names the setting."""
 import collections
 
 import numpy as np
@@ -64,6 +66,145 @@ def mlp_spec(parameters=None, head="q", n_in=None, n_out=None):
     if n_in is not None and not 1 <= int(n_in) <= _abi.NET_MAX_IN:
         raise ValueError("mlp_spec: %d inputs, at most %d" % (n_in, _abi.NET_MAX_IN))
     return NetSpec(None if n_in is None else int(n_in), units, hidden, out)
+
+
+CnnSpec = collections.namedtuple("CnnSpec", "side channels convs n_flat units hidden out")
+
+
+class _Dense:
+    """The parameters as mlp_spec reads them for the dense layers behind the conv part."""
+
+    def __init__(self, parameters):
+        self._p = parameters
+
+    def __getattr__(self, name):
+        if name == "CNN_REPR":
+            return False
+        if name.startswith("_"):
+            raise AttributeError(name)
+        v = _get(self._p, name, _Dense)
+        if v is _Dense:
+            raise AttributeError(name)
+        return v
+
+
+def conv_out_side(side, convs):
+    """The output side of every conv layer: (in - k) // s + 1 (valid padding)."""
+    out = []
+    for k, s, _ in convs:
+        side = (side - k) // s + 1
+        out.append(side)
+    return out
+
+
+def cnn_spec(parameters=None, head="q", n_out=None):
+    """CnnSpec of the reference's CNN over the pixel state (CNN_REPR with CNN_P_REPR;
+    network.py:154-183, actorCritic.py:122-136): the conv layers CNN_L1/2/3 = (kernel, stride,
+    filters) that CNN_USE_L1/2/3 switch on, the image side CNN_INPUT_DIM_* of the first of them
+    (rgbGenerator.py:16-21), 1 channel (3 with CNN_P_RGB), doubled by CNN_LAST_GRID; then the
+    dense layers and activations mlp_spec reads for the head, on the flattened length n_flat.
+    n_out as in mlp_spec."""
+    g = lambda n, d: _get(parameters, n, d)
+    if g("CNN_REPR", False) and not g("CNN_P_REPR", False):
+        raise ValueError("cnn_spec: CNN_REPR without CNN_P_REPR (the CNN over the grid view) is not supported by the "
+                         "device network")
+    if g("CNN_P_INCEPTION", False):
+        raise ValueError("cnn_spec: CNN_P_INCEPTION is not supported by the device network")
+    use = [bool(g("CNN_USE_L1", True)), bool(g("CNN_USE_L2", True)), bool(g("CNN_USE_L3", False))]
+    layers = [g("CNN_L1", (8, 4, 32)), g("CNN_L2", (4, 2, 64)), g("CNN_L3", (3, 1, 64))]
+    dims = [g("CNN_INPUT_DIM_1", 42), g("CNN_INPUT_DIM_2", 84), g("CNN_INPUT_DIM_3", 42)]
+    if not any(use):
+        raise ValueError("cnn_spec: none of CNN_USE_L1, CNN_USE_L2, CNN_USE_L3 is set: no conv layer")
+    side = int(dims[use.index(True)])
+    channels = (3 if g("CNN_P_RGB", False) else 1) * (2 if g("CNN_LAST_GRID", False) else 1)
+    if not 1 <= side <= _abi.CONV_MAX_SIDE:
+        raise ValueError("cnn_spec: CNN_INPUT_DIM_%d = %d is outside 1..%d" % (use.index(True) + 1, side,
+                                                                               _abi.CONV_MAX_SIDE))
+    convs, cur = [], side
+    for i in range(3):
+        if not use[i]:
+            continue
+        name = "CNN_L%d" % (i + 1)
+        if len(layers[i]) != 3:
+            raise ValueError("cnn_spec: %s must be (kernel, stride, filters), got %r" % (name, layers[i]))
+        k, s, f = (int(v) for v in layers[i])
+        if not 1 <= k <= _abi.CONV_MAX_KERNEL or not 1 <= s <= _abi.CONV_MAX_KERNEL:
+            raise ValueError("cnn_spec: %s = %r: kernel and stride must be in 1..%d" % (name, tuple(layers[i]),
+                                                                                      _abi.CONV_MAX_KERNEL))
+        if not 1 <= f <= _abi.CONV_MAX_FILTERS:
+            raise ValueError("cnn_spec: %s = %r: filters must be in 1..%d" % (name, tuple(layers[i]),
+                                                                             _abi.CONV_MAX_FILTERS))
+        if cur < k:
+            raise ValueError("cnn_spec: %s = %r has no output on an input of side %d" % (name, tuple(layers[i]), cur))
+        cur = (cur - k) // s + 1
+        convs.append((k, s, f))
+    n_flat = cur * cur * convs[-1][2]
+    if n_flat > _abi.NET_MAX_IN:
+        raise ValueError("cnn_spec: the flattened length %d (%d x %d x %d) is above %d: CNN_USE_L*"
+                         % (n_flat, cur, cur, convs[-1][2], _abi.NET_MAX_IN))
+    try:
+        dense = mlp_spec(_Dense(parameters), head, n_in=n_flat, n_out=n_out)
+    except ValueError as e:
+        raise ValueError(str(e).replace("mlp_spec:", "cnn_spec:", 1)) from None
+    return CnnSpec(side, channels, tuple(convs), n_flat, dense.units, dense.hidden, dense.out)
+
+
+def _np(a):
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def cnn_weights_from_torch(source, spec):
+    """[(W [k, k, Cin, F], b [F]), ..., (W [in, out], b [out]), ...] float32 numpy arrays in
+    Keras' layout for a CnnSpec, the conv pairs first: from a torch module or state dict of
+    nn.Conv2d layers (weight [out, in, kh, kw] -> [kh, kw, in, out]) followed by nn.Linear
+    layers (weight [out, in], transposed; the first one's input, which a torch Flatten of NCHW
+    gives in (c, y, x) order, is permuted to the device's (y, x, c) order), or from a plain
+    list of Keras-layout arrays, flat or in pairs, which is passed through."""
+    if hasattr(source, "state_dict"):
+        source = source.state_dict()
+    out = []
+    if isinstance(source, dict):
+        first = True
+        for k, w in source.items():
+            if not k.endswith("weight") or getattr(w, "ndim", 0) not in (2, 4):
+                continue
+            w = _np(w)
+            b = source.get(k[:-len("weight")] + "bias")
+            b = np.zeros(w.shape[0], np.float32) if b is None else _np(b)
+            if w.ndim == 4:
+                w = w.transpose(2, 3, 1, 0)
+            else:
+                w = w.T
+                if first:
+                    f = spec.convs[-1][2]
+                    o = conv_out_side(spec.side, spec.convs)[-1]
+                    if w.shape[0] != f * o * o:
+                        raise ValueError("cnn_weights_from_torch: the first Linear has %d inputs, the conv part gives "
+                                         "%d" % (w.shape[0], f * o * o))
+                    w = w.reshape(f, o, o, w.shape[1]).transpose(1, 2, 0, 3).reshape(f * o * o, w.shape[1])
+                    first = False
+            out.append((np.ascontiguousarray(w, np.float32), np.ascontiguousarray(b, np.float32)))
+    else:
+        items = list(source)
+        if items and isinstance(items[0], (tuple, list)) and len(items[0]) == 2:
+            pairs = items
+        else:
+            if len(items) % 2:
+                raise ValueError("cnn_weights_from_torch: a flat list must be [W0, b0, W1, b1, ...]")
+            pairs = list(zip(items[0::2], items[1::2]))
+        out = [(np.ascontiguousarray(_np(w), np.float32), np.ascontiguousarray(_np(b), np.float32)) for w, b in pairs]
+    shapes, cin = [], spec.channels
+    for k, _, f in spec.convs:
+        shapes.append((k, k, cin, f))
+        cin = f
+    n = spec.n_flat
+    for u in spec.units:
+        shapes.append((n, u))
+        n = u
+    got = [w.shape for w, _ in out]
+    if got != shapes or any(b.shape != (w.shape[-1],) for w, b in out):
+        raise ValueError("cnn_weights_from_torch: expected kernels of shapes %s with their biases, got %s" % (shapes, got))
+    return out
 
 
 def weights_from_torch(source):

@@ -627,6 +627,50 @@ int aigar_net_output(aigar_handle *h, double *out);
 int aigar_env_step_net(aigar_handle *h, int head, const double *explore, const double *u, int T, int enable_split,
                        int skip, const aigar_reward_params *p, double *reward_out, void *obs_out, int dtype,
                        int32_t *idx_out, double *val_out, double *noisy_out, int n_decisions);
+/* The CNN learners' acting network (CNN_REPR with CNN_P_REPR: network.py:154-183,
+ * actorCritic.py:122-136; tests/conv_model.py is the specification in plain
+ * Python): a convolutional front end in front of the dense layers above.  The image is
+ * x[side][side][channels] (the pixel state, channels last), rounded once to float32.  n_conv
+ * (1..3) conv layers, layer l with a square kernel W[k][k][Cin][F] and bias b[F] in float32
+ * (Keras' layout), valid padding, stride s, always relu; its output side is
+ * (in - k) / s + 1 (floor).  One output (oy, ox, f): acc = +0.0f,
+ * acc = fmaf(x[oy s + ky][ox s + kx][c], W[ky][kx][c][f], acc) as ONE chain in ascending
+ * order of (ky k + kx) Cin + c, then acc + b[f] as one float32 add, then y > 0 ? y : +0.0f.
+ * The last conv layer's output, flattened in (y, x, f) order (Keras' Flatten), is the dense
+ * part's float32 input row.  A sample whose first image value is a NaN (a dead player's
+ * pixel state) is not evaluated: its output row is NaN.
+ *
+ * aigar_net_config_cnn: both parameter sets are checked before the handle, each refusal with
+ * its own message: side 1..128, channels 1..8, n_conv 1..3, k 1..8, stride 1..8, filters
+ * 1..64, every layer's output side >= 1, the flattened length <= AIGAR_NET_MAX_IN, and
+ * d->n_in == the flattened length; d->x_dtype is the image's dtype.  A tiled handle is
+ * refused.  It allocates the padded filters (zero until aigar_net_set_conv_weights) and the
+ * float32 activations and feature rows for max(A*B, 64) samples, all owned by the handle,
+ * and drops the captured decision graph.  aigar_net_config (plain or NULL) turns the conv
+ * part off again.
+ *
+ * aigar_net_set_conv_weights: conv layer's W[k][k][Cin][F] and b[F], host or (on_device)
+ * DEVICE pointers, stream-ordered, re-packed into the handle's own copy: no re-capture
+ * (aigar_net_set_weights goes on setting the dense layers).  With a conv part
+ * aigar_net_forward takes x[rows][side][side][channels] and aigar_env_step_net requires a
+ * configured pixel state (aigar_pixel_config) of the same side and channel count; it then
+ * runs the conv layers, the dense layers and the head's selection or noise in the
+ * decision's one graph.  Without a conv part a pixel state is refused as before. */
+#define AIGAR_CONV_MAX_LAYERS  3
+#define AIGAR_CONV_MAX_SIDE    128
+#define AIGAR_CONV_MAX_CHANNELS 8
+#define AIGAR_CONV_MAX_KERNEL  8
+#define AIGAR_CONV_MAX_FILTERS 64
+typedef struct aigar_conv_params {
+  int32_t side;        /* the image's side, 1..AIGAR_CONV_MAX_SIDE                        */
+  int32_t channels;    /* ... and channels, 1..AIGAR_CONV_MAX_CHANNELS                    */
+  int32_t n_conv;      /* conv layers, 1..AIGAR_CONV_MAX_LAYERS                           */
+  int32_t k[3];        /* kernel side of layer l, 1..AIGAR_CONV_MAX_KERNEL                */
+  int32_t stride[3];   /* stride of layer l, 1..AIGAR_CONV_MAX_KERNEL                     */
+  int32_t filters[3];  /* filters of layer l, 1..AIGAR_CONV_MAX_FILTERS                   */
+} aigar_conv_params;
+int aigar_net_config_cnn(aigar_handle *h, const aigar_conv_params *c, const aigar_net_params *d);
+int aigar_net_set_conv_weights(aigar_handle *h, int layer, const float *W, const float *b, int on_device);
 /* The replay memory's fifth field (bot.py:206-216; replay_buffer.py:197-209 update_dones;
  * aigar.py:1079-1086).  With AIGAR_EXP_EXTRA in aigar_exp_params.flags the ring also keeps
  * extra[capacity][4] doubles and a valid byte per slot.  aigar_env_step_ac's transition
