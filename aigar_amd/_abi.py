@@ -78,6 +78,14 @@ class NoiseParams(C.Structure):
                 ("theta", C.c_double), ("ou_mu", C.c_double), ("dt", C.c_double), ("seed", C.c_uint64)]
 
 
+# aigar_selftest_sem's ops (include/aigar.h AIGAR_SEM_*) and their (input, output) column counts
+(SEM_MOD_POS, SEM_TRUNC_DIV_POS, SEM_PY_MOD, SEM_ROUND3, SEM_SUM, SEM_RADIUS, SEM_BUCKET, SEM_FOOTPRINT, SEM_MOVE,
+ SEM_MOMENTUM, SEM_MERGE_TIME, SEM_PHILOX, SEM_TRIG_FORMS) = range(13)
+SEM_COLS = {SEM_MOD_POS: (2, 1), SEM_TRUNC_DIV_POS: (2, 1), SEM_PY_MOD: (2, 1), SEM_ROUND3: (1, 1), SEM_SUM: (17, 2),
+            SEM_RADIUS: (1, 2), SEM_BUCKET: (2, 3), SEM_FOOTPRINT: (4, 4), SEM_MOVE: (6, 4), SEM_MOMENTUM: (7, 2),
+            SEM_MERGE_TIME: (2, 1), SEM_PHILOX: (8, 6), SEM_TRIG_FORMS: (2, 6)}
+
+
 NET_MAX_LAYERS, NET_MAX_UNITS, NET_MAX_IN = 5, 256, 16384  # aigar_net_params' bounds
 ACT_LINEAR, ACT_RELU, ACT_SIGMOID, ACT_ELU, ACT_TANH = 0, 1, 2, 3, 4  # (elu and tanh are refused)
 ACTIVATIONS = {"linear": ACT_LINEAR, "relu": ACT_RELU, "sigmoid": ACT_SIGMOID, "elu": ACT_ELU, "tanh": ACT_TANH}

@@ -127,6 +127,7 @@ def load(build_if_missing=False):
         "aigar_selftest_pow": [dp, dp, dp, i32],
         "aigar_selftest_log": [dp, dp, i32],
         "aigar_selftest_trig": [dp, dp, dp, i32],
+        "aigar_selftest_sem": [i32, dp, i32, dp, i32, i32],
         "aigar_counters": [vp, i32, C.POINTER(C.c_int64), i32],
         "aigar_policy_greedy": [vp, i32, vp, i32],
         "aigar_apply_actions": [vp, vp, i32, i32, i32, i32, i32],
@@ -1074,3 +1075,29 @@ def selftest_log(x):
     if L.aigar_selftest_log(x.ctypes.data_as(dp), out.ctypes.data_as(dp), len(x)) < 0:
         raise RuntimeError("aigar: " + L.aigar_last_error().decode())
     return out
+
+
+def selftest_sem(op, *columns):
+    """Device helpers of aigar_sem.h / aigar_math.h (include/aigar.h: aigar_selftest_sem) on host
+    columns of equal length: op is an _abi.SEM_* code, the result a tuple of the op's output
+    columns.  float64 columns are values; uint64 columns (the Philox op's words) go and come
+    back as bit patterns, viewed as float64: view an output as uint64 to read its word."""
+    L = load()
+    if op not in _abi.SEM_COLS:
+        raise ValueError("selftest_sem: op %r is no _abi.SEM_* code" % (op,))
+    n_in, n_out = _abi.SEM_COLS[op]
+    if len(columns) != n_in:
+        raise ValueError("selftest_sem: op %d takes %d columns, got %d" % (op, n_in, len(columns)))
+    cols = []
+    for c in columns:
+        c = np.asarray(c)
+        cols.append(c.view(np.float64) if c.dtype == np.uint64 else c.astype(np.float64, copy=False))
+    n = len(cols[0])
+    if any(c.shape != (n,) for c in cols):
+        raise ValueError("selftest_sem: columns of unequal length")
+    src = np.ascontiguousarray(np.stack(cols)) if n else np.zeros((n_in, 0))
+    out = np.zeros((n_out, n))
+    dp = C.POINTER(C.c_double)
+    if L.aigar_selftest_sem(op, src.ctypes.data_as(dp), n_in, out.ctypes.data_as(dp), n_out, n) < 0:
+        raise RuntimeError("aigar: " + L.aigar_last_error().decode())
+    return tuple(out)

@@ -20,7 +20,9 @@
 // -ffp-contract=off, so no other operation fuses.
 // tools/gen/check_glibc_trig.cpp checks the host build against libm and against
 // the FMA variants themselves (linked from libm-2.35.a) on 10^7 inputs shaped
-// like the path's; tests/test_gpu_parity.py checks the device.
+// like the path's; tests/test_gpu_math_families.py checks the device on the same
+// families against math.atan2 / math.sin / math.cos, the branchy forms and the
+// wavefront-shaped ones the stepper runs (tests/test_gpu_parity.py: a first few).
 // Domain: sin / cos for |x| < 105414350 (s_sin.c's __branred range beyond is
 // never reached by the path's angles, |x| < 2 pi; it falls back to the
 // correctly rounded aigar_trig.h), atan2 for all inputs.

@@ -12,7 +12,10 @@
 // multiply-adds as the x86-64 FMA variant the reference's host dispatches to
 // (glibc's __ieee754_pow_fma, whose contractions were read off its object code;
 // sysdeps/ieee754/dbl-64/e_pow.c).  tests/test_pow_host.py checks the host
-// build against libm's pow on 10^7 inputs; tests/test_gpu_parity.py the device.
+// build against libm's pow on 10^7 inputs; tests/test_gpu_math_families.py (and
+// tests/test_gpu_parity.py) the device's pow against math.pow on the same input
+// families, tests/test_gpu_sem.py the device's mod_pos and trunc_div_pos against
+// Python's % and int(x / b).
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -56,7 +59,12 @@ AIGAR_HD double mod_pos(double a, double b, double inv_b) {
 // fl(D); rounding is monotone and -t is a double, so fl(D) > -t implies D > -t
 // and fl(D) < -t implies D < -t; fl(D) == -t (D on or next to the midpoint,
 // where ties-to-even decides) takes the division itself.  x / b < 2^31.
-// (tools/gen/check_trunc_div.cpp, tests/test_pow_host.py)
+// (No pair of doubles lands there: x - n b = -t would make x the product of
+// b's significand and the 54-bit odd number n - ulp / 2, which no double holds,
+// and D and t are whole multiples of ulp(t), so a D that is not -t does not
+// round to it.  The division stays as the answer the comparison cannot give.)
+// (tools/gen/check_trunc_div.cpp, tests/test_pow_host.py; on the device
+// tests/test_gpu_sem.py)
 AIGAR_HD int trunc_div_pos(double x, double b, double inv_b) {
   const double n = rint(x * inv_b);
   if (n <= 0.0) return 0;

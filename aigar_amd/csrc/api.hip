@@ -3099,3 +3099,148 @@ extern "C" int aigar_selftest_trig(const double *y, const double *x, double *out
   (void)hipFree(dz);
   return 0;
 }
+
+// The per-entity helpers of aigar_sem.h and the exact integer helpers of aigar_math.h, one
+// thread per element, the header functions themselves (tests/test_gpu_sem.py).  in is
+// [in_cols][n], out [out_cols][n], 8-byte words: values are doubles, integers come back as
+// exact doubles, the Philox op's 64-bit words travel as bit patterns.
+namespace {
+struct SemOp {
+  int in_cols, out_cols;
+};
+constexpr SemOp kSemOps[AIGAR_SEM_N_OPS] = {
+    {2, 1},   // MOD_POS
+    {2, 1},   // TRUNC_DIV_POS
+    {2, 1},   // PY_MOD
+    {1, 1},   // ROUND3
+    {17, 2},  // SUM
+    {1, 2},   // RADIUS
+    {2, 3},   // BUCKET
+    {4, 4},   // FOOTPRINT
+    {6, 4},   // MOVE
+    {7, 2},   // MOMENTUM
+    {2, 1},   // MERGE_TIME
+    {8, 6},   // PHILOX
+    {2, 6},   // TRIG_FORMS
+};
+}  // namespace
+
+__global__ void k_selftest_sem(int op, const double *in, double *out, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const size_t N = (size_t)n;
+#define SEM_IN(c) in[(size_t)(c) * N + i]
+#define SEM_OUT(c) out[(size_t)(c) * N + i]
+  switch (op) {
+    case AIGAR_SEM_MOD_POS: {
+      const double a = SEM_IN(0), b = SEM_IN(1);
+      SEM_OUT(0) = aigar_math::mod_pos(a, b, 1.0 / b);
+    } break;
+    case AIGAR_SEM_TRUNC_DIV_POS: {
+      const double x = SEM_IN(0), b = SEM_IN(1);
+      SEM_OUT(0) = (double)aigar_math::trunc_div_pos(x, b, 1.0 / b);
+    } break;
+    case AIGAR_SEM_PY_MOD:
+      SEM_OUT(0) = py_mod(SEM_IN(0), SEM_IN(1));
+      break;
+    case AIGAR_SEM_ROUND3:
+      SEM_OUT(0) = py_round3(SEM_IN(0));
+      break;
+    case AIGAR_SEM_SUM: {
+      double t[kMaxCells];
+#pragma unroll
+      for (int k = 0; k < kMaxCells; k++) t[k] = SEM_IN(k);
+      int cnt = (int)SEM_IN(kMaxCells);
+      cnt = cnt < 0 ? 0 : (cnt > kMaxCells ? kMaxCells : cnt);  // (the array's length)
+      SEM_OUT(0) = np_sum(t, cnt);
+      NpAcc acc;
+#pragma unroll
+      for (int k = 0; k < kMaxCells; k++)  // (k a constant, as at add's call sites)
+        if (k < cnt) acc.add(k, cnt, t[k]);
+      SEM_OUT(1) = acc.sum(cnt);
+    } break;
+    case AIGAR_SEM_RADIUS:
+      SEM_OUT(0) = radius_of(SEM_IN(0));
+      SEM_OUT(1) = pellet_radius(SEM_IN(0));
+      break;
+    case AIGAR_SEM_BUCKET: {
+      const double c = SEM_IN(0);
+      const int cols = (int)SEM_IN(1);
+      SEM_OUT(0) = (double)bucket_floor_s(c);
+      SEM_OUT(1) = c >= 0 ? (double)bucket_floor(c) : -1.0;  // (bucket_floor: c >= 0 only)
+      SEM_OUT(2) = c >= 0 ? (double)center_bucket_coord(c, cols) : -1.0;
+    } break;
+    case AIGAR_SEM_FOOTPRINT: {
+      const Rect r = footprint(SEM_IN(0), SEM_IN(1), SEM_IN(2), (int)SEM_IN(3));
+      SEM_OUT(0) = (double)r.x0;
+      SEM_OUT(1) = (double)r.x1;
+      SEM_OUT(2) = (double)r.y0;
+      SEM_OUT(3) = (double)r.y1;
+    } break;
+    case AIGAR_SEM_MOVE: {
+      double vx, vy, c, s;
+      set_move_direction(SEM_IN(0), SEM_IN(1), SEM_IN(2), SEM_IN(3), SEM_IN(4), SEM_IN(5), vx, vy, c, s);
+      SEM_OUT(0) = vx;
+      SEM_OUT(1) = vy;
+      SEM_OUT(2) = c;
+      SEM_OUT(3) = s;
+    } break;
+    case AIGAR_SEM_MOMENTUM: {
+      double svx, svy;
+      int svc;
+      add_momentum(SEM_IN(0), SEM_IN(1), SEM_IN(2), SEM_IN(3), SEM_IN(4), SEM_IN(5), SEM_IN(6), svx, svy, svc);
+      SEM_OUT(0) = svx;
+      SEM_OUT(1) = svy;
+    } break;
+    case AIGAR_SEM_MERGE_TIME:
+      SEM_OUT(0) = merge_time_for(SEM_IN(0), SEM_IN(1));
+      break;
+    case AIGAR_SEM_PHILOX: {
+      uint64_t w[4];
+      philox(aigar_math::as_u64(SEM_IN(0)), aigar_math::as_u64(SEM_IN(1)), aigar_math::as_u64(SEM_IN(2)),
+             aigar_math::as_u64(SEM_IN(3)), aigar_math::as_u64(SEM_IN(4)), aigar_math::as_u64(SEM_IN(5)), w);
+#pragma unroll
+      for (int k = 0; k < 4; k++) SEM_OUT(k) = aigar_math::as_double(w[k]);
+      SEM_OUT(4) = u01(w[0]);
+      SEM_OUT(5) = (double)ph_randint(w[0], SEM_IN(6), SEM_IN(7));
+    } break;
+    case AIGAR_SEM_TRIG_FORMS: {
+      const double y = SEM_IN(0), x = SEM_IN(1);
+      SEM_OUT(0) = aigar_math::atan2_glibc(y, x);
+      SEM_OUT(1) = aigar_math::atan2_glibc_flat(y, x);
+      SEM_OUT(2) = aigar_math::sin_glibc(x);
+      SEM_OUT(3) = aigar_math::cos_glibc(x);
+      double s, c;
+      aigar_math::sincos_glibc(x, s, c);
+      SEM_OUT(4) = s;
+      SEM_OUT(5) = c;
+    } break;
+    default:
+      break;
+  }
+#undef SEM_IN
+#undef SEM_OUT
+}
+
+extern "C" int aigar_selftest_sem(int op, const double *in, int in_cols, double *out, int out_cols, int n) {
+  if (op < 0 || op >= AIGAR_SEM_N_OPS) return fail("selftest_sem: op %d is none of 0..%d", op, AIGAR_SEM_N_OPS - 1);
+  if (in_cols != kSemOps[op].in_cols) return fail("selftest_sem: in_cols %d, op %d takes %d", in_cols, op, kSemOps[op].in_cols);
+  if (out_cols != kSemOps[op].out_cols)
+    return fail("selftest_sem: out_cols %d, op %d gives %d", out_cols, op, kSemOps[op].out_cols);
+  if (!in) return fail("selftest_sem: in is null");
+  if (!out) return fail("selftest_sem: out is null");
+  if (n < 0) return fail("selftest_sem: n %d is negative", n);
+  if (n == 0) return 0;
+  double *di = nullptr, *dout = nullptr;
+  const size_t bi = sizeof(double) * (size_t)in_cols * n, bo = sizeof(double) * (size_t)out_cols * n;
+  HIPCHK(hipMalloc(&di, bi));
+  HIPCHK(hipMalloc(&dout, bo));
+  HIPCHK(hipMemcpy(di, in, bi, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(dout, 0, bo));
+  hipLaunchKernelGGL(k_selftest_sem, dim3((n + 255) / 256), dim3(256), 0, 0, op, di, dout, n);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(out, dout, bo, hipMemcpyDeviceToHost));
+  (void)hipFree(di);
+  (void)hipFree(dout);
+  return 0;
+}

@@ -874,6 +874,45 @@ int aigar_selftest_log(const double *x, double *out, int n);
  * out[0, n) = atan2(y, x), out[n, 2n) = sin(x), out[2n, 3n) = cos(x). */
 int aigar_selftest_trig(const double *y, const double *x, double *out, int n);
 
+/* Diagnostics: evaluate the device's per-entity helpers (aigar_sem.h) and exact integer
+ * helpers (aigar_math.h) on host arrays, one element per thread, the header functions
+ * themselves.  in is [in_cols][n] and out is [out_cols][n], both of 8-byte words: values
+ * are doubles, integers come back as exact doubles, and the 64-bit words of the Philox op
+ * are bit patterns.  Each op fixes its column counts (inputs -> outputs):
+ *   MOD_POS        a, b                     -> mod_pos(a, b, 1.0 / b)
+ *   TRUNC_DIV_POS  x, b                     -> trunc_div_pos(x, b, 1.0 / b)
+ *   PY_MOD         a, b                     -> py_mod
+ *   ROUND3         v                        -> py_round3
+ *   SUM            16 terms, count (0..16)  -> np_sum, NpAcc fed term by term
+ *   RADIUS         m                        -> radius_of, pellet_radius
+ *   BUCKET         c, cols                  -> bucket_floor_s; where c >= 0 (else -1):
+ *                                              bucket_floor, center_bucket_coord
+ *   FOOTPRINT      px, py, rad, size        -> x0, x1, y0, y1
+ *   MOVE           x, y, m, r, cpx, cpy     -> vx, vy, c, s of set_move_direction
+ *   MOMENTUM       x, y, cpx, cpy, w, h, orig_r -> svx, svy of add_momentum
+ *   MERGE_TIME     f, m                     -> merge_time_for
+ *   PHILOX         c0..c3, k0, k1, lo, hi   -> the 4 output words, u01(out0),
+ *                                              ph_randint(out0, lo, hi)
+ *   TRIG_FORMS     y, x                     -> atan2_glibc, atan2_glibc_flat, sin_glibc(x),
+ *                                              cos_glibc(x), sincos_glibc(x)'s sin and cos
+ * An unknown op, column counts that are not the op's, a null pointer or a negative n
+ * return < 0 with a message that names the argument; n == 0 succeeds. */
+#define AIGAR_SEM_MOD_POS 0
+#define AIGAR_SEM_TRUNC_DIV_POS 1
+#define AIGAR_SEM_PY_MOD 2
+#define AIGAR_SEM_ROUND3 3
+#define AIGAR_SEM_SUM 4
+#define AIGAR_SEM_RADIUS 5
+#define AIGAR_SEM_BUCKET 6
+#define AIGAR_SEM_FOOTPRINT 7
+#define AIGAR_SEM_MOVE 8
+#define AIGAR_SEM_MOMENTUM 9
+#define AIGAR_SEM_MERGE_TIME 10
+#define AIGAR_SEM_PHILOX 11
+#define AIGAR_SEM_TRIG_FORMS 12
+#define AIGAR_SEM_N_OPS 13
+int aigar_selftest_sem(int op, const double *in, int in_cols, double *out, int out_cols, int n);
+
 #ifdef __cplusplus
 }
 #endif

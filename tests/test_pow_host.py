@@ -35,7 +35,8 @@ def test_mod_pos_matches_python_float_mod(tmp_path):
 def test_trunc_div_pos_matches_division(tmp_path):
     """aigar_math::trunc_div_pos (nearest integer of x * (1 / b) + an exact fma
     residual test) == int(x / b) on the observation's mask-loop operands and next
-    to every k * b (host build; the device runs the same header)."""
+    to every k * b (host build; tests/test_gpu_sem.py runs the device's compile of the same
+    header on the same operands)."""
     exe = str(tmp_path / "check_trunc_div")
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-I",
                            os.path.join(ROOT, "aigar_amd", "csrc"),

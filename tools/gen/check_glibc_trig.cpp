@@ -83,8 +83,20 @@ int main(int argc, char **argv) {
       check_sc(a);
       check_sc(-a);
     }
+  // ... and where __sin / __cos switch: they compare the high word alone, so their bounds are
+  // the constants above cut to 32 bits, up to 2^-21 below them
+  const uint64_t words[] = {0x3e400000, 0x3e500000, 0x3feb6000, 0x400368fd, 0x419921fb};
+  for (uint64_t w : words)
+    for (int k = -300; k <= 300; k++) {
+      const double a = as_double((w << 32) + (uint64_t)(int64_t)k);
+      check_sc(a);
+      check_sc(-a);
+    }
   for (int k = 0; k < 110; k++)
-    for (int e = -64; e <= 64; e++) check_sc(k / 128.0 + e * 0x1p-53);
+    for (int e = -64; e <= 64; e++) {
+      check_sc(k / 128.0 + e * 0x1p-53);          // a row's centre
+      check_sc((k + 0.5) / 128.0 + e * 0x1p-53);  // where the row changes
+    }
   for (int d = 0; d < 360; d++) check_sc(d * (M_PI / 180.0));  // numpy.deg2rad(randint(0, 360)) (field.py:363)
   for (long it = 0; it < n; it++) {
     const int kind = (int)(it % 8);

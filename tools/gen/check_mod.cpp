@@ -1,6 +1,8 @@
 // Host check: aigar_math::mod_pos(a, b, 1/b) == Python's a % b (fmod, +0 for a
 // zero remainder) for a >= 0, b > 0: random values, exact multiples and their
-// neighbours, for the bucket size 20 and random grid-square sizes.
+// neighbours, for the bucket size 20 and random grid-square sizes.  (Host build;
+// tests/test_gpu_sem.py runs the same families, restated in tests/math_cases.py,
+// through the device's compile of the header.)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>

@@ -3,7 +3,10 @@
 // from a multiple of the square size b by repeated addition, so x / b sits next
 // to an integer every time), and on adversarial operands: k * b +- a few ulps,
 // the midpoints between an integer and its predecessor, powers of two.
-// Prints "checks=<n> fallbacks=<f> mismatches=<m>"; any mismatch fails.
+// Prints "checks=<n> fallbacks=<f> mismatches=<m>"; any mismatch fails.  (fallbacks
+// counts residuals exactly on the midpoint: 0, as aigar_math.h argues it must be.)
+// Host build; tests/test_gpu_sem.py runs the same families, restated in
+// tests/math_cases.py, through the device's compile of the header.
 // g++ -O2 -std=c++17 -ffp-contract=off -I aigar_amd/csrc tools/gen/check_trunc_div.cpp -o /tmp/ctd
 #include <cmath>
 #include <cstdio>
