@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/aigar.h"
@@ -106,6 +107,105 @@ int rccl_load(const char *path) {
 }
 }  // namespace
 
+// ---- captured graphs
+// A slot owns one executable graph.  Every entry point that replays a graph keeps
+// it in a slot, and there is one rule for letting a graph go (drop): the handle's
+// stream is synchronised first, since replays of the graph may still be queued.
+struct GraphSlot {
+  hipGraphExec_t exec = nullptr;
+  void drop(aigar_handle *h);
+  hipError_t launch(const aigar_handle *h) const;
+};
+// ... together with the byte image of the key it was captured for: everything
+// the captured launches bake in -- parameters by value, buffers by pointer.  A key
+// is a plain struct built in cleared storage (key_clear), whose struct members are
+// set with key_put, and it is stored and compared as bytes (memcpy, memcmp): the
+// comparison reads no padding that the language leaves unspecified.
+template <class K>
+struct KeyedSlot : GraphSlot {
+  static_assert(std::is_trivially_copyable_v<K>, "a graph key is moved and compared as bytes");
+  unsigned char image[sizeof(K)] = {};
+  bool holds(const K &k) const { return exec && memcmp(image, &k, sizeof(K)) == 0; }
+  // the graph of k: captured from issue(stream) unless the slot holds it; false: the capture failed
+  template <class F>
+  bool ensure(aigar_handle *h, const K &k, F issue);
+};
+template <class K>
+static void key_clear(K &k) {
+  static_assert(std::is_trivially_copyable_v<K>, "a graph key is moved and compared as bytes");
+  memset(&k, 0, sizeof k);
+}
+template <class T>
+static void key_put(T &member, const T &v) {
+  memcpy(&member, &v, sizeof(T));
+}
+struct StepKey {  // aigar_step: one Field.update
+  int rounds;  // food_rounds
+};
+struct RunKey {  // aigar_run, aigar_tile_run: one whole step
+  aigar_run_params p;
+  void *out;
+  int dtype;  // -1: no observation
+  int extra;  // aigar_tile_run's extra passes
+};
+struct TileKey {  // aigar_tile_begin, aigar_tile_end: the tick before the first / after the last exchange
+  aigar_run_params p;  // (tile_end: none)
+  const void *box[2];  // the message buffers (aigar_tile_set_buffers)
+  void *out;           // (tile_begin: none)
+  int dtype;           // -1: no observation
+};
+struct EnvKey {  // aigar_env_step*: one learner decision
+  const double *act;
+  int n_act, enable_split, skip, dtype;
+  aigar_reward_params prm;
+  double *reward;
+  void *obs;
+  aigar_env_params envp;
+  int n_greedy, n_random;
+  aigar_pixel_params pix;  // side 0: the grid row
+  uint32_t *pix_hist;
+  const void *exp;  // the replay memory the decision appends to (null: none)
+  const double *exp_act;  // ... and the action rows it stores, [NP][exp_n_act]
+  int exp_n_act;
+  // aigar_env_step_q: the selection in front of the decision (q null: none)
+  const void *q;
+  const double *explore, *u;
+  int32_t *idx_out;
+  double *val_out;
+  Decide dec;
+  // aigar_env_step_ac: the exploration noise in front of the decision (mu null: none)
+  const void *mu;
+  const double *nstd, *nu;
+  double *noisy;
+  const double *exp_extra;  // the transitions' fifth field, [NP][exp_n_act] (null: invalid)
+  int nT, pad;
+  Noise noi;
+  // aigar_env_step_net: the acting network in front of either (n_layers 0: none)
+  Net net;
+  // ... with a conv part in front of it (aigar_net_config_cnn; n_conv 0: none)
+  Conv conv;
+};
+
+// A feature's device buffers, allocated one by one and freed together.
+struct DevBlock {
+  std::vector<void *> bufs;
+  // null: out of device memory (the HIP error is cleared); zero: cleared on stream s
+  void *alloc(size_t bytes, bool zero, hipStream_t s) {
+    void *m = nullptr;
+    if (hipMalloc(&m, bytes ? bytes : 1) != hipSuccess) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+    bufs.push_back(m);
+    if (zero) (void)hipMemsetAsync(m, 0, bytes, s);
+    return m;
+  }
+  void release() {
+    for (void *m : bufs) (void)hipFree(m);
+    bufs.clear();
+  }
+};
+
 struct aigar_handle {
   aigar_config cfg;
   Dev d;
@@ -119,7 +219,6 @@ struct aigar_handle {
   // round exits at once but costs a dependent launch
   int rounds = 0;
   bool greedy_seen = false;
-  int graph_rounds = 0;  // the rounds the step graph was captured with
   int64_t *scr_k = nullptr;
   int *scr_v = nullptr;
   double *d_cmd = nullptr, *d_stats = nullptr;
@@ -156,17 +255,13 @@ struct aigar_handle {
   // C4: the tick up to the first exchange and the tick after the last one, as
   // graphs (re-captured when the policy, the observation buffer or the message
   // buffers change)
-  hipGraphExec_t tb_graph = nullptr, te_graph = nullptr;
-  aigar_run_params tb_key{};
-  const void *tb_box[2] = {nullptr, nullptr}, *te_box[2] = {nullptr, nullptr};
-  void *te_out = nullptr;
-  int te_dtype = -2;
+  KeyedSlot<TileKey> tb, te;
   bool profile = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // timer name -> recorded (start, stop) event pairs, resolved lazily
   std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> marks;
   std::vector<hipEvent_t> event_pool;
-  hipGraphExec_t graph = nullptr;
+  KeyedSlot<StepKey> step;  // aigar_step: one Field.update as a graph
   hipStream_t cap_stream = nullptr;  // private stream graphs are captured on (the caller's may be the null stream)
   bool use_graph = true;  // AIGAR_NO_GRAPH=1 disables (direct launches)
   // C4 tile phases as graphs (AIGAR_TILE_GRAPH=1): measured no faster than direct
@@ -181,75 +276,46 @@ struct aigar_handle {
   bool loopback = false;  // timing rehearsal: the exchange copies this tile's message to its own slot only
   bool cmd_ready = false;  // this tick's Greedy commands were exchanged and applied (aigar_tile_apply_commands)
   bool cmd_pending = false;  // aigar_tile_policy wrote a command message that was not applied yet
-  hipGraphExec_t tr_graph = nullptr;
-  aigar_run_params tr_key{};
-  void *tr_out = nullptr;
-  int tr_dtype = -2, tr_extra = -1;
+  KeyedSlot<RunKey> tr;
   bool tr_failed = false;
   // aigar_run: one whole env step (policy + Field.update + observation) as a graph
-  hipGraphExec_t run_graph = nullptr;
-  hipGraphExec_t run_graph_u = nullptr;  // run_unroll steps in one graph (same key)
+  KeyedSlot<RunKey> run;
+  GraphSlot run_u;  // run_unroll steps in one graph (keyed off run's key: dropped with it)
   // AIGAR_RUN_UNROLL (default 4): each graph launch costs an inter-graph gap on
   // the device that a node boundary inside a graph does not (C3 A/B,
   // profiles/r05_ab_notes.txt v30: 1 -> 4 steps per graph 42.5 -> 44.4 M env-steps/s)
   int run_unroll = 4;
   bool run_u_tried = false;  // the unrolled graph of this key was captured (or its capture failed)
-  aigar_run_params run_key{};
-  void *run_out = nullptr;
-  int run_dtype = -1;
   // aigar_env_step: one learner decision (skip + 1 ticks) as a graph
-  hipGraphExec_t env_graph = nullptr;
-  struct EnvKey {
-    const double *act;
-    int n_act, enable_split, skip, dtype;
-    aigar_reward_params prm;
-    double *reward;
-    void *obs;
-    aigar_env_params envp;
-    int n_greedy, n_random;
-    aigar_pixel_params pix;  // side 0: the grid row
-    uint32_t *pix_hist;
-    const void *exp;  // the replay memory the decision appends to (null: none)
-    const double *exp_act;  // ... and the action rows it stores, [NP][exp_n_act]
-    int exp_n_act;
-    // aigar_env_step_q: the selection in front of the decision (q null: none)
-    const void *q;
-    const double *explore, *u;
-    int32_t *idx_out;
-    double *val_out;
-    Decide dec;
-    // aigar_env_step_ac: the exploration noise in front of the decision (mu null: none)
-    const void *mu;
-    const double *nstd, *nu;
-    double *noisy;
-    const double *exp_extra;  // the transitions' fifth field, [NP][exp_n_act] (null: invalid)
-    int nT, pad;
-    Noise noi;
-    // aigar_env_step_net: the acting network in front of either (n_layers 0: none)
-    Net net;
-    // ... with a conv part in front of it (aigar_net_config_cnn; n_conv 0: none)
-    Conv conv;
-  } env_key{};
+  KeyedSlot<EnvKey> env;
   // aigar_decide_config: the Q-learning bots' action selection (decide.inc; n_out 0: off)
   Decide dec{};
-  std::vector<void *> dec_allocs;
+  DevBlock dec_mem;
   // aigar_noise_config: the actor-critic learners' exploration noise (noise.inc; n_act 0: off)
   Noise noi{};
-  std::vector<void *> noi_allocs;
+  DevBlock noi_mem;
   // aigar_net_config: the learners' acting network (net.inc; n_layers 0: off)
   Net net{};
-  std::vector<void *> net_allocs;
-  float *net_stage = nullptr;  // aigar_net_set_weights' staging of host weights (one of net_allocs)
+  DevBlock net_mem;  // ... and the conv part's buffers
+  float *net_stage = nullptr;  // aigar_net_set_weights' staging of host weights (one of net_mem)
   // aigar_net_config_cnn: the conv part in front of it (conv.inc; n_conv 0: off)
   Conv conv{};
-  std::vector<void *> conv_allocs;
-  float *conv_stage = nullptr;  // aigar_net_set_conv_weights' staging (one of conv_allocs)
+  float *conv_stage = nullptr;  // aigar_net_set_conv_weights' staging (one of net_mem)
   // aigar_exp_config: the learners' replay memory (replay.inc; cap 0: off)
   Exp exp;
-  std::vector<void *> exp_allocs;
+  DevBlock exp_mem;
   int *d_exp_off = nullptr;  // aigar_exp_add's slot offsets, [exp_off_n]
   size_t exp_off_n = 0;
+  GraphSlot *const slots[7] = {&step, &run, &run_u, &env, &tb, &te, &tr};
 };
+
+void GraphSlot::drop(aigar_handle *h) {
+  if (!exec) return;
+  (void)hipStreamSynchronize(h->stream);  // (no replay of the graph is pending)
+  (void)hipGraphExecDestroy(exec);
+  exec = nullptr;
+}
+hipError_t GraphSlot::launch(const aigar_handle *h) const { return hipGraphLaunch(exec, h->stream); }
 
 extern "C" const char *aigar_last_error(void) { return g_err.c_str(); }
 extern "C" int aigar_abi_version(void) { return AIGAR_ABI_VERSION; }
@@ -295,10 +361,7 @@ static int obs_len_of(const aigar_config &c) {
 }
 
 static void free_all(aigar_handle *h) {
-  if (h->graph) (void)hipGraphExecDestroy(h->graph);
-  if (h->run_graph) (void)hipGraphExecDestroy(h->run_graph);
-  if (h->run_graph_u) (void)hipGraphExecDestroy(h->run_graph_u);
-  if (h->env_graph) (void)hipGraphExecDestroy(h->env_graph);
+  for (GraphSlot *g : h->slots) g->drop(h);
   for (void *p : h->allocs) (void)hipFree(p);
   h->allocs.clear();
   if (h->d_pix) (void)hipFree(h->d_pix);
@@ -307,25 +370,9 @@ static void free_all(aigar_handle *h) {
   h->pix_bytes = 0;
   if (h->d_pix_hist) (void)hipFree(h->d_pix_hist);
   h->d_pix_hist = nullptr;
-  for (void *p : h->exp_allocs) (void)hipFree(p);
-  h->exp_allocs.clear();
-  for (void *p : h->dec_allocs) (void)hipFree(p);
-  h->dec_allocs.clear();
-  h->dec = Decide{};
-  for (void *p : h->noi_allocs) (void)hipFree(p);
-  h->noi_allocs.clear();
-  h->noi = Noise{};
-  for (void *p : h->net_allocs) (void)hipFree(p);
-  h->net_allocs.clear();
-  h->net = Net{};
-  h->net_stage = nullptr;
-  for (void *p : h->conv_allocs) (void)hipFree(p);
-  h->conv_allocs.clear();
-  h->conv = Conv{};
-  h->conv_stage = nullptr;
+  for (DevBlock *m : {&h->exp_mem, &h->dec_mem, &h->noi_mem, &h->net_mem}) m->release();
   if (h->d_exp_off) (void)hipFree(h->d_exp_off);
   h->d_exp_off = nullptr;
-  h->exp = Exp{};
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->ev_x) (void)hipEventDestroy(h->ev_x);
@@ -333,9 +380,6 @@ static void free_all(aigar_handle *h) {
     if (e) (void)hipEventDestroy(e);
   if (h->h_reset) (void)hipHostFree(h->h_reset);
   h->h_reset = nullptr;
-  if (h->tb_graph) (void)hipGraphExecDestroy(h->tb_graph);
-  if (h->te_graph) (void)hipGraphExecDestroy(h->te_graph);
-  if (h->tr_graph) (void)hipGraphExecDestroy(h->tr_graph);
   if (h->rccl_comm && g_rccl.comm_destroy) (void)g_rccl.comm_destroy(h->rccl_comm);
   h->rccl_comm = nullptr;
   for (auto &m : h->marks) {
@@ -793,6 +837,15 @@ static hipGraphExec_t capture_graph(aigar_handle *h, F launch) {
   }
   return ge;
 }
+template <class K>
+template <class F>
+bool KeyedSlot<K>::ensure(aigar_handle *h, const K &k, F issue) {
+  if (holds(k)) return true;
+  drop(h);
+  exec = capture_graph(h, issue);
+  memcpy(image, &k, sizeof(K));
+  return exec != nullptr;
+}
 
 __global__ void k_step_begin(Dev d) {
   int a = blockIdx.x * blockDim.x + threadIdx.x;
@@ -804,16 +857,13 @@ static int food_rounds(const aigar_handle *h) { return h->rounds > 0 ? h->rounds
 // food_rounds() follows the handle's history: when a Greedy policy first runs, the
 // graphs captured with the old round count are dropped (recaptured at their next
 // call), so a step graph and the tile passes never mix round counts.  (The
-// Field.update graph of aigar_step keeps its own graph_rounds check.)
+// Field.update graph of aigar_step has the round count in its key.)
 static void note_greedy(aigar_handle *h) {
   if (h->greedy_seen) return;
   h->greedy_seen = true;
   if (h->rounds > 0) return;  // (the round count is fixed: nothing changes)
-  (void)hipStreamSynchronize(h->stream);  // (no replay of a graph being destroyed is pending)
-  for (hipGraphExec_t *g : {&h->run_graph, &h->run_graph_u, &h->env_graph, &h->tb_graph, &h->te_graph, &h->tr_graph}) {
-    if (*g) (void)hipGraphExecDestroy(*g);
-    *g = nullptr;
-  }
+  for (GraphSlot *g : h->slots)
+    if (g != &h->step) g->drop(h);
   h->run_u_tried = false;
 }
 
@@ -824,19 +874,16 @@ extern "C" int aigar_step(aigar_handle *h, int n_ticks) {
   if (h->d.flags & AIGAR_FLAG_EVENTS)  // the event log restarts every step
     hipLaunchKernelGGL(k_step_begin, dim3((h->d.A + 63) / 64), dim3(64), 0, h->stream, h->d);
   const int rounds = food_rounds(h);
-  if (h->graph && h->graph_rounds != rounds) {  // (the population changed the eat phase's rounds)
-    (void)hipGraphExecDestroy(h->graph);
-    h->graph = nullptr;
-  }
-  if (h->use_graph && !h->graph && !h->graph_failed && n_ticks > 0) {
-    // capture one Field.update() (~25 kernel launches) once; replay it per tick
-    h->graph = capture_graph(h, [&](hipStream_t cs) { launch_tick(h->d, cs, rounds, h->scr_k, h->scr_v); });
-    if (!h->graph) h->graph_failed = true;
-    h->graph_rounds = rounds;
-  }
+  StepKey k;
+  key_clear(k);
+  k.rounds = rounds;  // (the population changes the eat phase's rounds)
+  // capture one Field.update() (~25 kernel launches) once; replay it per tick
+  if (h->use_graph && !h->graph_failed && n_ticks > 0 &&
+      !h->step.ensure(h, k, [&](hipStream_t cs) { launch_tick(h->d, cs, rounds, h->scr_k, h->scr_v); }))
+    h->graph_failed = true;
   for (int t = 0; t < n_ticks; t++) {
     Mark m(h, "tick");
-    if (h->graph) HIPCHK(hipGraphLaunch(h->graph, h->stream));
+    if (h->step.exec) HIPCHK(h->step.launch(h));
     else launch_tick(h->d, h->stream, rounds, h->scr_k, h->scr_v);
   }
   HIPCHK(hipGetLastError());
@@ -880,40 +927,38 @@ extern "C" int aigar_run(aigar_handle *h, int n_steps, const aigar_run_params *p
   if (h->d.flags & AIGAR_FLAG_EVENTS)  // the event log restarts every call (all n_steps accumulate)
     hipLaunchKernelGGL(k_step_begin, dim3((h->d.A + 63) / 64), dim3(64), 0, h->stream, h->d);
   if (p->policy == AIGAR_POLICY_GREEDY) note_greedy(h);  // (food_rounds)
-  const bool same = h->run_graph && memcmp(&h->run_key, p, sizeof *p) == 0 && h->run_out == obs_out &&
-                    h->run_dtype == (obs_out ? dtype : -1);
-  if (h->use_graph && !same && n_steps > 0) {
-    if (h->run_graph) (void)hipGraphExecDestroy(h->run_graph);
-    if (h->run_graph_u) (void)hipGraphExecDestroy(h->run_graph_u);
-    h->run_graph = capture_graph(h, [&](hipStream_t cs) { launch_env_step(h, cs, *p, obs_out, dtype); });
-    if (!h->run_graph) return fail("aigar_run: graph capture failed");
-    h->run_graph_u = nullptr;
+  RunKey k;
+  key_clear(k);
+  key_put(k.p, *p);
+  k.out = obs_out;
+  k.dtype = obs_out ? dtype : -1;
+  if (h->use_graph && n_steps > 0 && !h->run.holds(k)) {
+    h->run_u.drop(h);
     h->run_u_tried = false;
-    h->run_key = *p;
-    h->run_out = obs_out;
-    h->run_dtype = obs_out ? dtype : -1;
+    if (!h->run.ensure(h, k, [&](hipStream_t cs) { launch_env_step(h, cs, *p, obs_out, dtype); }))
+      return fail("aigar_run: graph capture failed");
   }
   // run_unroll > 1: the same step captured that many times in one graph -- one
   // graph launch, and one inter-graph gap, per run_unroll steps.  Captured at the
   // first call of the key that can use it; if that capture fails, the one-step
   // graph serves alone.
-  if (h->run_graph && !h->run_graph_u && !h->run_u_tried && h->run_unroll > 1 && n_steps >= h->run_unroll &&
+  if (h->run.exec && !h->run_u.exec && !h->run_u_tried && h->run_unroll > 1 && n_steps >= h->run_unroll &&
       !h->profile) {
     h->run_u_tried = true;
     // (the Greedy population: steps 1.. of the graph take the moves their previous
     // step's observation picked -- the first step, and the one-step graph, run the policy)
     const bool fuse = run_fuses_greedy(h, *p, obs_out);
-    h->run_graph_u = capture_graph(h, [&](hipStream_t cs) {
+    h->run_u.exec = capture_graph(h, [&](hipStream_t cs) {
       for (int k = 0; k < h->run_unroll; k++)
         launch_env_step(h, cs, *p, obs_out, dtype, fuse && k > 0, fuse && k + 1 < h->run_unroll);
     });
   }
   int t = 0;
-  if (h->run_graph_u && !h->profile)
-    for (; t + h->run_unroll <= n_steps; t += h->run_unroll) HIPCHK(hipGraphLaunch(h->run_graph_u, h->stream));
+  if (h->run_u.exec && !h->profile)
+    for (; t + h->run_unroll <= n_steps; t += h->run_unroll) HIPCHK(h->run_u.launch(h));
   for (; t < n_steps; t++) {
     Mark m(h, "run");
-    if (h->run_graph) HIPCHK(hipGraphLaunch(h->run_graph, h->stream));
+    if (h->run.exec) HIPCHK(h->run.launch(h));
     else launch_env_step(h, h->stream, *p, obs_out, dtype);
   }
   HIPCHK(hipGetLastError());
@@ -998,18 +1043,15 @@ extern "C" int aigar_tile_begin(aigar_handle *h, const aigar_run_params *p) {
     launch_tick_pre(h->d, s, h->scr_k, h->scr_v, &rp);
     launch_tile_pass(h->d, s, food_rounds(h), h->scr_k, h->scr_v, 1);
   };
-  const bool same = h->tb_graph && memcmp(&h->tb_key, p, sizeof *p) == 0 && h->tb_box[0] == h->d.outbox &&
-                    h->tb_box[1] == h->d.inbox;
-  if (h->tile_graph && !same) {
-    if (h->tb_graph) (void)hipGraphExecDestroy(h->tb_graph);
-    h->tb_graph = capture_graph(h, issue);
-    h->tb_key = *p;
-    h->tb_box[0] = h->d.outbox;
-    h->tb_box[1] = h->d.inbox;
-  }
+  TileKey k;
+  key_clear(k);
+  key_put(k.p, *p);
+  k.box[0] = h->d.outbox;
+  k.box[1] = h->d.inbox;
+  const bool graphed = h->tile_graph && h->tb.ensure(h, k, issue);
   {
     Mark m(h, "tile_begin");
-    if (h->tile_graph && h->tb_graph) HIPCHK(hipGraphLaunch(h->tb_graph, h->stream));
+    if (graphed) HIPCHK(h->tb.launch(h));
     else issue(h->stream);
   }
   h->pass_recs = 1 + h->d.tcap + h->d.hcap * h->d.hrec;  // (+ the observation-history hand-off slots)
@@ -1066,17 +1108,13 @@ extern "C" int aigar_tile_end(aigar_handle *h, void *obs_out, int dtype) {
     launch_tick_post(h->d, s, h->scr_k, h->scr_v);
     if (obs_out) launch_observe(h->d, s, obs_out, dtype, 0);
   };
-  const bool same = h->te_graph && h->te_out == obs_out && h->te_dtype == (obs_out ? dtype : -1) &&
-                    h->te_box[0] == h->d.outbox && h->te_box[1] == h->d.inbox;
-  if (h->use_graph && !same) {
-    if (h->te_graph) (void)hipGraphExecDestroy(h->te_graph);
-    h->te_graph = capture_graph(h, issue);
-    h->te_out = obs_out;
-    h->te_dtype = obs_out ? dtype : -1;
-    h->te_box[0] = h->d.outbox;
-    h->te_box[1] = h->d.inbox;
-  }
-  if (h->use_graph && h->te_graph) HIPCHK(hipGraphLaunch(h->te_graph, h->stream));
+  TileKey k;
+  key_clear(k);
+  k.box[0] = h->d.outbox;
+  k.box[1] = h->d.inbox;
+  k.out = obs_out;
+  k.dtype = obs_out ? dtype : -1;
+  if (h->use_graph && h->te.ensure(h, k, issue)) HIPCHK(h->te.launch(h));
   else issue(h->stream);
   HIPCHK(hipGetLastError());
   return 0;
@@ -1236,26 +1274,22 @@ extern "C" int aigar_tile_run(aigar_handle *h, int n_steps, const aigar_run_para
     hipLaunchKernelGGL(k_step_begin, dim3(1), dim3(64), 0, h->stream, h->d);
   h->pass_recs = 0;  // (the aigar_tile_* call sequence restarts at a tile_begin)
   h->cmd_pending = false;
-  const bool same = h->tr_graph && memcmp(&h->tr_key, p, sizeof *p) == 0 && h->tr_out == obs_out &&
-                    h->tr_dtype == (obs_out ? dtype : -1) && h->tr_extra == extra_passes;
-  if (h->use_graph && !h->profile && !same && !h->tr_failed && n_steps > 0) {
-    if (h->tr_graph) (void)hipGraphExecDestroy(h->tr_graph);
+  RunKey k;
+  key_clear(k);
+  key_put(k.p, *p);
+  k.out = obs_out;
+  k.dtype = obs_out ? dtype : -1;
+  k.extra = extra_passes;
+  if (h->use_graph && !h->profile && !h->tr_failed && n_steps > 0 && !h->tr.holds(k)) {
     h->rccl_bad = false;
-    h->tr_graph = capture_graph(h, [&](hipStream_t cs) { (void)issue_tile_step(h, cs, *p, extra_passes, obs_out, dtype); });
-    if (h->rccl_bad && h->tr_graph) {  // an all-gather refused the capture: direct launches from now on
-      (void)hipGraphExecDestroy(h->tr_graph);
-      h->tr_graph = nullptr;
-    }
-    if (!h->tr_graph) h->tr_failed = true;
-    h->tr_key = *p;
-    h->tr_out = obs_out;
-    h->tr_dtype = obs_out ? dtype : -1;
-    h->tr_extra = extra_passes;
+    h->tr.ensure(h, k, [&](hipStream_t cs) { (void)issue_tile_step(h, cs, *p, extra_passes, obs_out, dtype); });
+    if (h->rccl_bad) h->tr.drop(h);  // an all-gather refused the capture: direct launches from now on
+    if (!h->tr.exec) h->tr_failed = true;
   }
   for (int t = 0; t < n_steps; t++) {
-    if (h->tr_graph && !h->profile) {
+    if (h->tr.exec && !h->profile) {
       Mark m(h, "tile_step");
-      HIPCHK(hipGraphLaunch(h->tr_graph, h->stream));
+      HIPCHK(h->tr.launch(h));
     } else if (issue_tile_step(h, h->stream, *p, extra_passes, obs_out, dtype)) {
       return -1;
     }
@@ -1264,7 +1298,7 @@ extern "C" int aigar_tile_run(aigar_handle *h, int n_steps, const aigar_run_para
   return 0;
 }
 
-extern "C" int aigar_tile_run_graphed(aigar_handle *h) { return h && h->tr_graph ? 1 : 0; }
+extern "C" int aigar_tile_run_graphed(aigar_handle *h) { return h && h->tr.exec ? 1 : 0; }
 
 extern "C" int aigar_tile_loopback(aigar_handle *h) {
   if (need_tiled(h)) return -1;
@@ -1273,8 +1307,7 @@ extern "C" int aigar_tile_loopback(aigar_handle *h) {
   HIPCHK(hipMemsetAsync((void *)h->d.inbox, 0, (size_t)h->box_recs * h->d.ntiles * sizeof(TileRec), h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   h->loopback = true;
-  if (h->tr_graph) (void)hipGraphExecDestroy(h->tr_graph);
-  h->tr_graph = nullptr;
+  h->tr.drop(h);
   h->tr_failed = false;
   return 0;
 }
@@ -1317,7 +1350,7 @@ static void launch_exp_latch(aigar_handle *h, hipStream_t s, const void *obs, in
   hipLaunchKernelGGL(k_exp_latch, dim3(h->d.NP), dim3(256), 0, s, h->exp, obs, dtype, mask);
 }
 
-static void launch_env_decision(aigar_handle *h, hipStream_t s, const aigar_handle::EnvKey &k) {
+static void launch_env_decision(aigar_handle *h, hipStream_t s, const EnvKey &k) {
   for (int t = 0; t <= k.skip; t++) {
     if (t > 0) launch_rewards(h->d, s, k.reward, k.prm, 0, t == 1 ? 1 : 2);  // updateRewards (bot.py:166-168)
     launch_apply_actions(h->d, s, k.act, k.n_act, k.enable_split, t > 0, t == 0);
@@ -1338,7 +1371,7 @@ static void launch_env_decision(aigar_handle *h, hipStream_t s, const aigar_hand
 // The decision of aigar_env_step / aigar_env_step_q / aigar_env_step_ac: the key's common
 // part, then the replay of its graph (k.q: the selection's kernel in front, decide.inc;
 // k.mu: the noise's, noise.inc).
-static int env_step_keyed(aigar_handle *h, aigar_handle::EnvKey &k, int enable_split, int skip,
+static int env_step_keyed(aigar_handle *h, EnvKey &k, int enable_split, int skip,
                           const aigar_reward_params *p, double *reward_out, void *obs_out, int dtype,
                           int n_decisions = 1) {
   if (skip < 0) return fail("env_step: skip < 0");
@@ -1347,13 +1380,13 @@ static int env_step_keyed(aigar_handle *h, aigar_handle::EnvKey &k, int enable_s
   k.enable_split = enable_split ? 1 : 0;
   k.skip = skip;
   k.dtype = dtype;
-  k.prm = *p;
+  key_put(k.prm, *p);
   k.reward = reward_out;
   k.obs = obs_out;
-  k.envp = h->envp;
+  key_put(k.envp, h->envp);
   k.n_greedy = h->n_greedy;
   k.n_random = h->n_random;
-  k.pix = h->pix;
+  key_put(k.pix, h->pix);
   k.pix_hist = h->d_pix_hist;
   k.exp = h->exp.cap ? h->exp.ctl : nullptr;
   if (!k.q && !k.mu) {  // (the selection stores the index, [NP][1]; the noise its noisy rows)
@@ -1383,14 +1416,9 @@ static int env_step_keyed(aigar_handle *h, aigar_handle::EnvKey &k, int enable_s
   if (!h->use_graph) {
     for (int i = 0; i < n_decisions; i++) launch(h->stream);
   } else {
-    if (!h->env_graph || memcmp(&h->env_key, &k, sizeof k) != 0) {
-      if (h->env_graph) (void)hipGraphExecDestroy(h->env_graph);
-      h->env_graph = capture_graph(h, launch);
-      if (!h->env_graph) return fail("env_step: graph capture failed");
-      h->env_key = k;
-    }
+    if (!h->env.ensure(h, k, launch)) return fail("env_step: graph capture failed");
     Mark m(h, "env_step");
-    for (int i = 0; i < n_decisions; i++) HIPCHK(hipGraphLaunch(h->env_graph, h->stream));
+    for (int i = 0; i < n_decisions; i++) HIPCHK(h->env.launch(h));
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -1400,22 +1428,30 @@ extern "C" int aigar_env_step(aigar_handle *h, const double *act, int n_act, int
                               const aigar_reward_params *p, double *reward_out, void *obs_out, int dtype) {
   if (!h || !act || !p || !reward_out || !obs_out) return fail("null argument");
   if (n_act < 2 || n_act > 4) return fail("env_step: n_act must be 2, 3 or 4");
-  aigar_handle::EnvKey k{};
+  EnvKey k;
+  key_clear(k);
   k.act = act;
   k.n_act = n_act;
   return env_step_keyed(h, k, enable_split, skip, p, reward_out, obs_out, dtype);
 }
 
 // ------------------------------------------------------------ action selection
-static void dec_free(aigar_handle *h) {
-  for (void *p : h->dec_allocs) (void)hipFree(p);
-  h->dec_allocs.clear();
-  h->dec = Decide{};
+// A feature's entry points need the feature (on: its "configured?" flag, read once the handle is known)
+static int need(aigar_handle *h, bool on, const char *who, const char *what) {
+  if (!h) return fail("null handle");
+  return on ? 0 : fail("%s: %s", who, what);
+}
+// Every *_config begins here: nothing that reads the feature's buffers is pending,
+// and the decision graph goes.  Its key holds the buffers by pointer, and a freed
+// buffer can come back at the same address: the key alone would not notice.
+static int begin_reconfig(aigar_handle *h) {
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->env.drop(h);
+  return 0;
 }
 static int need_dec(aigar_handle *h, const char *who) {
-  if (!h) return fail("null handle");
-  if (!h->dec.n_out) return fail("%s: no action selection is configured (aigar_decide_config)", who);
-  return 0;
+  return need(h, h && h->dec.n_out, who, "no action selection is configured (aigar_decide_config)");
 }
 
 extern "C" int aigar_decide_config(aigar_handle *h, const aigar_decide_params *p, const double *actions) {
@@ -1427,11 +1463,9 @@ extern "C" int aigar_decide_config(aigar_handle *h, const aigar_decide_params *p
     if (p->strategy != 0 && p->strategy != 1) return fail("decide_config: strategy must be 0 (e-Greedy) or 1 (Boltzmann)");
     if (p->q_dtype != 0 && p->q_dtype != 1) return fail("decide_config: q_dtype must be 0 (float64) or 1 (float32)");
   }
-  HIPCHK(hipSetDevice(h->cfg.device));
-  HIPCHK(hipStreamSynchronize(h->stream));  // (no replay of the graph is pending)
-  if (h->env_graph) (void)hipGraphExecDestroy(h->env_graph);
-  h->env_graph = nullptr;
-  dec_free(h);
+  if (begin_reconfig(h)) return -1;
+  h->dec_mem.release();
+  h->dec = Decide{};
   if (!p) return 0;
   Decide c{};
   c.n_out = p->n_out;
@@ -1439,21 +1473,14 @@ extern "C" int aigar_decide_config(aigar_handle *h, const aigar_decide_params *p
   c.q_dtype = p->q_dtype;
   c.seed = p->seed;
   const size_t NP = (size_t)h->d.NP, nt = (size_t)c.n_out * 4;
-  void *m[3] = {nullptr, nullptr, nullptr};
-  const size_t bytes[3] = {nt * sizeof(double), NP * 4 * sizeof(double), NP * sizeof(double)};
-  for (int i = 0; i < 3; i++) {
-    if (hipMalloc(&m[i], bytes[i]) != hipSuccess) {
-      (void)hipGetLastError();
-      dec_free(h);
-      return fail("decide_config: out of device memory");
-    }
-    h->dec_allocs.push_back(m[i]);
+  c.table = (double *)h->dec_mem.alloc(nt * sizeof(double), false, h->stream);
+  c.act = (double *)h->dec_mem.alloc(NP * 4 * sizeof(double), true, h->stream);
+  c.idx = (double *)h->dec_mem.alloc(NP * sizeof(double), false, h->stream);
+  if (!c.table || !c.act || !c.idx) {
+    h->dec_mem.release();
+    return fail("decide_config: out of device memory");
   }
-  c.table = (double *)m[0];
-  c.act = (double *)m[1];
-  c.idx = (double *)m[2];
-  HIPCHK(hipMemcpyAsync(c.table, actions, bytes[0], hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemsetAsync(c.act, 0, bytes[1], h->stream));
+  HIPCHK(hipMemcpyAsync(c.table, actions, nt * sizeof(double), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_fill_d, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, h->stream, c.idx, NP, -1.0);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's table is read)
@@ -1471,12 +1498,9 @@ extern "C" int aigar_decide(aigar_handle *h, const void *q, const double *explor
   return 0;
 }
 
-extern "C" int aigar_env_step_q(aigar_handle *h, const void *q, const double *explore, const double *u,
-                                int enable_split, int skip, const aigar_reward_params *p, double *reward_out,
-                                void *obs_out, int dtype, int32_t *idx_out, double *val_out) {
-  if (need_dec(h, "env_step_q")) return -1;
-  if (!q || !explore || !p || !reward_out || !obs_out || !idx_out || !val_out) return fail("env_step_q: null argument");
-  aigar_handle::EnvKey k{};
+// The decision key's "selection in front" half: q is the caller's values or the network's output
+static void key_select(EnvKey &k, const aigar_handle *h, const void *q, const double *explore, const double *u,
+                       int32_t *idx_out, double *val_out) {
   k.act = h->dec.act;
   k.n_act = 4;
   k.q = q;
@@ -1484,22 +1508,25 @@ extern "C" int aigar_env_step_q(aigar_handle *h, const void *q, const double *ex
   k.u = u;
   k.idx_out = idx_out;
   k.val_out = val_out;
-  k.dec = h->dec;
+  key_put(k.dec, h->dec);
   k.exp_act = h->dec.idx;
   k.exp_n_act = 1;
+}
+
+extern "C" int aigar_env_step_q(aigar_handle *h, const void *q, const double *explore, const double *u,
+                                int enable_split, int skip, const aigar_reward_params *p, double *reward_out,
+                                void *obs_out, int dtype, int32_t *idx_out, double *val_out) {
+  if (need_dec(h, "env_step_q")) return -1;
+  if (!q || !explore || !p || !reward_out || !obs_out || !idx_out || !val_out) return fail("env_step_q: null argument");
+  EnvKey k;
+  key_clear(k);
+  key_select(k, h, q, explore, u, idx_out, val_out);
   return env_step_keyed(h, k, enable_split, skip, p, reward_out, obs_out, dtype);
 }
 
 // ------------------------------------------------------------ exploration noise
-static void noi_free(aigar_handle *h) {
-  for (void *p : h->noi_allocs) (void)hipFree(p);
-  h->noi_allocs.clear();
-  h->noi = Noise{};
-}
 static int need_noi(aigar_handle *h, const char *who) {
-  if (!h) return fail("null handle");
-  if (!h->noi.n_act) return fail("%s: no exploration noise is configured (aigar_noise_config)", who);
-  return 0;
+  return need(h, h && h->noi.n_act, who, "no exploration noise is configured (aigar_noise_config)");
 }
 
 extern "C" int aigar_noise_config(aigar_handle *h, const aigar_noise_params *p) {
@@ -1515,11 +1542,9 @@ extern "C" int aigar_noise_config(aigar_handle *h, const aigar_noise_params *p) 
       return fail("noise_config: Orn-Uhl needs finite theta and ou_mu and a finite dt >= 0 (got %g, %g, %g)", p->theta,
                   p->ou_mu, p->dt);
   }
-  HIPCHK(hipSetDevice(h->cfg.device));
-  HIPCHK(hipStreamSynchronize(h->stream));  // (no replay of the graph is pending)
-  if (h->env_graph) (void)hipGraphExecDestroy(h->env_graph);
-  h->env_graph = nullptr;
-  noi_free(h);
+  if (begin_reconfig(h)) return -1;
+  h->noi_mem.release();
+  h->noi = Noise{};
   if (!p) return 0;
   Noise c{};
   c.n_act = p->n_act;
@@ -1531,19 +1556,14 @@ extern "C" int aigar_noise_config(aigar_handle *h, const aigar_noise_params *p) 
   c.dt = p->type == AIGAR_NOISE_ORN_UHL ? p->dt : 0.0;
   c.seed = p->seed;
   const size_t bytes = (size_t)h->d.NP * 4 * sizeof(double);
-  void *m[3] = {nullptr, nullptr, nullptr};
-  for (int i = 0; i < 3; i++) {
-    if (hipMalloc(&m[i], bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      noi_free(h);
-      return fail("noise_config: out of device memory");
-    }
-    h->noi_allocs.push_back(m[i]);
-    HIPCHK(hipMemsetAsync(m[i], 0, bytes, h->stream));
+  c.act = (double *)h->noi_mem.alloc(bytes, true, h->stream);
+  c.raw = (double *)h->noi_mem.alloc(bytes, true, h->stream);
+  c.ou = (double *)h->noi_mem.alloc(bytes, true, h->stream);
+  if (!c.act || !c.raw || !c.ou) {
+    h->noi_mem.release();
+    return fail("noise_config: out of device memory");
   }
-  c.act = (double *)m[0];
-  c.raw = (double *)m[1];
-  c.ou = (double *)m[2];
+  HIPCHK(hipGetLastError());
   h->noi = c;
   return 0;
 }
@@ -1564,13 +1584,9 @@ extern "C" int aigar_noise(aigar_handle *h, const void *mu, int rows, const doub
   return 0;
 }
 
-extern "C" int aigar_env_step_ac(aigar_handle *h, const void *mu, const double *std, const double *u, int T,
-                                 int enable_split, int skip, const aigar_reward_params *p, double *reward_out,
-                                 void *obs_out, int dtype, double *noisy_out) {
-  if (need_noi(h, "env_step_ac")) return -1;
-  if (!mu || !std || !p || !reward_out || !obs_out) return fail("env_step_ac: null argument");
-  if (u && (T < 1 || T > kNoiseMaxT)) return fail("env_step_ac: T = %d is outside 1..%d", T, kNoiseMaxT);
-  aigar_handle::EnvKey k{};
+// The decision key's "noise in front" half: mu is the caller's actions or the network's output
+static void key_noise(EnvKey &k, const aigar_handle *h, const void *mu, const double *std, const double *u, int T,
+                      double *noisy_out) {
   k.act = h->noi.act;
   k.n_act = h->noi.n_act;
   k.mu = mu;
@@ -1578,29 +1594,35 @@ extern "C" int aigar_env_step_ac(aigar_handle *h, const void *mu, const double *
   k.nu = u;
   k.nT = u ? T : kNoiseOwnT;
   k.noisy = noisy_out;
-  k.noi = h->noi;
+  key_put(k.noi, h->noi);
   k.exp_act = h->noi.act;
   k.exp_n_act = h->noi.n_act;
   k.exp_extra = h->noi.store_raw ? h->noi.raw : nullptr;
+}
+
+extern "C" int aigar_env_step_ac(aigar_handle *h, const void *mu, const double *std, const double *u, int T,
+                                 int enable_split, int skip, const aigar_reward_params *p, double *reward_out,
+                                 void *obs_out, int dtype, double *noisy_out) {
+  if (need_noi(h, "env_step_ac")) return -1;
+  if (!mu || !std || !p || !reward_out || !obs_out) return fail("env_step_ac: null argument");
+  if (u && (T < 1 || T > kNoiseMaxT)) return fail("env_step_ac: T = %d is outside 1..%d", T, kNoiseMaxT);
+  EnvKey k;
+  key_clear(k);
+  key_noise(k, h, mu, std, u, T, noisy_out);
   return env_step_keyed(h, k, enable_split, skip, p, reward_out, obs_out, dtype);
 }
 
 // ------------------------------------------------------------ acting network
 static int pix_channels(const aigar_pixel_params &p);
 static void net_free(aigar_handle *h) {
-  for (void *p : h->net_allocs) (void)hipFree(p);
-  h->net_allocs.clear();
+  h->net_mem.release();
   h->net = Net{};
   h->net_stage = nullptr;
-  for (void *p : h->conv_allocs) (void)hipFree(p);
-  h->conv_allocs.clear();
   h->conv = Conv{};
   h->conv_stage = nullptr;
 }
 static int need_net(aigar_handle *h, const char *who) {
-  if (!h) return fail("null handle");
-  if (!h->net.n_layers) return fail("%s: no acting network is configured (aigar_net_config)", who);
-  return 0;
+  return need(h, h && h->net.n_layers, who, "no acting network is configured (aigar_net_config)");
 }
 static const char *net_act_name(int a) {
   switch (a) {
@@ -1631,10 +1653,7 @@ extern "C" int aigar_net_config(aigar_handle *h, const aigar_net_params *p) {
   }
   if (!h) return fail("null handle");
   if (p && h->d.tiled) return fail("net_config: a tiled handle has no acting network");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  HIPCHK(hipStreamSynchronize(h->stream));  // (no replay of the graph is pending)
-  if (h->env_graph) (void)hipGraphExecDestroy(h->env_graph);
-  h->env_graph = nullptr;
+  if (begin_reconfig(h)) return -1;
   net_free(h);
   if (!p) return 0;
   Net c{};
@@ -1643,16 +1662,7 @@ extern "C" int aigar_net_config(aigar_handle *h, const aigar_net_params *p) {
   c.hid_act = p->hidden_act;
   c.out_act = p->out_act;
   size_t stage = 0;
-  auto alloc = [&](size_t bytes) -> void * {
-    void *m = nullptr;
-    if (hipMalloc(&m, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
-    h->net_allocs.push_back(m);
-    (void)hipMemsetAsync(m, 0, bytes, h->stream);
-    return m;
-  };
+  auto alloc = [&](size_t bytes) { return h->net_mem.alloc(bytes, true, h->stream); };
   bool ok = true;
   for (int l = 0; l < c.n_layers && ok; l++) {
     c.in[l] = l ? p->units[l - 1] : p->n_in;
@@ -1762,16 +1772,7 @@ extern "C" int aigar_net_config_cnn(aigar_handle *h, const aigar_conv_params *cp
   if (aigar_net_config(h, p)) return -1;  // (its own checks; drops the graph and any earlier conv part)
   c.cap = std::max(h->d.NP, kConvMinRows);
   size_t stage = 0;
-  auto alloc = [&](size_t bytes) -> void * {
-    void *m = nullptr;
-    if (hipMalloc(&m, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
-    h->conv_allocs.push_back(m);
-    (void)hipMemsetAsync(m, 0, bytes, h->stream);
-    return m;
-  };
+  auto alloc = [&](size_t bytes) { return h->net_mem.alloc(bytes, true, h->stream); };
   bool ok = true;
   for (int l = 0; l < c.n_conv && ok; l++) {
     const size_t K = (size_t)c.k[l] * c.k[l] * (l ? c.filters[l - 1] : c.channels), F = c.filters[l];
@@ -1850,42 +1851,24 @@ extern "C" int aigar_env_step_net(aigar_handle *h, int head, const double *explo
       return fail("env_step_net: the network has %d inputs, the state %d values", c.in[0], h->d.L);
   }
   if (dtype != c.x_dtype) return fail("env_step_net: dtype %d differs from the network's x_dtype %d", dtype, c.x_dtype);
-  aigar_handle::EnvKey k{};
-  k.net = c;
-  k.conv = h->conv;
+  EnvKey k;
+  key_clear(k);
+  key_put(k.net, c);
+  key_put(k.conv, h->conv);
   if (head == AIGAR_NET_HEAD_Q) {
     if (need_dec(h, "env_step_net")) return -1;
     if (h->dec.q_dtype != 0) return fail("env_step_net: the action selection's q_dtype must be 0 (float64)");
     if (h->dec.n_out != n_out)
       return fail("env_step_net: the network has %d outputs, the action selection %d", n_out, h->dec.n_out);
     if (!idx_out || !val_out) return fail("env_step_net: null argument");
-    k.act = h->dec.act;
-    k.n_act = 4;
-    k.q = c.y;
-    k.explore = explore;
-    k.u = u;
-    k.idx_out = idx_out;
-    k.val_out = val_out;
-    k.dec = h->dec;
-    k.exp_act = h->dec.idx;
-    k.exp_n_act = 1;
+    key_select(k, h, c.y, explore, u, idx_out, val_out);
   } else {
     if (need_noi(h, "env_step_net")) return -1;
     if (h->noi.mu_dtype != 0) return fail("env_step_net: the exploration noise's mu_dtype must be 0 (float64)");
     if (h->noi.n_act != n_out)
       return fail("env_step_net: the network has %d outputs, the exploration noise n_act = %d", n_out, h->noi.n_act);
     if (u && (T < 1 || T > kNoiseMaxT)) return fail("env_step_net: T = %d is outside 1..%d", T, kNoiseMaxT);
-    k.act = h->noi.act;
-    k.n_act = h->noi.n_act;
-    k.mu = c.y;
-    k.nstd = explore;
-    k.nu = u;
-    k.nT = u ? T : kNoiseOwnT;
-    k.noisy = noisy_out;
-    k.noi = h->noi;
-    k.exp_act = h->noi.act;
-    k.exp_n_act = h->noi.n_act;
-    k.exp_extra = h->noi.store_raw ? h->noi.raw : nullptr;
+    key_noise(k, h, c.y, explore, u, T, noisy_out);
   }
   return env_step_keyed(h, k, enable_split, skip, p, reward_out, obs_out, dtype, n_decisions);
 }
@@ -2027,10 +2010,7 @@ extern "C" int aigar_pixel_config(aigar_handle *h, const aigar_pixel_params *p) 
     if (q.side < 1 || q.side > 84) return fail("pixel_config: side must be in [1, 84], got %d", q.side);
     if (q.flags & ~(AIGAR_PIX_RGB | AIGAR_PIX_LAST)) return fail("pixel_config: unknown flags 0x%x", q.flags);
   }
-  HIPCHK(hipSetDevice(h->cfg.device));
-  HIPCHK(hipStreamSynchronize(h->stream));  // (no replay of the graph, no reader of the history is pending)
-  if (h->env_graph) (void)hipGraphExecDestroy(h->env_graph);
-  h->env_graph = nullptr;
+  if (begin_reconfig(h)) return -1;  // (no reader of the history is pending either)
   if (q.side && !h->d_pix_ovf) {
     h->d_pix_ovf = dalloc<uint8_t>(h, h->d.NP);
     if (!h->d_pix_ovf) return fail("out of device memory");
@@ -2052,18 +2032,11 @@ extern "C" int aigar_pixel_config(aigar_handle *h, const aigar_pixel_params *p) 
 
 
 // ------------------------------------------------------------ replay memory
-static void exp_free(aigar_handle *h) {
-  for (void *p : h->exp_allocs) (void)hipFree(p);
-  h->exp_allocs.clear();
-  h->exp = Exp{};
-}
 static int exp_state_len(aigar_handle *h) {
   return h->pix.side ? h->pix.side * h->pix.side * pix_channels(h->pix) : h->d.L;
 }
 static int need_exp(aigar_handle *h, const char *who) {
-  if (!h) return fail("null handle");
-  if (!h->exp.cap) return fail("%s: no replay memory is configured (aigar_exp_config)", who);
-  return 0;
+  return need(h, h && h->exp.cap, who, "no replay memory is configured (aigar_exp_config)");
 }
 
 extern "C" int aigar_exp_config(aigar_handle *h, const aigar_exp_params *p) {
@@ -2080,11 +2053,9 @@ extern "C" int aigar_exp_config(aigar_handle *h, const aigar_exp_params *p) {
     if ((p->flags & AIGAR_EXP_PRIORITIZED) && (!(p->alpha >= 0) || !(p->beta > 0)))
       return fail("exp_config: need alpha >= 0 and beta > 0 (got %g, %g)", p->alpha, p->beta);
   }
-  HIPCHK(hipSetDevice(h->cfg.device));
-  HIPCHK(hipStreamSynchronize(h->stream));  // (no replay of the graph, no reader of the memory is pending)
-  if (h->env_graph) (void)hipGraphExecDestroy(h->env_graph);
-  h->env_graph = nullptr;
-  exp_free(h);
+  if (begin_reconfig(h)) return -1;  // (no reader of the memory is pending either)
+  h->exp_mem.release();
+  h->exp = Exp{};
   if (!on) return 0;
   Exp e;
   e.cap = p->capacity;
@@ -2101,56 +2072,43 @@ extern "C" int aigar_exp_config(aigar_handle *h, const aigar_exp_params *p) {
   const size_t cap = (size_t)e.cap, NP = (size_t)h->d.NP;
   bool ok = true;
   size_t total = 0;
-  auto get = [&](size_t bytes) -> void * {
-    void *q = nullptr;
+  auto get = [&](size_t bytes, bool zero) -> void * {
     if (!ok) return nullptr;
     total += bytes;
-    if (hipMalloc(&q, bytes ? bytes : 1) != hipSuccess) {
-      (void)hipGetLastError();
-      ok = false;
-      return nullptr;
-    }
-    h->exp_allocs.push_back(q);
+    void *q = h->exp_mem.alloc(bytes, zero, h->stream);
+    ok = q != nullptr;
     return q;
   };
-  e.s = (char *)get(cap * e.stride);
-  e.s2 = (char *)get(cap * e.stride);
-  e.a = (double *)get(cap * 4 * sizeof(double));
-  e.r = (double *)get(cap * sizeof(double));
-  e.done = (uint8_t *)get(cap);
+  // zeroed: the rows and the old states; the trees, the scratch and the fifth field are filled below
+  e.s = (char *)get(cap * e.stride, true);
+  e.s2 = (char *)get(cap * e.stride, true);
+  e.a = (double *)get(cap * 4 * sizeof(double), true);
+  e.r = (double *)get(cap * sizeof(double), true);
+  e.done = (uint8_t *)get(cap, true);
   if (e.prio) {
-    e.vsum = (double *)get(2 * (size_t)e.it_cap * sizeof(double));
-    e.vmin = (double *)get(2 * (size_t)e.it_cap * sizeof(double));
+    e.vsum = (double *)get(2 * (size_t)e.it_cap * sizeof(double), false);
+    e.vmin = (double *)get(2 * (size_t)e.it_cap * sizeof(double), false);
   }
   const bool extra = (p->flags & AIGAR_EXP_EXTRA) != 0;
-  if (e.prio || extra) e.last = (int *)get(cap * sizeof(int));
+  if (e.prio || extra) e.last = (int *)get(cap * sizeof(int), false);
   if (extra) {
-    e.x = (double *)get(cap * 4 * sizeof(double));
-    e.xv = (uint8_t *)get(cap);
+    e.x = (double *)get(cap * 4 * sizeof(double), false);
+    e.xv = (uint8_t *)get(cap, true);
   }
-  e.ctl = (ExpCtl *)get(sizeof(ExpCtl));
-  e.old = (char *)get(NP * e.stride);
-  e.has_old = (uint8_t *)get(NP);
-  e.off = (int *)get(NP * sizeof(int));
+  e.ctl = (ExpCtl *)get(sizeof(ExpCtl), false);
+  e.old = (char *)get(NP * e.stride, true);
+  e.has_old = (uint8_t *)get(NP, true);
+  e.off = (int *)get(NP * sizeof(int), false);
   if (!ok) {
-    exp_free(h);
+    h->exp_mem.release();
     return fail("exp_config: out of device memory (%zu bytes for %lld transitions of %d values)", total,
                 (long long)p->capacity, e.L);
   }
-  // cleared: rows zero, trees empty, no old states
-  HIPCHK(hipMemsetAsync(e.s, 0, cap * e.stride, h->stream));
-  HIPCHK(hipMemsetAsync(e.s2, 0, cap * e.stride, h->stream));
-  HIPCHK(hipMemsetAsync(e.a, 0, cap * 4 * sizeof(double), h->stream));
-  HIPCHK(hipMemsetAsync(e.r, 0, cap * sizeof(double), h->stream));
-  HIPCHK(hipMemsetAsync(e.done, 0, cap, h->stream));
-  HIPCHK(hipMemsetAsync(e.old, 0, NP * e.stride, h->stream));
-  HIPCHK(hipMemsetAsync(e.has_old, 0, NP, h->stream));
   if (e.last)
     hipLaunchKernelGGL(k_exp_fill_i, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, h->stream, e.last, cap, -1);
   if (e.x) {  // no slot has a fifth field: NaN, invalid
     hipLaunchKernelGGL(k_fill_d, dim3((unsigned)((cap * 4 + 255) / 256)), dim3(256), 0, h->stream, e.x, cap * 4,
                        __builtin_nan(""));
-    HIPCHK(hipMemsetAsync(e.xv, 0, cap, h->stream));
   }
   const size_t ni = e.prio ? 2 * (size_t)e.it_cap : 1;
   hipLaunchKernelGGL(k_exp_init, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, h->stream, e);
