@@ -99,6 +99,18 @@ class NetParams(C.Structure):
                 ("out_act", C.c_int32), ("pad", C.c_int32), ("units", C.c_int32 * 8)]
 
 
+TRAIN_MAX_BATCH = 256
+WARN_TRAIN_NONFINITE = 0x40  # aigar_warnings (arena 0): a training step met a non-finite TD error and was skipped
+NET_ONLINE, NET_TARGET, NET_ADAM_M, NET_ADAM_V = 0, 1, 2, 3  # aigar_net_get_weights' which
+
+
+class TrainParams(C.Structure):
+    """aigar_train_params (include/aigar.h): the Q-learning trainer (qLearning.py:116-193; Keras 2.2.4 Adam)."""
+    _fields_ = [("batch", C.c_int32), ("min_size", C.c_int32), ("target_steps", C.c_int32), ("pad", C.c_int32),
+                ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("epsilon", C.c_double),
+                ("discount", C.c_double)]
+
+
 CONV_MAX_LAYERS, CONV_MAX_SIDE, CONV_MAX_CHANNELS, CONV_MAX_KERNEL, CONV_MAX_FILTERS = 3, 128, 8, 8, 64
 
 

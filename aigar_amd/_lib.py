@@ -108,6 +108,14 @@ def load(build_if_missing=False):
         "aigar_net_set_conv_weights": [vp, i32, vp, vp, i32],
         "aigar_env_step_net": [vp, i32, vp, vp, i32, i32, i32, C.POINTER(_abi.RewardParams), vp, vp, i32, vp, vp, vp,
                                i32],
+        "aigar_train_config": [vp, C.POINTER(_abi.TrainParams)],
+        "aigar_train_step": [vp, i32, vp],
+        "aigar_train_info": [vp, C.POINTER(C.c_int64)],
+        "aigar_train_td": [vp, vp, vp],
+        "aigar_train_sync_target": [vp],
+        "aigar_train_reset": [vp],
+        "aigar_net_get_weights": [vp, i32, i32, vp, vp, i32],
+        "aigar_net_pad_check": [vp, i32, C.POINTER(C.c_int64)],
         "aigar_exp_extra_get": [vp, vp, i32, vp, vp],
         "aigar_exp_extra_set": [vp, vp, vp, i32],
         "aigar_warnings": [vp, i32, C.POINTER(C.c_uint32)],
@@ -200,6 +208,7 @@ class Stepper:
         self.noi = None  # (n_act, mu dtype name, Orn-Uhl) while an exploration noise is configured
         self.net = None  # (n_in, units, state dtype name) while an acting network is configured
         self.conv = None  # (side, channels, convs) while that network has a conv part (n_in: the flattened length)
+        self.trn = None  # the batch while a training is configured
 
     def _chk(self, r):
         if r < 0:
@@ -417,6 +426,7 @@ class Stepper:
         is set every env_step appends the NN players' transitions inside its graph.  extra:
         the ring also keeps the tuple's fifth field (exp_extra_get / exp_extra_set).
         exp_config(None) frees it."""
+        self.trn = None  # (the library drops the train configuration with the memory)
         if not capacity:
             self._chk(self.L.aigar_exp_config(self.h, None))
             self.exp = None
@@ -633,6 +643,7 @@ class Stepper:
         conv layers in front (aigar_net_config_cnn): the states are then images [side, side,
         channels] and n_in is n_flat.  The weights are zero until net_set_weights.
         net_config(None) turns it off."""
+        self.trn = None  # (the library drops the train configuration with the network)
         if spec is None:
             self._chk(self.L.aigar_net_config(self.h, None))
             self.net = self.conv = None
@@ -705,6 +716,96 @@ class Stepper:
             if on != on_b:
                 raise ValueError("net_set_weights: W and b both numpy arrays or both device tensors")
             self._chk(self.L.aigar_net_set_weights(self.h, l, wp, bp, on))
+
+    def net_get_weights(self, which="online", device=False):
+        """The read-back of net_set_weights (aigar_net_get_weights): a list of (W [in, out],
+        b [out]) float32 per dense layer, numpy arrays or (device=True) device tensors.  which:
+        "online", or with a train configuration "target", "m", "v" (Adam's state)."""
+        n_in, units, _ = self._need_net("net_get_weights")
+        code = {"online": _abi.NET_ONLINE, "target": _abi.NET_TARGET, "m": _abi.NET_ADAM_M, "v": _abi.NET_ADAM_V}
+        if which not in code:
+            raise ValueError("net_get_weights: which must be one of %s" % sorted(code))
+        out = []
+        for l, n in enumerate(units):
+            k = units[l - 1] if l else n_in
+            if device:
+                import torch
+                dev = "cuda:%d" % self.cfg.device
+                W = torch.empty((k, n), dtype=torch.float32, device=dev)
+                b = torch.empty((n,), dtype=torch.float32, device=dev)
+            else:
+                W, b = np.empty((k, n), np.float32), np.empty((n,), np.float32)
+            self._chk(self.L.aigar_net_get_weights(self.h, code[which], l, _ptr(W)[0], _ptr(b)[0], int(device)))
+            out.append((W, b))
+        return out
+
+    def net_pad_check(self, which="online"):
+        """A debug read (aigar_net_pad_check): how many padded entries of the packed copies are
+        not +0.0f (0 in every correct state; a host round trip)."""
+        code = {"online": _abi.NET_ONLINE, "target": _abi.NET_TARGET, "m": _abi.NET_ADAM_M, "v": _abi.NET_ADAM_V}
+        v = C.c_int64()
+        self._chk(self.L.aigar_net_pad_check(self.h, code[which], C.byref(v)))
+        return int(v.value)
+
+    # ---- the Q-learning trainer (include/aigar.h: aigar_train*)
+    def train_config(self, batch=32, min_size=0, target_steps=0, lr=1e-4, beta1=0.9, beta2=0.999, epsilon=1e-7,
+                     discount=0.85):
+        """The trainer of the handle's acting network on its replay memory (aigar_train_config):
+        Q-learning, Keras 2.2.4 Adam on the importance-weighted mse, a hard target copy every
+        target_steps applied steps.  Needs net_config (dense, linear head), exp_config and
+        decide_config.  train_config(None) turns it off."""
+        if batch is None:
+            self._chk(self.L.aigar_train_config(self.h, None))
+            self.trn = None
+            return
+        prm = _abi.TrainParams(int(batch), int(min_size), int(target_steps), 0, float(lr), float(beta1), float(beta2),
+                               float(epsilon), float(discount))
+        self._chk(self.L.aigar_train_config(self.h, C.byref(prm)))
+        self.trn = int(batch)
+
+    def _need_trn(self, what):
+        if getattr(self, "trn", None) is None:
+            raise RuntimeError("aigar: %s: no training is configured (train_config)" % what)
+        return self.trn
+
+    def train_step(self, n=1, u=None):
+        """n training steps, one graph replay each with no host work in between
+        (aigar_train_step).  u: None (the memory's own stream) or a device tensor [n, batch]
+        float64 of draws in [0, 1)."""
+        batch = self._need_trn("train_step")
+        up = None
+        if u is not None:
+            self._check_dev(u, (int(n), batch), ("float64",), "train_step")
+            up = C.c_void_p(u.data_ptr())
+        self._chk(self.L.aigar_train_step(self.h, int(n), up))
+
+    def train_info(self):
+        """{steps, skipped, since_target} of the trainer (the one synchronising read)."""
+        self._need_trn("train_info")
+        v = (C.c_int64 * 4)()
+        self._chk(self.L.aigar_train_info(self.h, v))
+        return {"steps": v[0], "skipped": v[1], "since_target": v[2]}
+
+    def train_td(self, td=None, idx=None):
+        """The last drawn step's TD errors and memory indices into the device tensors td [batch]
+        float64 and idx [batch] int64 (stream-ordered copies)."""
+        batch = self._need_trn("train_td")
+        tp = ip = None
+        if td is not None:
+            self._check_dev(td, (batch,), ("float64",), "train_td")
+            tp = C.c_void_p(td.data_ptr())
+        if idx is not None:
+            self._check_dev(idx, (batch,), ("int64",), "train_td")
+            ip = C.c_void_p(idx.data_ptr())
+        self._chk(self.L.aigar_train_td(self.h, tp, ip))
+
+    def train_sync_target(self):
+        self._need_trn("train_sync_target")
+        self._chk(self.L.aigar_train_sync_target(self.h))
+
+    def train_reset(self):
+        self._need_trn("train_reset")
+        self._chk(self.L.aigar_train_reset(self.h))
 
     def net_forward(self, x, out):
         """The network alone on device tensors (aigar_net_forward): x [rows, n_in] float64 /

@@ -106,7 +106,8 @@ enum : uint32_t {
   WARN_NEW_VIRUS_EATS = 1, WARN_DEAD_VIRUS = 2, WARN_TILE_OBS = 4,
   WARN_Q_NONFINITE = 8,  // k_decide met a NaN or an infinity in a live player's Q row (index 0 was taken)
   WARN_NOISE_NONFINITE = 16,  // k_noise met a non-finite mu value, a negative / non-finite std or a non-finite new Orn-Uhl state (each taken as 0)
-  WARN_NOISE_EXHAUSTED = 32   // k_noise: a pair's attempts were all rejected (the pair is (0.0, 0.0))
+  WARN_NOISE_EXHAUSTED = 32,  // k_noise: a pair's attempts were all rejected (the pair is (0.0, 0.0))
+  WARN_TRAIN_NONFINITE = 64   // k_td: a TD error was not finite or a stored action index outside the head (the step was skipped; arena 0's bit)
 };
 enum : uint32_t { DIRTY_VIRUS = 1, DIRTY_BLOB = 2 };
 

@@ -57,6 +57,7 @@ using namespace aigar;
 #include "noise.inc"
 #include "net.inc"
 #include "conv.inc"
+#include "train.inc"
 
 static thread_local std::string g_err;
 static int fail(const char *fmt, ...) {
@@ -153,6 +154,9 @@ struct TileKey {  // aigar_tile_begin, aigar_tile_end: the tick before the first
   const void *box[2];  // the message buffers (aigar_tile_set_buffers)
   void *out;           // (tile_begin: none)
   int dtype;           // -1: no observation
+};
+struct TrainKey {  // aigar_train_step: one training step (every buffer is the train configuration's own)
+  int has_u;  // the draws come from the handle's u row (the caller's draws are copied there)
 };
 struct EnvKey {  // aigar_env_step*: one learner decision
   const double *act;
@@ -306,7 +310,11 @@ struct aigar_handle {
   DevBlock exp_mem;
   int *d_exp_off = nullptr;  // aigar_exp_add's slot offsets, [exp_off_n]
   size_t exp_off_n = 0;
-  GraphSlot *const slots[7] = {&step, &run, &run_u, &env, &tb, &te, &tr};
+  // aigar_train_config: the Q-learning trainer (train.inc; batch 0: off) and its step's graph
+  Train trn;
+  DevBlock trn_mem;
+  KeyedSlot<TrainKey> train;
+  GraphSlot *const slots[8] = {&step, &run, &run_u, &env, &tb, &te, &tr, &train};
 };
 
 void GraphSlot::drop(aigar_handle *h) {
@@ -370,7 +378,7 @@ static void free_all(aigar_handle *h) {
   h->pix_bytes = 0;
   if (h->d_pix_hist) (void)hipFree(h->d_pix_hist);
   h->d_pix_hist = nullptr;
-  for (DevBlock *m : {&h->exp_mem, &h->dec_mem, &h->noi_mem, &h->net_mem}) m->release();
+  for (DevBlock *m : {&h->exp_mem, &h->dec_mem, &h->noi_mem, &h->net_mem, &h->trn_mem}) m->release();
   if (h->d_exp_off) (void)hipFree(h->d_exp_off);
   h->d_exp_off = nullptr;
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1450,6 +1458,13 @@ static int begin_reconfig(aigar_handle *h) {
   h->env.drop(h);
   return 0;
 }
+// The train configuration goes with the network or the memory it was made for
+// (after begin_reconfig: no training step is pending).
+static void train_free(aigar_handle *h) {
+  h->train.drop(h);
+  h->trn_mem.release();
+  h->trn = Train{};
+}
 static int need_dec(aigar_handle *h, const char *who) {
   return need(h, h && h->dec.n_out, who, "no action selection is configured (aigar_decide_config)");
 }
@@ -1654,6 +1669,7 @@ extern "C" int aigar_net_config(aigar_handle *h, const aigar_net_params *p) {
   if (!h) return fail("null handle");
   if (p && h->d.tiled) return fail("net_config: a tiled handle has no acting network");
   if (begin_reconfig(h)) return -1;
+  train_free(h);
   net_free(h);
   if (!p) return 0;
   Net c{};
@@ -2054,6 +2070,7 @@ extern "C" int aigar_exp_config(aigar_handle *h, const aigar_exp_params *p) {
       return fail("exp_config: need alpha >= 0 and beta > 0 (got %g, %g)", p->alpha, p->beta);
   }
   if (begin_reconfig(h)) return -1;  // (no reader of the memory is pending either)
+  train_free(h);
   h->exp_mem.release();
   h->exp = Exp{};
   if (!on) return 0;
@@ -2264,6 +2281,268 @@ extern "C" int aigar_exp_extra_set(aigar_handle *h, const int64_t *idx, const do
   HIPCHK(hipSetDevice(h->cfg.device));
   hipLaunchKernelGGL(k_exp_extra_set, dim3(1), dim3(kExpPlanThreads), 0, h->stream, h->exp, idx, rows, n);
   HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------------ Q-learning trainer
+static int need_trn(aigar_handle *h, const char *who) {
+  return need(h, h && h->trn.batch, who, "no training is configured (aigar_train_config)");
+}
+
+extern "C" int aigar_train_config(aigar_handle *h, const aigar_train_params *p) {
+  if (p) {  // (before the handle: a bad set has its own message)
+    if (p->batch < 1 || p->batch > kTrainMaxBatch)
+      return fail("train_config: batch = %d is outside 1..%d", p->batch, kTrainMaxBatch);
+    if (p->min_size < 0) return fail("train_config: min_size = %d is negative", p->min_size);
+    if (p->target_steps < 0) return fail("train_config: target_steps = %d is negative", p->target_steps);
+    if (!(p->lr > 0) || !(p->lr < __builtin_inf())) return fail("train_config: lr = %g must be positive and finite", p->lr);
+    if (!(p->beta1 >= 0 && p->beta1 < 1)) return fail("train_config: beta1 = %g is outside [0, 1)", p->beta1);
+    if (!(p->beta2 >= 0 && p->beta2 < 1)) return fail("train_config: beta2 = %g is outside [0, 1)", p->beta2);
+    if (!(p->epsilon > 0) || !(p->epsilon < __builtin_inf()))
+      return fail("train_config: epsilon = %g must be positive and finite", p->epsilon);
+    if (!(p->discount >= 0 && p->discount <= 1)) return fail("train_config: discount = %g is outside [0, 1]", p->discount);
+  }
+  if (!h) return fail("null handle");
+  if (p) {
+    if (h->d.tiled) return fail("train_config: a tiled handle has no training");
+    if (need_net(h, "train_config")) return -1;
+    if (h->conv.n_conv) return fail("train_config: a network with a conv part is not trained on the device");
+    if (h->net.out_act != AIGAR_ACT_LINEAR)
+      return fail("train_config: the network's head is %s, Q-learning needs a linear head", net_act_name(h->net.out_act));
+    if (need_exp(h, "train_config")) return -1;
+    if (need_dec(h, "train_config")) return -1;
+    if (h->dec.n_out != h->net.out[h->net.n_layers - 1])
+      return fail("train_config: the network has %d outputs, the action selection %d", h->net.out[h->net.n_layers - 1],
+                  h->dec.n_out);
+    if (h->net.in[0] != h->exp.L)
+      return fail("train_config: the network has %d inputs, the memory's states %d values", h->net.in[0], h->exp.L);
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  train_free(h);
+  if (!p) return 0;
+  const Net &c = h->net;
+  const Exp &e = h->exp;
+  Train t;
+  t.batch = p->batch;
+  t.bpad = (p->batch + kNetRows - 1) / kNetRows * kNetRows;
+  t.min_size = p->min_size;
+  t.target_steps = p->target_steps;
+  t.lr = p->lr;
+  t.beta1 = p->beta1;
+  t.beta2 = p->beta2;
+  t.epsilon = p->epsilon;
+  t.discount = p->discount;
+  bool ok = true;
+  auto get = [&](size_t bytes) -> void * {
+    if (!ok) return nullptr;
+    void *q = h->trn_mem.alloc(bytes, true, h->stream);
+    ok = q != nullptr;
+    return q;
+  };
+  const size_t B = (size_t)t.batch, n_out = (size_t)c.out[c.n_layers - 1];
+  for (int l = 0; l < c.n_layers; l++) {
+    const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
+    t.tw[l] = (float *)get(nw);
+    t.tb[l] = (float *)get(op * sizeof(float));
+    t.mw[l] = (float *)get(nw);
+    t.mb[l] = (float *)get(op * sizeof(float));
+    t.vw[l] = (float *)get(nw);
+    t.vb[l] = (float *)get(op * sizeof(float));
+    t.tile0[l + 1] = t.tile0[l] + (c.in[l] + 15) / 16 * (int)(op / 16);
+    if (ok) {
+      (void)hipMemcpyAsync(t.tw[l], c.w[l], nw, hipMemcpyDeviceToDevice, h->stream);
+      (void)hipMemcpyAsync(t.tb[l], c.b[l], op * sizeof(float), hipMemcpyDeviceToDevice, h->stream);
+    }
+  }
+  const size_t row = (size_t)e.L * e.esz;
+  t.s = (char *)get(B * row);
+  t.s2 = (char *)get(B * row);
+  t.a = (double *)get(B * 4 * sizeof(double));
+  t.r = (double *)get(B * sizeof(double));
+  t.w = (double *)get(B * sizeof(double));
+  t.u = (double *)get(B * sizeof(double));
+  t.done = (uint8_t *)get(B);
+  t.idx = (int64_t *)get(B * sizeof(int64_t));
+  t.q = (double *)get(B * n_out * sizeof(double));
+  t.q2 = (double *)get(B * n_out * sizeof(double));
+  t.td = (double *)get(B * sizeof(double));
+  t.prio = (double *)get(B * sizeof(double));
+  t.hsave = (float *)get((size_t)std::max(c.n_layers - 1, 1) * t.bpad * kNetMaxUnits * sizeof(float));
+  t.delta = (float *)get((size_t)c.n_layers * t.bpad * kNetMaxUnits * sizeof(float));
+  t.ctl = (TrainCtl *)get(sizeof(TrainCtl));
+  if (!ok) {
+    h->trn_mem.release();
+    return fail("train_config: out of device memory");
+  }
+  HIPCHK(hipGetLastError());
+  h->trn = t;
+  return 0;
+}
+
+// One training step's launches on stream s (train.inc).
+static void launch_train_step(aigar_handle *h, hipStream_t s, int has_u) {
+  const Train &t = h->trn;
+  const Exp &e = h->exp;
+  Net on = h->net, tg = h->net;
+  on.x_dtype = tg.x_dtype = e.dtype;
+  for (int l = 0; l < tg.n_layers; l++) {
+    tg.w[l] = t.tw[l];
+    tg.b[l] = t.tb[l];
+  }
+  const int B = t.batch, n_out = on.out[on.n_layers - 1];
+  const dim3 rows16((unsigned)(t.bpad / kNetRows)), net_block(64 * kNetWaves);
+  hipLaunchKernelGGL(k_exp_draw, dim3((B + 255) / 256), dim3(256), 0, s, e, B, has_u ? t.u : (const double *)nullptr, t.w,
+                     t.idx);
+  if (e.dtype == 0) {
+    hipLaunchKernelGGL(k_exp_fetch<uint64_t>, dim3(B), dim3(256), 0, s, e, t.idx, t.s, t.a, t.r, t.s2, t.done, 0);
+    hipLaunchKernelGGL(k_net_save<double>, rows16, net_block, 0, s, on, (const double *)t.s, B, t.q, t.hsave);
+  } else {
+    hipLaunchKernelGGL(k_exp_fetch<uint32_t>, dim3(B), dim3(256), 0, s, e, t.idx, t.s, t.a, t.r, t.s2, t.done, 0);
+    hipLaunchKernelGGL(k_net_save<float>, rows16, net_block, 0, s, on, (const float *)t.s, B, t.q, t.hsave);
+  }
+  launch_net(s, tg, t.s2, B, t.q2, nullptr, nullptr);
+  hipLaunchKernelGGL(k_td, dim3(1), dim3(kTrainMaxBatch), 0, s, t, e, h->d, on.n_layers, n_out);
+  if (on.n_layers > 1) hipLaunchKernelGGL(k_net_bwd, rows16, net_block, 0, s, on, t);
+  if (e.dtype == 0) hipLaunchKernelGGL(k_net_grad_adam<double>, dim3(t.tile0[on.n_layers]), dim3(64), 0, s, on, t);
+  else hipLaunchKernelGGL(k_net_grad_adam<float>, dim3(t.tile0[on.n_layers]), dim3(64), 0, s, on, t);
+  if (e.prio) hipLaunchKernelGGL(k_exp_update, dim3(1), dim3(kExpPlanThreads), 0, s, e, t.idx, t.prio, B);
+  hipLaunchKernelGGL(k_train_tail, dim3(64), dim3(256), 0, s, on, t);
+}
+
+extern "C" int aigar_train_step(aigar_handle *h, int n_steps, const double *u) {
+  if (need_trn(h, "train_step")) return -1;
+  if (n_steps < 1) return fail("train_step: n_steps = %d is below 1", n_steps);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  TrainKey k;
+  key_clear(k);
+  k.has_u = u ? 1 : 0;
+  const bool graph = h->use_graph;
+  if (graph && !h->train.ensure(h, k, [&](hipStream_t cs) { launch_train_step(h, cs, k.has_u); }))
+    return fail("train_step: graph capture failed");
+  Mark m(h, "train_step");
+  for (int i = 0; i < n_steps; i++) {
+    if (u)
+      HIPCHK(hipMemcpyAsync(h->trn.u, u + (size_t)i * h->trn.batch, (size_t)h->trn.batch * sizeof(double),
+                            hipMemcpyDeviceToDevice, h->stream));
+    if (graph) HIPCHK(h->train.launch(h));
+    else launch_train_step(h, h->stream, k.has_u);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int aigar_train_info(aigar_handle *h, int64_t info[4]) {
+  if (need_trn(h, "train_info")) return -1;
+  if (!info) return fail("train_info: null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  TrainCtl c;
+  HIPCHK(hipMemcpyAsync(&c, h->trn.ctl, sizeof c, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  info[0] = c.t;
+  info[1] = c.skipped;
+  info[2] = c.since;
+  info[3] = 0;
+  return 0;
+}
+
+extern "C" int aigar_train_td(aigar_handle *h, double *td, int64_t *idx) {
+  if (need_trn(h, "train_td")) return -1;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const size_t B = (size_t)h->trn.batch;
+  if (td) HIPCHK(hipMemcpyAsync(td, h->trn.td, B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  if (idx) HIPCHK(hipMemcpyAsync(idx, h->trn.idx, B * sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream));
+  return 0;
+}
+
+__global__ void k_train_clear(TrainCtl *ctl, int target) {  // target: the copy was made; else Adam starts over
+  if (target) ctl->since = 0;
+  else ctl->t = 0;
+}
+
+extern "C" int aigar_train_sync_target(aigar_handle *h) {
+  if (need_trn(h, "train_sync_target")) return -1;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const Net &c = h->net;
+  for (int l = 0; l < c.n_layers; l++) {
+    const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
+    HIPCHK(hipMemcpyAsync(h->trn.tw[l], c.w[l], nw, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->trn.tb[l], c.b[l], op * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  }
+  hipLaunchKernelGGL(k_train_clear, dim3(1), dim3(1), 0, h->stream, h->trn.ctl, 1);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int aigar_train_reset(aigar_handle *h) {
+  if (need_trn(h, "train_reset")) return -1;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const Net &c = h->net;
+  const Train &t = h->trn;
+  for (int l = 0; l < c.n_layers; l++) {
+    const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
+    HIPCHK(hipMemsetAsync(t.mw[l], 0, nw, h->stream));
+    HIPCHK(hipMemsetAsync(t.vw[l], 0, nw, h->stream));
+    HIPCHK(hipMemsetAsync(t.mb[l], 0, op * sizeof(float), h->stream));
+    HIPCHK(hipMemsetAsync(t.vb[l], 0, op * sizeof(float), h->stream));
+  }
+  hipLaunchKernelGGL(k_train_clear, dim3(1), dim3(1), 0, h->stream, t.ctl, 0);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// which: 0 online, 1 target, 2 Adam's m, 3 Adam's v (the last three need a train configuration)
+static int net_which(aigar_handle *h, const char *who, int which, int layer, const float **wp, const float **bp) {
+  if (need_net(h, who)) return -1;
+  if (which < 0 || which > 3) return fail("%s: which = %d is outside 0..3", who, which);
+  if (layer < 0 || layer >= h->net.n_layers) return fail("%s: layer %d is outside 0..%d", who, layer, h->net.n_layers - 1);
+  if (which && need_trn(h, who)) return -1;
+  const Train &t = h->trn;
+  *wp = which == 0 ? h->net.w[layer] : which == 1 ? t.tw[layer] : which == 2 ? t.mw[layer] : t.vw[layer];
+  *bp = which == 0 ? h->net.b[layer] : which == 1 ? t.tb[layer] : which == 2 ? t.mb[layer] : t.vb[layer];
+  return 0;
+}
+
+extern "C" int aigar_net_get_weights(aigar_handle *h, int which, int layer, float *W, float *b, int on_device) {
+  const float *wp, *bp;
+  if (net_which(h, "net_get_weights", which, layer, &wp, &bp)) return -1;
+  if (h->conv.n_conv) return fail("net_get_weights: a network with a conv part has no read-back");
+  if (!W || !b) return fail("net_get_weights: null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const int in = h->net.in[layer], out = h->net.out[layer];
+  const size_t nw = (size_t)in * out;
+  float *dW = on_device ? W : h->net_stage, *db = on_device ? b : h->net_stage + nw;
+  hipLaunchKernelGGL(k_net_unpack, dim3((unsigned)std::min<size_t>((nw + 255) / 256, 4096)), dim3(256), 0, h->stream, wp, bp,
+                     dW, db, in, out, net_out_pad(out));
+  HIPCHK(hipGetLastError());
+  if (!on_device) {
+    HIPCHK(hipMemcpyAsync(W, dW, nw * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(b, db, (size_t)out * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  return 0;
+}
+
+extern "C" int aigar_net_pad_check(aigar_handle *h, int which, int64_t *count) {
+  const float *wp, *bp;
+  if (net_which(h, "net_pad_check", which, 0, &wp, &bp)) return -1;
+  if (!count) return fail("net_pad_check: null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  unsigned long long *dc = nullptr, n = 0;
+  HIPCHK(hipMalloc((void **)&dc, sizeof n));
+  hipError_t er = hipMemsetAsync(dc, 0, sizeof n, h->stream);
+  for (int l = 0; l < h->net.n_layers && er == hipSuccess; l++) {
+    (void)net_which(h, "net_pad_check", which, l, &wp, &bp);
+    const int in = h->net.in[l], out = h->net.out[l], ip = net_in_pad(in), op = net_out_pad(out);
+    hipLaunchKernelGGL(k_net_pad_count, dim3((unsigned)std::min<size_t>(((size_t)ip * op + 255) / 256, 4096)), dim3(256), 0,
+                       h->stream, wp, bp, in, out, ip, op, dc);
+    er = hipGetLastError();
+  }
+  if (er == hipSuccess) er = hipMemcpyAsync(&n, dc, sizeof n, hipMemcpyDeviceToHost, h->stream);
+  if (er == hipSuccess) er = hipStreamSynchronize(h->stream);
+  (void)hipFree(dc);
+  if (er != hipSuccess) return fail("net_pad_check: %s", hipGetErrorString(er));
+  *count = (int64_t)n;
   return 0;
 }
 

@@ -90,10 +90,12 @@ __device__ __forceinline__ void net_chunk(net_f4 (&acc)[NT], const float *a, con
 // Layer l for a block whose waves carry up to NT tiles each.  The next chunk's weights (and,
 // in the first layer, the next chunk's states) are in flight while the matrix core works on
 // this one; the last iteration re-loads its own chunk, so nothing in the loop is conditional.
-template <class T, int NT>
+// SAVE (the trainer's online pass, train.inc): every hidden layer's activations also go to
+// hsave [n_layers - 1][16 gridDim.x][kNetMaxUnits], padded units as -0.0f.
+template <class T, int NT, bool SAVE>
 __device__ __forceinline__ void net_layer(const Net &c, int l, const T *x, size_t row0, const bool (&lrow)[4],
                                           float (*xs)[kNetRows][kNetXStride], float (*hid)[kNetRows][kNetHStride],
-                                          const int *rowflag, int &src, double *y) {
+                                          const int *rowflag, int &src, double *y, float *hsave) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lk = lane;
   const int r16 = lane & 15, g = lane >> 4;
   const int n = c.out[l], op = net_out_pad(n), nt = op >> 4, K = c.in[l];
@@ -171,14 +173,20 @@ __device__ __forceinline__ void net_layer(const Net &c, int l, const T *x, size_
   }
   src = dst;
   __syncthreads();
+  if constexpr (SAVE) {
+    if (!last) {  // the finished tile, from LDS: row tid / 16, units tid % 16, + 16, ...
+      float *hs = hsave + (((size_t)l * gridDim.x) * kNetRows + row0 + (tid >> 4)) * kNetMaxUnits;
+      for (int j = tid & 15; j < op; j += 16) hs[j] = hid[dst][tid >> 4][j];
+    }
+  }
 }
 
 // x [rows][in_0] of T; y [rows][n_out] float64.  alive / role (null: the call alone): only
 // live NN players' rows are evaluated and stored.  A row whose first value is a NaN is
 // not evaluated: its output row is NaN.
-template <class T>
-__global__ void __launch_bounds__(64 * kNetWaves) k_net(Net c, const T *x, int rows, double *y, const int *alive,
-                                                        const uint8_t *role) {
+template <class T, bool SAVE>
+__device__ __forceinline__ void net_body(const Net &c, const T *x, int rows, double *y, const int *alive,
+                                         const uint8_t *role, float *hsave) {
   __shared__ float xs[2][kNetRows][kNetXStride];
   __shared__ float hid[2][kNetRows][kNetHStride];
   __shared__ int rowflag[kNetRows];  // 0: not stored, 1: evaluated, 2: a NaN row
@@ -199,12 +207,22 @@ __global__ void __launch_bounds__(64 * kNetWaves) k_net(Net c, const T *x, int r
   int src = 0;  // the hidden tile that the next layer reads
   for (int l = 0; l < c.n_layers; l++) {
     switch ((net_out_pad(c.out[l]) / 16 + kNetWaves - 1) / kNetWaves) {  // tiles of a wave at the most
-      case 1: net_layer<T, 1>(c, l, x, row0, lrow, xs, hid, rowflag, src, y); break;
-      case 2: net_layer<T, 2>(c, l, x, row0, lrow, xs, hid, rowflag, src, y); break;
-      case 3: net_layer<T, 3>(c, l, x, row0, lrow, xs, hid, rowflag, src, y); break;
-      default: net_layer<T, 4>(c, l, x, row0, lrow, xs, hid, rowflag, src, y); break;
+      case 1: net_layer<T, 1, SAVE>(c, l, x, row0, lrow, xs, hid, rowflag, src, y, hsave); break;
+      case 2: net_layer<T, 2, SAVE>(c, l, x, row0, lrow, xs, hid, rowflag, src, y, hsave); break;
+      case 3: net_layer<T, 3, SAVE>(c, l, x, row0, lrow, xs, hid, rowflag, src, y, hsave); break;
+      default: net_layer<T, 4, SAVE>(c, l, x, row0, lrow, xs, hid, rowflag, src, y, hsave); break;
     }
   }
+}
+template <class T>
+__global__ void __launch_bounds__(64 * kNetWaves) k_net(Net c, const T *x, int rows, double *y, const int *alive,
+                                                        const uint8_t *role) {
+  net_body<T, false>(c, x, rows, y, alive, role, nullptr);
+}
+// ... and the trainer's online pass: all rows, the hidden activations kept
+template <class T>
+__global__ void __launch_bounds__(64 * kNetWaves) k_net_save(Net c, const T *x, int rows, double *y, float *hsave) {
+  net_body<T, true>(c, x, rows, y, nullptr, nullptr, hsave);
 }
 
 static void launch_net(hipStream_t s, const Net &c, const void *x, int rows, double *y, const int *alive,

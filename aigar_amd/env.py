@@ -94,6 +94,16 @@ activations; what the device cannot evaluate is refused there); a (n_in, units, 
 overrides it.  The weights are zero until the first `set_weights`.  Epsilon, temperature and the
 noise level are read from `explore` / `noise_std` at every decision, so `collect(n)` uses what
 they hold for all n: a decay schedule is written between calls.
+The trainer (`train=True` or a dict, with `discrete=`, `network=` and `memory=`):
+the reference's Q-learning trainer (qLearning.py:116-193, Keras 2.2.4 Adam on the importance-weighted
+mse, a hard target copy every TARGET_NETWORK_STEPS) on the device, in place on the acting network's
+weights: `train(n)` makes n steps on the replay memory, one graph replay each, and the next decision
+acts with the trained weights; `get_weights()` reads them back, `train_info()` the counters.
+`train=True` reads ALPHA, DISCOUNT, TARGET_NETWORK_STEPS, NUM_EXPS_BEFORE_TRAIN and the memory's batch;
+a dict (batch, min_size, target_steps, lr, beta1, beta2, epsilon, discount) overrides them.  Every
+other optimiser setting of the reference is refused by name (aigar_amd.net.train_params).  It is never
+switched on by `parameters` alone.
+
 With a pixel state (`pixels=` or CNN_REPR and CNN_P_REPR) the network is the reference's CNN
 (DESIGN.md §4k): `network=True` builds a CnnSpec from `parameters` (aigar_amd.net.cnn_spec: CNN_L1/2/3,
 CNN_USE_L1/2/3 and the dense settings above), a CnnSpec overrides it; the conv layers run on the
@@ -115,7 +125,8 @@ Batch = collections.namedtuple("Batch", "s a r s2 done w idx")
 class AgarVecEnv:
     def __init__(self, n_players, parameters=None, n_arenas=1, virus=None, field_size=0, max_pellets=-1.0,
                  max_viruses=-1.0, device=0, torch_stream=True, roles=None, reset_limit=None, desync=True, seed=0,
-                 score=False, pixels=None, pixel_dtype=None, memory=None, discrete=None, continuous=None, network=None):
+                 score=False, pixels=None, pixel_dtype=None, memory=None, discrete=None, continuous=None, network=None,
+                 train=None):
         import torch
         if continuous and discrete:
             raise ValueError("continuous= and discrete= exclude each other (one learner decides per env)")
@@ -298,9 +309,81 @@ class AgarVecEnv:
             self._net_out = torch.empty((self.NP, n_out), dtype=torch.float64, device=self.dev)
             self.net_output = None
 
+        self.training = None
+        if train:  # (explicit only, as memory=)
+            if self.discrete is None or self.network is None or self.memory is None:
+                raise ValueError("train= needs discrete=, network= and memory= (Q-learning on the device's replay memory)")
+            if self.pixels is not None or hasattr(self.network, "convs"):
+                raise ValueError("train=: CNN / pixel states are not trained on the device")
+            tp = _net.train_params(parameters)
+            if self.memory is not None:
+                tp["batch"] = int(self.memory["batch"])
+            if isinstance(train, dict):
+                unknown = set(train) - set(tp)
+                if unknown:
+                    raise ValueError("train: unknown keys %s" % sorted(unknown))
+                tp.update(train)
+            self.training = tp
+            self.stepper.train_config(**tp)
+
     def _need_network(self):
         if self.network is None:
             raise RuntimeError("AgarVecEnv was created without network=")
+
+    # ---- the Q-learning trainer on the device
+    def _need_training(self):
+        if self.training is None:
+            raise RuntimeError("AgarVecEnv was created without train=")
+
+    def train(self, n=1, u=None):
+        """n training steps of the acting network on the replay memory, one graph replay each with
+        no host work in between: draw, forward, TD errors, priorities, backward, Adam in place,
+        target copy when due.  u: None (the memory's own stream) or [n, batch] draws in [0, 1).
+        A step is skipped on the device while the memory is too small (train_info)."""
+        self._need_training()
+        torch = self.torch
+        n = int(n)
+        if n < 1:
+            raise ValueError("train: n must be at least 1")
+        if u is not None:
+            u = torch.as_tensor(u, dtype=torch.float64, device=self.dev).reshape(n, self.training["batch"]).contiguous()
+        if self._mem_sync:
+            torch.cuda.synchronize(self.dev)
+        self.stepper.train_step(n, u)
+        if self._mem_sync:
+            self.stepper.sync()  # (u is freed when this returns)
+
+    def train_info(self):
+        """{steps, skipped, since_target} (aigar_train_info: a host round trip)."""
+        self._need_training()
+        return self.stepper.train_info()
+
+    def train_td(self):
+        """(td [batch] float64, idx [batch] int64) of the last drawn training step, device tensors."""
+        self._need_training()
+        torch = self.torch
+        b = self.training["batch"]
+        td = torch.empty(b, dtype=torch.float64, device=self.dev)
+        idx = torch.empty(b, dtype=torch.int64, device=self.dev)
+        if self._mem_sync:
+            torch.cuda.synchronize(self.dev)
+        self.stepper.train_td(td, idx)
+        if self._mem_sync:
+            self.stepper.sync()
+        return td, idx
+
+    def get_weights(self, target=False):
+        """The acting network's dense weights as [(W [in, out], b [out])] float32 numpy arrays
+        (Keras' layout; aigar_amd.net.weights_to_torch loads them into a module); target=True:
+        the trainer's target network."""
+        self._need_network()
+        if hasattr(self.network, "convs"):
+            raise RuntimeError("get_weights: a network with a conv part has no read-back")
+        if target:
+            self._need_training()
+        if self._mem_sync:
+            self.torch.cuda.synchronize(self.dev)
+        return self.stepper.net_get_weights("target" if target else "online")
 
     def set_weights(self, weights):
         """The trainer's weight push: a list of (W [in, out], b [out]) float32 per layer as device

@@ -242,3 +242,43 @@ def weights_from_torch(source):
             raise ValueError("weights_from_torch: expected W [in, out] and b [out], got %s and %s" % (w.shape, b.shape))
         out.append((np.ascontiguousarray(w, np.float32), np.ascontiguousarray(b, np.float32)))
     return out
+
+
+def weights_to_torch(weights, module):
+    """The inverse of weights_from_torch: [(W [in, out], b [out]), ...] (numpy arrays or
+    tensors, Keras' layout) into the nn.Linear layers of a torch module, in order (weight
+    [out, in] = W transposed).  Returns the module."""
+    import torch
+    layers = [m for m in module.modules() if isinstance(m, torch.nn.Linear)]
+    if len(layers) != len(weights):
+        raise ValueError("weights_to_torch: %d layers given, the module has %d nn.Linear" % (len(weights), len(layers)))
+    with torch.no_grad():
+        for m, (W, b) in zip(layers, weights):
+            W, b = torch.as_tensor(_np(W)), torch.as_tensor(_np(b))
+            if tuple(W.shape) != (m.in_features, m.out_features):
+                raise ValueError("weights_to_torch: W is %s, the layer takes (%d, %d)"
+                                 % (tuple(W.shape), m.in_features, m.out_features))
+            m.weight.copy_(W.t().to(m.weight))
+            if m.bias is not None:
+                m.bias.copy_(b.to(m.bias))
+    return module
+
+
+def train_params(parameters=None):
+    """The device trainer's settings from the reference's parameters: Q-learning
+    with Keras' Adam, what qLearning.py and network.py do by default.  Everything else the
+    reference can train with is refused here, by the name of the setting."""
+    g = lambda n, d: _get(parameters, n, d)
+    if g("OPTIMIZER", "Adam") != "Adam":
+        raise ValueError("train: OPTIMIZER = %r: the device trainer is Adam" % (g("OPTIMIZER", "Adam"),))
+    for name in ("AMSGRAD", "GRADIENT_CLIP", "GRADIENT_CLIP_NORM", "Q_WEIGHT_DECAY", "DROPOUT", "ENABLE_QV",
+                 "USE_ACTION_AS_INPUT", "END_DISCOUNT", "CNN_REPR", "BATCHNORM"):
+        if g(name, 0):
+            raise ValueError("train: %s = %r is not supported by the device trainer" % (name, g(name, 0)))
+    if g("NEURON_TYPE", "MLP") != "MLP":
+        raise ValueError("train: NEURON_TYPE = %r: the device trainer takes no LSTM" % (g("NEURON_TYPE", "MLP"),))
+    if g("TD", 0) != 0:
+        raise ValueError("train: TD = %r: only one-step targets (TD = 0)" % (g("TD", 0),))
+    return {"batch": int(g("MEMORY_BATCH_LEN", 32)), "min_size": int(g("NUM_EXPS_BEFORE_TRAIN", 32)),
+            "target_steps": int(g("TARGET_NETWORK_STEPS", 1500)), "lr": float(g("ALPHA", 0.001)), "beta1": 0.9,
+            "beta2": 0.999, "epsilon": 1e-7, "discount": float(g("DISCOUNT", 0.9))}

@@ -689,9 +689,76 @@ int aigar_net_set_conv_weights(aigar_handle *h, int layer, const float *W, const
  * [0, size) are skipped. */
 int aigar_exp_extra_get(aigar_handle *h, const int64_t *idx, int batch, double *out, uint8_t *valid);
 int aigar_exp_extra_set(aigar_handle *h, const int64_t *idx, const double *rows, int n);
+/* The Q-learning trainer on the device (qLearning.py:116-193 QLearn.train, network.py:378-392
+ * trainOnBatch; tests/train_model.py is the specification in plain Python): the
+ * reference's default discrete learner -- an MLP with a linear head, Keras 2.2.4 Adam
+ * (amsgrad off) on loss='mse' with the memory's importance weights as sample weights, a
+ * hard target-network copy every target_steps applied steps.  One step, for a batch of B
+ * drawn transitions (s, a, rew, s2, done, w), a = [index, 0, 0, 0]:
+ *   q = forward(s, online) with every layer's float32 activations kept; q2 = forward(s2, target);
+ *   t = rew if done, else rew + discount * max_j q2[j] (float64: one multiply, one add);
+ *   td = t - q[a]; with a prioritized memory |td| + 1e-4 becomes the priority of the drawn
+ *   slot (aigar_exp_update_priorities: the last of a repeated index wins);
+ *   delta_L[r][a_r] = float32(((2 w_r) (-td_r)) / (n_out B)), +0.0f elsewhere;
+ *   for l = L ... 1 in float32: dW_l[k][j] = ONE fmaf chain over ascending r of
+ *   h_{l-1}[r][k] delta_l[r][j] from +0.0f; db_l[j] = the plain sum over ascending r; and,
+ *   with the weights as they are before the update, e[r][k] = ONE fmaf chain over ascending
+ *   j of delta_l[r][j] W_l[k][j], delta_{l-1} = e where y_{l-1} > 0 (relu; else +0.0f) or e (linear);
+ *   Adam per parameter, m and v float32, float64 arithmetic on the widened values with every
+ *   operation rounding on its own: lr_t = lr * sqrt(1 - pow(beta2, t)) / (1 - pow(beta1, t))
+ *   (glibc's pow; t counts applied steps from 1), m = f32(beta1 m + (1 - beta1) g),
+ *   v = f32(beta2 v + (1 - beta2) (g g)), p = f32(p - lr_t m / (sqrt(v) + epsilon));
+ *   after a step with t % target_steps == 0 (target_steps > 0) target <- online.
+ * A step is skipped on the device -- no weight, counter t or priority changes -- while the
+ * memory holds fewer than max(batch, min_size) transitions, and also when a TD error is not
+ * finite or a stored action index lies outside the head; the latter sets the sticky bit
+ * AIGAR_WARN_TRAIN_NONFINITE of arena 0.  Skipped steps are counted.
+ *
+ * aigar_train_config: the parameters are checked before the handle, each refusal with its own
+ * message (batch 1..256, min_size >= 0, target_steps >= 0, lr > 0, betas in [0, 1),
+ * epsilon > 0, discount in [0, 1]).  It needs a dense acting network with a linear head and no
+ * conv part (aigar_net_config), a replay memory whose state length is the network's n_in, an
+ * action selection (aigar_decide_config) of the network's n_out, and no tiled handle.  It
+ * allocates the target network as a copy of the online one as it is NOW, zeroed Adam state,
+ * the staging rows and the activation buffers.  NULL turns training off and frees them;
+ * aigar_net_config* and aigar_exp_config drop the train configuration.
+ * Training is in place on the acting network's packed weights: the next decision acts with
+ * the trained weights.  aigar_net_set_weights overwrites the online weights only.
+ *
+ * aigar_train_step: n_steps >= 1 steps, one captured graph replayed n_steps times with no
+ * host work in between.  u NULL: the memory's own Philox stream, as aigar_exp_sample; else
+ * the DEVICE buffer u [n_steps][batch] of draws in [0, 1) (step i's row is copied on the
+ * stream in front of its replay).  Stream-ordered.
+ * aigar_train_info: {steps applied, steps skipped, steps since the last target copy, 0};
+ * the one synchronising read.  aigar_train_td: stream-ordered copies of the last drawn
+ * step's TD errors [batch] and memory indices [batch] into DEVICE buffers (each may be NULL).
+ * aigar_train_sync_target: target <- online now.  aigar_train_reset: m, v and t to zero.
+ * aigar_net_get_weights: layer's W[in][out] and b[out] in Keras' layout, into host or
+ * (on_device) DEVICE buffers; which 0 the online network (needs no train configuration),
+ * 1 the target network, 2 Adam's m, 3 Adam's v.  aigar_net_pad_check: a debug read, the
+ * number of padded entries of which's packed copies whose bits are not +0.0f's (a host
+ * round trip; 0 in every correct state). */
+typedef struct aigar_train_params {
+  int32_t batch;         /* transitions a step, 1..256                          */
+  int32_t min_size;      /* NUM_EXPS_BEFORE_TRAIN: no step below this memory size */
+  int32_t target_steps;  /* TARGET_NETWORK_STEPS; 0: never copied                */
+  int32_t pad;
+  double lr, beta1, beta2, epsilon;  /* Keras' Adam: 1e-4 (ALPHA), 0.9, 0.999, 1e-7 */
+  double discount;                   /* DISCOUNT                                  */
+} aigar_train_params;
+int aigar_train_config(aigar_handle *h, const aigar_train_params *p);
+int aigar_train_step(aigar_handle *h, int n_steps, const double *u);
+int aigar_train_info(aigar_handle *h, int64_t info[4]);
+int aigar_train_td(aigar_handle *h, double *td, int64_t *idx);
+int aigar_train_sync_target(aigar_handle *h);
+int aigar_train_reset(aigar_handle *h);
+int aigar_net_get_weights(aigar_handle *h, int which, int layer, float *W, float *b, int on_device);
+int aigar_net_pad_check(aigar_handle *h, int which, int64_t *count);
 /* The sticky quirk bits of one arena since its last reset (a host round trip): 1 a virus
  * made this tick ate, 2 a dead virus was met, 4 a tile observed past its held pellets,
- * 8 AIGAR_WARN_Q_NONFINITE, 16 AIGAR_WARN_NOISE_NONFINITE, 32 AIGAR_WARN_NOISE_EXHAUSTED. */
+ * 8 AIGAR_WARN_Q_NONFINITE, 16 AIGAR_WARN_NOISE_NONFINITE, 32 AIGAR_WARN_NOISE_EXHAUSTED,
+ * 64 AIGAR_WARN_TRAIN_NONFINITE (arena 0 only). */
+#define AIGAR_WARN_TRAIN_NONFINITE 0x40
 #define AIGAR_WARN_Q_NONFINITE 0x8
 #define AIGAR_WARN_NOISE_NONFINITE 0x10
 #define AIGAR_WARN_NOISE_EXHAUSTED 0x20
