@@ -111,6 +111,18 @@ class TrainParams(C.Structure):
                 ("discount", C.c_double)]
 
 
+ACTRAIN_MAX_EPOCHS = 8
+# aigar_net_get_weights' which, the CACLA learner's: the critic, its target, its Adam m and v
+NET_CRITIC, NET_CRITIC_TARGET, NET_CRITIC_M, NET_CRITIC_V = 4, 5, 6, 7
+
+
+class ActrainParams(C.Structure):
+    """aigar_actrain_params (include/aigar.h): the CACLA trainer (actorCritic.py:791-858, 1032-1065)."""
+    _fields_ = [("batch", C.c_int32), ("min_size", C.c_int32), ("target_steps", C.c_int32), ("var_epochs", C.c_int32),
+                ("critic_lr", C.c_double), ("actor_lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("epsilon", C.c_double), ("discount", C.c_double), ("var_start", C.c_double), ("var_beta", C.c_double)]
+
+
 CONV_MAX_LAYERS, CONV_MAX_SIDE, CONV_MAX_CHANNELS, CONV_MAX_KERNEL, CONV_MAX_FILTERS = 3, 128, 8, 8, 64
 
 

@@ -114,6 +114,16 @@ def load(build_if_missing=False):
         "aigar_train_td": [vp, vp, vp],
         "aigar_train_sync_target": [vp],
         "aigar_train_reset": [vp],
+        "aigar_critic_config": [vp, C.POINTER(_abi.NetParams)],
+        "aigar_critic_set_weights": [vp, i32, vp, vp, i32],
+        "aigar_critic_forward": [vp, vp, i32, i32, vp],
+        "aigar_actrain_config": [vp, C.POINTER(_abi.ActrainParams)],
+        "aigar_actrain_step": [vp, i32, vp],
+        "aigar_actrain_info": [vp, C.POINTER(C.c_int64)],
+        "aigar_actrain_td": [vp, vp, vp, vp],
+        "aigar_actrain_var": [vp, C.POINTER(C.c_double)],
+        "aigar_actrain_sync_target": [vp],
+        "aigar_actrain_reset": [vp],
         "aigar_net_get_weights": [vp, i32, i32, vp, vp, i32],
         "aigar_net_pad_check": [vp, i32, C.POINTER(C.c_int64)],
         "aigar_exp_extra_get": [vp, vp, i32, vp, vp],
@@ -209,6 +219,8 @@ class Stepper:
         self.net = None  # (n_in, units, state dtype name) while an acting network is configured
         self.conv = None  # (side, channels, convs) while that network has a conv part (n_in: the flattened length)
         self.trn = None  # the batch while a training is configured
+        self.crit = None  # (n_in, units) while a critic is configured
+        self.act = None  # the batch while a CACLA training is configured
 
     def _chk(self, r):
         if r < 0:
@@ -426,7 +438,7 @@ class Stepper:
         is set every env_step appends the NN players' transitions inside its graph.  extra:
         the ring also keeps the tuple's fifth field (exp_extra_get / exp_extra_set).
         exp_config(None) frees it."""
-        self.trn = None  # (the library drops the train configuration with the memory)
+        self.trn = self.act = None  # (the library drops the train configurations with the memory)
         if not capacity:
             self._chk(self.L.aigar_exp_config(self.h, None))
             self.exp = None
@@ -643,7 +655,7 @@ class Stepper:
         conv layers in front (aigar_net_config_cnn): the states are then images [side, side,
         channels] and n_in is n_flat.  The weights are zero until net_set_weights.
         net_config(None) turns it off."""
-        self.trn = None  # (the library drops the train configuration with the network)
+        self.trn = self.crit = self.act = None  # (the library drops the train configurations and the critic with the network)
         if spec is None:
             self._chk(self.L.aigar_net_config(self.h, None))
             self.net = self.conv = None
@@ -806,6 +818,145 @@ class Stepper:
     def train_reset(self):
         self._need_trn("train_reset")
         self._chk(self.L.aigar_train_reset(self.h))
+
+    # ---- the CACLA learner's critic and trainer (include/aigar.h: aigar_critic*, aigar_actrain*)
+    def critic_config(self, spec, x_dtype="float64"):
+        """The handle's critic V(s): spec is (n_in, units, hidden, "linear") with units[-1] == 1 and
+        the acting network's n_in (aigar_critic_config).  The weights are zero until
+        critic_set_weights.  critic_config(None) turns it off."""
+        self.act = None  # (the library drops the CACLA train configuration with the critic)
+        if spec is None:
+            self._chk(self.L.aigar_critic_config(self.h, None))
+            self.crit = None
+            return
+        n_in, units, hidden, out = spec
+        units = [int(v) for v in units]
+        if not 1 <= len(units) <= 8:
+            raise ValueError("critic_config: %d layers, 1..%d" % (len(units), _abi.NET_MAX_LAYERS))
+        code = lambda a: _abi.ACTIVATIONS[a] if isinstance(a, str) else int(a)
+        d = str(x_dtype).replace("torch.", "")
+        prm = _abi.NetParams(len(units), int(n_in), 0 if d == "float64" else 1, code(hidden), code(out), 0)
+        for i, v in enumerate(units):
+            prm.units[i] = v
+        self._chk(self.L.aigar_critic_config(self.h, C.byref(prm)))
+        self.crit = (int(n_in), tuple(units))
+
+    def _need_crit(self, what):
+        if getattr(self, "crit", None) is None:
+            raise RuntimeError("aigar: %s: no critic is configured (critic_config)" % what)
+        return self.crit
+
+    def critic_set_weights(self, weights):
+        """The critic's weights: a list of (W [in, out], b [out]) float32 per layer, numpy arrays or
+        device tensors (stream-ordered)."""
+        n_in, units = self._need_crit("critic_set_weights")
+        if len(weights) != len(units):
+            raise ValueError("critic_set_weights: %d layers given, the critic has %d" % (len(weights), len(units)))
+        for l, (W, b) in enumerate(weights):
+            shape = (units[l - 1] if l else n_in, units[l])
+            if isinstance(W, np.ndarray) or not hasattr(W, "data_ptr"):
+                W, b = np.ascontiguousarray(W, np.float32), np.ascontiguousarray(b, np.float32)
+            self._check_out(W, shape, ("float32",), "critic_set_weights")
+            self._check_out(b, (shape[1],), ("float32",), "critic_set_weights")
+            (wp, on), (bp, on_b) = _ptr(W), _ptr(b)
+            if on != on_b:
+                raise ValueError("critic_set_weights: W and b both numpy arrays or both device tensors")
+            self._chk(self.L.aigar_critic_set_weights(self.h, l, wp, bp, on))
+
+    def critic_get_weights(self, which="online"):
+        """[(W [in, out], b [out])] float32 numpy arrays of the critic ("online"), or with a CACLA
+        train configuration of its "target", "m" or "v"."""
+        n_in, units = self._need_crit("critic_get_weights")
+        code = {"online": _abi.NET_CRITIC, "target": _abi.NET_CRITIC_TARGET, "m": _abi.NET_CRITIC_M,
+                "v": _abi.NET_CRITIC_V}
+        if which not in code:
+            raise ValueError("critic_get_weights: which must be one of %s" % sorted(code))
+        out = []
+        for l, n in enumerate(units):
+            W, b = np.empty((units[l - 1] if l else n_in, n), np.float32), np.empty((n,), np.float32)
+            self._chk(self.L.aigar_net_get_weights(self.h, code[which], l, _ptr(W)[0], _ptr(b)[0], 0))
+            out.append((W, b))
+        return out
+
+    def critic_pad_check(self, which="online"):
+        code = {"online": _abi.NET_CRITIC, "target": _abi.NET_CRITIC_TARGET, "m": _abi.NET_CRITIC_M,
+                "v": _abi.NET_CRITIC_V}
+        v = C.c_int64()
+        self._chk(self.L.aigar_net_pad_check(self.h, code[which], C.byref(v)))
+        return int(v.value)
+
+    def critic_forward(self, x, out):
+        """V(s) on device tensors (aigar_critic_forward): x [rows, n_in] float64 / float32 -> out
+        [rows] float64."""
+        n_in, _ = self._need_crit("critic_forward")
+        rows = int(x.shape[0])
+        self._check_dev(x, (rows, n_in), ("float64", "float32"), "critic_forward")
+        self._check_dev(out, (rows,), ("float64",), "critic_forward")
+        self._chk(self.L.aigar_critic_forward(self.h, C.c_void_p(x.data_ptr()), 0 if str(x.dtype) == "torch.float64" else 1,
+                                              rows, C.c_void_p(out.data_ptr())))
+
+    def actrain_config(self, batch=32, min_size=0, target_steps=0, var_epochs=0, critic_lr=7.5e-5, actor_lr=5e-4,
+                       beta1=0.9, beta2=0.999, epsilon=1e-7, discount=0.9, var_start=1.0, var_beta=0.001):
+        """The CACLA trainer of the handle's actor and critic on its replay memory
+        (aigar_actrain_config).  Needs net_config (dense, sigmoid head), critic_config and
+        exp_config.  actrain_config(None) turns it off."""
+        if batch is None:
+            self._chk(self.L.aigar_actrain_config(self.h, None))
+            self.act = None
+            return
+        prm = _abi.ActrainParams(int(batch), int(min_size), int(target_steps), int(var_epochs), float(critic_lr),
+                                 float(actor_lr), float(beta1), float(beta2), float(epsilon), float(discount),
+                                 float(var_start), float(var_beta))
+        self._chk(self.L.aigar_actrain_config(self.h, C.byref(prm)))
+        self.act = int(batch)
+
+    def _need_act(self, what):
+        if getattr(self, "act", None) is None:
+            raise RuntimeError("aigar: %s: no CACLA training is configured (actrain_config)" % what)
+        return self.act
+
+    def actrain_step(self, n=1, u=None):
+        """n CACLA training steps, one graph replay each (aigar_actrain_step); u as train_step's."""
+        batch = self._need_act("actrain_step")
+        up = None
+        if u is not None:
+            self._check_dev(u, (int(n), batch), ("float64",), "actrain_step")
+            up = C.c_void_p(u.data_ptr())
+        self._chk(self.L.aigar_actrain_step(self.h, int(n), up))
+
+    def actrain_info(self):
+        """The CACLA trainer's counters (aigar_actrain_info: the one synchronising read)."""
+        self._need_act("actrain_info")
+        v = (C.c_int64 * 8)()
+        self._chk(self.L.aigar_actrain_info(self.h, v))
+        return {"steps": v[0], "skipped": v[1], "since_target": v[2], "actor_epochs": v[3], "selected": v[4],
+                "epochs": v[5], "cut": v[6], "epochs_skipped": v[7]}
+
+    def actrain_td(self, td=None, idx=None, count=None):
+        """The last drawn step's TD errors, memory indices and per-row actor epochs into the device
+        tensors td [batch] float64, idx [batch] int64 and count [batch] int32."""
+        batch = self._need_act("actrain_td")
+        ptrs = []
+        for t, dt in ((td, "float64"), (idx, "int64"), (count, "int32")):
+            if t is not None:
+                self._check_dev(t, (batch,), (dt,), "actrain_td")
+            ptrs.append(None if t is None else C.c_void_p(t.data_ptr()))
+        self._chk(self.L.aigar_actrain_td(self.h, *ptrs))
+
+    def actrain_var(self):
+        """CACLA-Var's running variance (a host round trip)."""
+        self._need_act("actrain_var")
+        v = C.c_double()
+        self._chk(self.L.aigar_actrain_var(self.h, C.byref(v)))
+        return float(v.value)
+
+    def actrain_sync_target(self):
+        self._need_act("actrain_sync_target")
+        self._chk(self.L.aigar_actrain_sync_target(self.h))
+
+    def actrain_reset(self):
+        self._need_act("actrain_reset")
+        self._chk(self.L.aigar_actrain_reset(self.h))
 
     def net_forward(self, x, out):
         """The network alone on device tensors (aigar_net_forward): x [rows, n_in] float64 /

@@ -58,6 +58,7 @@ using namespace aigar;
 #include "net.inc"
 #include "conv.inc"
 #include "train.inc"
+#include "actrain.inc"
 
 static thread_local std::string g_err;
 static int fail(const char *fmt, ...) {
@@ -314,7 +315,15 @@ struct aigar_handle {
   Train trn;
   DevBlock trn_mem;
   KeyedSlot<TrainKey> train;
-  GraphSlot *const slots[8] = {&step, &run, &run_u, &env, &tb, &te, &tr, &train};
+  // aigar_critic_config: the CACLA learner's critic, a second network (n_layers 0: off)
+  Net crit{};
+  DevBlock crit_mem;
+  float *crit_stage = nullptr;  // aigar_critic_set_weights' staging of host weights (one of crit_mem)
+  // aigar_actrain_config: the CACLA trainer (actrain.inc; batch 0: off) and its step's graph
+  ACTrain act;
+  DevBlock act_mem;
+  KeyedSlot<TrainKey> actrain;
+  GraphSlot *const slots[9] = {&step, &run, &run_u, &env, &tb, &te, &tr, &train, &actrain};
 };
 
 void GraphSlot::drop(aigar_handle *h) {
@@ -378,7 +387,7 @@ static void free_all(aigar_handle *h) {
   h->pix_bytes = 0;
   if (h->d_pix_hist) (void)hipFree(h->d_pix_hist);
   h->d_pix_hist = nullptr;
-  for (DevBlock *m : {&h->exp_mem, &h->dec_mem, &h->noi_mem, &h->net_mem, &h->trn_mem}) m->release();
+  for (DevBlock *m : {&h->exp_mem, &h->dec_mem, &h->noi_mem, &h->net_mem, &h->trn_mem, &h->crit_mem, &h->act_mem}) m->release();
   if (h->d_exp_off) (void)hipFree(h->d_exp_off);
   h->d_exp_off = nullptr;
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1465,6 +1474,18 @@ static void train_free(aigar_handle *h) {
   h->trn_mem.release();
   h->trn = Train{};
 }
+// ... and so does the CACLA trainer's, which also goes with the critic
+static void actrain_free(aigar_handle *h) {
+  h->actrain.drop(h);
+  h->act_mem.release();
+  h->act = ACTrain{};
+}
+static void critic_free(aigar_handle *h) {
+  actrain_free(h);
+  h->crit_mem.release();
+  h->crit = Net{};
+  h->crit_stage = nullptr;
+}
 static int need_dec(aigar_handle *h, const char *who) {
   return need(h, h && h->dec.n_out, who, "no action selection is configured (aigar_decide_config)");
 }
@@ -1670,6 +1691,7 @@ extern "C" int aigar_net_config(aigar_handle *h, const aigar_net_params *p) {
   if (p && h->d.tiled) return fail("net_config: a tiled handle has no acting network");
   if (begin_reconfig(h)) return -1;
   train_free(h);
+  critic_free(h);
   net_free(h);
   if (!p) return 0;
   Net c{};
@@ -2071,6 +2093,7 @@ extern "C" int aigar_exp_config(aigar_handle *h, const aigar_exp_params *p) {
   }
   if (begin_reconfig(h)) return -1;  // (no reader of the memory is pending either)
   train_free(h);
+  actrain_free(h);
   h->exp_mem.release();
   h->exp = Exp{};
   if (!on) return 0;
@@ -2491,27 +2514,390 @@ extern "C" int aigar_train_reset(aigar_handle *h) {
   return 0;
 }
 
+// ------------------------------------------------------------ CACLA: the critic and the trainer
+static int need_crit(aigar_handle *h, const char *who) {
+  return need(h, h && h->crit.n_layers, who, "no critic is configured (aigar_critic_config)");
+}
+static int need_act(aigar_handle *h, const char *who) {
+  return need(h, h && h->act.batch, who, "no CACLA training is configured (aigar_actrain_config)");
+}
+
+extern "C" int aigar_critic_config(aigar_handle *h, const aigar_net_params *p) {
+  if (p) {  // (before the handle: a bad set has its own message)
+    if (p->n_layers < 1 || p->n_layers > kNetMaxLayers)
+      return fail("critic_config: n_layers = %d is outside 1..%d", p->n_layers, kNetMaxLayers);
+    if (p->n_in < 1 || p->n_in > kNetMaxIn) return fail("critic_config: n_in = %d is outside 1..%d", p->n_in, kNetMaxIn);
+    for (int l = 0; l < p->n_layers; l++)
+      if (p->units[l] < 1 || p->units[l] > kNetMaxUnits)
+        return fail("critic_config: layer %d has %d units, outside 1..%d", l, p->units[l], kNetMaxUnits);
+    if (p->x_dtype != 0 && p->x_dtype != 1) return fail("critic_config: x_dtype must be 0 (float64) or 1 (float32)");
+    if (p->hidden_act != AIGAR_ACT_RELU && p->hidden_act != AIGAR_ACT_LINEAR)
+      return fail("critic_config: hidden activation %d (%s) is not supported: relu or linear", p->hidden_act,
+                  net_act_name(p->hidden_act));
+    if (p->units[p->n_layers - 1] != 1 || p->out_act != AIGAR_ACT_LINEAR)
+      return fail("critic_config: the head has %d units with activation %d (%s), V(s) is one linear unit",
+                  p->units[p->n_layers - 1], p->out_act, net_act_name(p->out_act));
+  }
+  if (!h) return fail("null handle");
+  if (p) {
+    if (need_net(h, "critic_config")) return -1;
+    if (h->conv.n_conv) return fail("critic_config: the acting network has a conv part, the critic is a dense network");
+    if (p->n_in != h->net.in[0])
+      return fail("critic_config: n_in = %d differs from the acting network's %d", p->n_in, h->net.in[0]);
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));  // (no training step or forward pass is pending)
+  critic_free(h);
+  if (!p) return 0;
+  Net c{};
+  c.n_layers = p->n_layers;
+  c.x_dtype = p->x_dtype;
+  c.hid_act = p->hidden_act;
+  c.out_act = AIGAR_ACT_LINEAR;
+  size_t stage = 0;
+  bool ok = true;
+  for (int l = 0; l < c.n_layers && ok; l++) {
+    c.in[l] = l ? p->units[l - 1] : p->n_in;
+    c.out[l] = p->units[l];
+    const size_t ip = net_in_pad(c.in[l]), op = net_out_pad(c.out[l]);
+    c.w[l] = (float *)h->crit_mem.alloc(ip * op * sizeof(float), true, h->stream);
+    c.b[l] = (float *)h->crit_mem.alloc(op * sizeof(float), true, h->stream);
+    ok = c.w[l] && c.b[l];
+    stage = std::max(stage, (size_t)c.in[l] * c.out[l] + c.out[l]);
+  }
+  if (ok) ok = (h->crit_stage = (float *)h->crit_mem.alloc(stage * sizeof(float), true, h->stream)) != nullptr;
+  if (!ok) {
+    critic_free(h);
+    return fail("critic_config: out of device memory");
+  }
+  HIPCHK(hipGetLastError());
+  h->crit = c;
+  return 0;
+}
+
+extern "C" int aigar_critic_set_weights(aigar_handle *h, int layer, const float *W, const float *b, int on_device) {
+  if (need_crit(h, "critic_set_weights")) return -1;
+  const Net &c = h->crit;
+  if (layer < 0 || layer >= c.n_layers)
+    return fail("critic_set_weights: layer %d is outside 0..%d", layer, c.n_layers - 1);
+  if (!W || !b) return fail("critic_set_weights: null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const int in = c.in[layer], out = c.out[layer];
+  const size_t nw = (size_t)in * out;
+  if (!on_device) {
+    HIPCHK(hipMemcpyAsync(h->crit_stage, W, nw * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->crit_stage + nw, b, (size_t)out * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    W = h->crit_stage;
+    b = h->crit_stage + nw;
+  }
+  const int ip = net_in_pad(in), op = net_out_pad(out);
+  const size_t n = (size_t)ip * op;
+  hipLaunchKernelGGL(k_net_pack, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, h->stream, W, b,
+                     c.w[layer], c.b[layer], in, out, ip, op);
+  HIPCHK(hipGetLastError());
+  if (!on_device) HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's arrays are read, the staging is free)
+  return 0;
+}
+
+extern "C" int aigar_critic_forward(aigar_handle *h, const void *x, int x_dtype, int rows, double *out) {
+  if (need_crit(h, "critic_forward")) return -1;
+  if (!x || !out) return fail("critic_forward: null argument");
+  if (x_dtype != 0 && x_dtype != 1) return fail("critic_forward: x_dtype must be 0 (float64) or 1 (float32)");
+  if (rows < 1 || rows > (1 << 30)) return fail("critic_forward: rows = %d is outside 1..2^30", rows);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  Net c = h->crit;
+  c.x_dtype = x_dtype;
+  launch_net(h->stream, c, x, rows, out, nullptr, nullptr);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int aigar_actrain_config(aigar_handle *h, const aigar_actrain_params *p) {
+  if (p) {  // (before the handle: a bad set has its own message)
+    const double inf = __builtin_inf();
+    if (p->batch < 1 || p->batch > kTrainMaxBatch)
+      return fail("actrain_config: batch = %d is outside 1..%d", p->batch, kTrainMaxBatch);
+    if (p->min_size < 0) return fail("actrain_config: min_size = %d is negative", p->min_size);
+    if (p->target_steps < 0) return fail("actrain_config: target_steps = %d is negative", p->target_steps);
+    if (p->var_epochs < 0 || p->var_epochs > AIGAR_ACTRAIN_MAX_EPOCHS)
+      return fail("actrain_config: var_epochs = %d is outside 0..%d", p->var_epochs, AIGAR_ACTRAIN_MAX_EPOCHS);
+    if (!(p->critic_lr > 0) || !(p->critic_lr < inf))
+      return fail("actrain_config: critic_lr = %g must be positive and finite", p->critic_lr);
+    if (!(p->actor_lr > 0) || !(p->actor_lr < inf))
+      return fail("actrain_config: actor_lr = %g must be positive and finite", p->actor_lr);
+    if (!(p->beta1 >= 0 && p->beta1 < 1)) return fail("actrain_config: beta1 = %g is outside [0, 1)", p->beta1);
+    if (!(p->beta2 >= 0 && p->beta2 < 1)) return fail("actrain_config: beta2 = %g is outside [0, 1)", p->beta2);
+    if (!(p->epsilon > 0) || !(p->epsilon < inf))
+      return fail("actrain_config: epsilon = %g must be positive and finite", p->epsilon);
+    if (!(p->discount >= 0 && p->discount <= 1)) return fail("actrain_config: discount = %g is outside [0, 1]", p->discount);
+    if (!(p->var_start > 0) || !(p->var_start < inf))
+      return fail("actrain_config: var_start = %g must be positive and finite", p->var_start);
+    if (!(p->var_beta >= 0 && p->var_beta < 1)) return fail("actrain_config: var_beta = %g is outside [0, 1)", p->var_beta);
+  }
+  if (!h) return fail("null handle");
+  if (p) {
+    if (h->d.tiled) return fail("actrain_config: a tiled handle has no training");
+    if (need_net(h, "actrain_config")) return -1;
+    if (h->conv.n_conv) return fail("actrain_config: a network with a conv part is not trained on the device");
+    if (h->net.out_act != AIGAR_ACT_SIGMOID)
+      return fail("actrain_config: the network's head is %s, the CACLA actor needs a sigmoid head",
+                  net_act_name(h->net.out_act));
+    if (h->net.out[h->net.n_layers - 1] > 4)
+      return fail("actrain_config: the actor has %d outputs, a stored action has at most 4", h->net.out[h->net.n_layers - 1]);
+    if (need_crit(h, "actrain_config")) return -1;
+    if (need_exp(h, "actrain_config")) return -1;
+    if (h->net.in[0] != h->exp.L)
+      return fail("actrain_config: the network has %d inputs, the memory's states %d values", h->net.in[0], h->exp.L);
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  actrain_free(h);
+  if (!p) return 0;
+  const Exp &e = h->exp;
+  ACTrain t;
+  t.batch = p->batch;
+  t.var_epochs = p->var_epochs;
+  t.var_start = p->var_start;
+  t.var_beta = p->var_beta;
+  bool ok = true;
+  auto get = [&](size_t bytes) -> void * {
+    if (!ok) return nullptr;
+    void *q = h->act_mem.alloc(bytes, true, h->stream);
+    ok = q != nullptr;
+    return q;
+  };
+  const size_t B = (size_t)p->batch, row = (size_t)e.L * e.esz;
+  Train s;  // what the two views share: the settings and the staged batch
+  s.batch = p->batch;
+  s.bpad = (p->batch + kNetRows - 1) / kNetRows * kNetRows;
+  s.min_size = p->min_size;
+  s.target_steps = p->target_steps;
+  s.beta1 = p->beta1;
+  s.beta2 = p->beta2;
+  s.epsilon = p->epsilon;
+  s.discount = p->discount;
+  s.s = (char *)get(B * row);
+  s.s2 = (char *)get(B * row);
+  s.a = (double *)get(B * 4 * sizeof(double));
+  s.r = (double *)get(B * sizeof(double));
+  s.w = (double *)get(B * sizeof(double));
+  s.u = (double *)get(B * sizeof(double));
+  s.done = (uint8_t *)get(B);
+  s.idx = (int64_t *)get(B * sizeof(int64_t));
+  s.td = (double *)get(B * sizeof(double));
+  s.prio = (double *)get(B * sizeof(double));
+  auto view = [&](const Net &c, double lr, bool target) {
+    Train v = s;
+    v.lr = lr;
+    for (int l = 0; l < c.n_layers; l++) {
+      const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
+      if (target) {
+        v.tw[l] = (float *)get(nw);
+        v.tb[l] = (float *)get(op * sizeof(float));
+      }
+      v.mw[l] = (float *)get(nw);
+      v.mb[l] = (float *)get(op * sizeof(float));
+      v.vw[l] = (float *)get(nw);
+      v.vb[l] = (float *)get(op * sizeof(float));
+      v.tile0[l + 1] = v.tile0[l] + (c.in[l] + 15) / 16 * (int)(op / 16);
+      if (ok && target) {
+        (void)hipMemcpyAsync(v.tw[l], c.w[l], nw, hipMemcpyDeviceToDevice, h->stream);
+        (void)hipMemcpyAsync(v.tb[l], c.b[l], op * sizeof(float), hipMemcpyDeviceToDevice, h->stream);
+      }
+    }
+    const size_t n_out = (size_t)c.out[c.n_layers - 1];
+    v.q = (double *)get(B * n_out * sizeof(double));
+    if (target) v.q2 = (double *)get(B * n_out * sizeof(double));
+    v.hsave = (float *)get((size_t)std::max(c.n_layers - 1, 1) * v.bpad * kNetMaxUnits * sizeof(float));
+    v.delta = (float *)get((size_t)c.n_layers * v.bpad * kNetMaxUnits * sizeof(float));
+    v.ctl = (TrainCtl *)get(sizeof(TrainCtl));
+    return v;
+  };
+  t.c = view(h->crit, p->critic_lr, true);
+  t.a = view(h->net, p->actor_lr, false);
+  t.count = (int32_t *)get(B * sizeof(int32_t));
+  t.x = (ACtl *)get(sizeof(ACtl));
+  if (!ok) {
+    h->act_mem.release();
+    return fail("actrain_config: out of device memory");
+  }
+  hipLaunchKernelGGL(k_actrain_clear, dim3(1), dim3(1), 0, h->stream, t.c.ctl, t.a.ctl, t.x, t.var_start);
+  HIPCHK(hipGetLastError());
+  h->act = t;
+  return 0;
+}
+
+// One CACLA training step's launches on stream s (actrain.inc).
+static void launch_actrain_step(aigar_handle *h, hipStream_t s, int has_u) {
+  const ACTrain &t = h->act;
+  const Train &c = t.c, &a = t.a;
+  const Exp &e = h->exp;
+  Net cr = h->crit, tg = h->crit, ac = h->net;
+  cr.x_dtype = tg.x_dtype = ac.x_dtype = e.dtype;
+  for (int l = 0; l < tg.n_layers; l++) {
+    tg.w[l] = c.tw[l];
+    tg.b[l] = c.tb[l];
+  }
+  const int B = t.batch, n_out = ac.out[ac.n_layers - 1];
+  const dim3 rows16((unsigned)(c.bpad / kNetRows)), net_block(64 * kNetWaves);
+  auto save = [&](const Net &n, const Train &v) {
+    if (e.dtype == 0) hipLaunchKernelGGL(k_net_save<double>, rows16, net_block, 0, s, n, (const double *)v.s, B, v.q, v.hsave);
+    else hipLaunchKernelGGL(k_net_save<float>, rows16, net_block, 0, s, n, (const float *)v.s, B, v.q, v.hsave);
+  };
+  auto update = [&](const Net &n, const Train &v) {
+    if (n.n_layers > 1) hipLaunchKernelGGL(k_net_bwd, rows16, net_block, 0, s, n, v);
+    if (e.dtype == 0) hipLaunchKernelGGL(k_net_grad_adam<double>, dim3(v.tile0[n.n_layers]), dim3(64), 0, s, n, v);
+    else hipLaunchKernelGGL(k_net_grad_adam<float>, dim3(v.tile0[n.n_layers]), dim3(64), 0, s, n, v);
+  };
+  hipLaunchKernelGGL(k_exp_draw, dim3((B + 255) / 256), dim3(256), 0, s, e, B, has_u ? c.u : (const double *)nullptr, c.w,
+                     c.idx);
+  if (e.dtype == 0) hipLaunchKernelGGL(k_exp_fetch<uint64_t>, dim3(B), dim3(256), 0, s, e, c.idx, c.s, c.a, c.r, c.s2, c.done, 0);
+  else hipLaunchKernelGGL(k_exp_fetch<uint32_t>, dim3(B), dim3(256), 0, s, e, c.idx, c.s, c.a, c.r, c.s2, c.done, 0);
+  save(cr, c);
+  launch_net(s, tg, c.s2, B, c.q2, nullptr, nullptr);
+  hipLaunchKernelGGL(k_td_v, dim3(1), dim3(kTrainMaxBatch), 0, s, t, e, h->d, cr.n_layers);
+  update(cr, c);
+  if (e.prio) hipLaunchKernelGGL(k_exp_update, dim3(1), dim3(kExpPlanThreads), 0, s, e, c.idx, c.prio, B);
+  for (int ep = 0; ep < std::max(t.var_epochs, 1); ep++) {
+    save(ac, a);
+    hipLaunchKernelGGL(k_actor_delta, dim3(1), dim3(kTrainMaxBatch), 0, s, t, h->d, ep, ac.n_layers, n_out);
+    update(ac, a);
+  }
+  hipLaunchKernelGGL(k_train_tail, dim3(64), dim3(256), 0, s, cr, c);
+}
+
+extern "C" int aigar_actrain_step(aigar_handle *h, int n_steps, const double *u) {
+  if (need_act(h, "actrain_step")) return -1;
+  if (n_steps < 1) return fail("actrain_step: n_steps = %d is below 1", n_steps);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  TrainKey k;
+  key_clear(k);
+  k.has_u = u ? 1 : 0;
+  const bool graph = h->use_graph;
+  if (graph && !h->actrain.ensure(h, k, [&](hipStream_t cs) { launch_actrain_step(h, cs, k.has_u); }))
+    return fail("actrain_step: graph capture failed");
+  Mark m(h, "actrain_step");
+  const size_t B = (size_t)h->act.batch;
+  for (int i = 0; i < n_steps; i++) {
+    if (u) HIPCHK(hipMemcpyAsync(h->act.c.u, u + (size_t)i * B, B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (graph) HIPCHK(h->actrain.launch(h));
+    else launch_actrain_step(h, h->stream, k.has_u);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int aigar_actrain_info(aigar_handle *h, int64_t info[8]) {
+  if (need_act(h, "actrain_info")) return -1;
+  if (!info) return fail("actrain_info: null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  TrainCtl c, a;
+  ACtl x;
+  HIPCHK(hipMemcpyAsync(&c, h->act.c.ctl, sizeof c, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(&a, h->act.a.ctl, sizeof a, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(&x, h->act.x, sizeof x, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  info[0] = c.t;
+  info[1] = c.skipped;
+  info[2] = c.since;
+  info[3] = a.t;
+  info[4] = x.sel;
+  info[5] = x.epochs;
+  info[6] = x.cut;
+  info[7] = x.eskipped;
+  return 0;
+}
+
+extern "C" int aigar_actrain_td(aigar_handle *h, double *td, int64_t *idx, int32_t *count) {
+  if (need_act(h, "actrain_td")) return -1;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const ACTrain &t = h->act;
+  const size_t B = (size_t)t.batch;
+  if (td) HIPCHK(hipMemcpyAsync(td, t.c.td, B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  if (idx) HIPCHK(hipMemcpyAsync(idx, t.c.idx, B * sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream));
+  if (count) HIPCHK(hipMemcpyAsync(count, t.count, B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+  return 0;
+}
+
+extern "C" int aigar_actrain_var(aigar_handle *h, double *var) {
+  if (need_act(h, "actrain_var")) return -1;
+  if (!var) return fail("actrain_var: null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  ACtl x;
+  HIPCHK(hipMemcpyAsync(&x, h->act.x, sizeof x, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  *var = x.var;
+  return 0;
+}
+
+extern "C" int aigar_actrain_sync_target(aigar_handle *h) {
+  if (need_act(h, "actrain_sync_target")) return -1;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const Net &c = h->crit;
+  const Train &t = h->act.c;
+  for (int l = 0; l < c.n_layers; l++) {
+    const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
+    HIPCHK(hipMemcpyAsync(t.tw[l], c.w[l], nw, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(t.tb[l], c.b[l], op * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  }
+  hipLaunchKernelGGL(k_train_clear, dim3(1), dim3(1), 0, h->stream, t.ctl, 1);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int aigar_actrain_reset(aigar_handle *h) {
+  if (need_act(h, "actrain_reset")) return -1;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const ACTrain &t = h->act;
+  for (int k = 0; k < 2; k++) {
+    const Net &c = k ? h->net : h->crit;
+    const Train &v = k ? t.a : t.c;
+    for (int l = 0; l < c.n_layers; l++) {
+      const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
+      HIPCHK(hipMemsetAsync(v.mw[l], 0, nw, h->stream));
+      HIPCHK(hipMemsetAsync(v.vw[l], 0, nw, h->stream));
+      HIPCHK(hipMemsetAsync(v.mb[l], 0, op * sizeof(float), h->stream));
+      HIPCHK(hipMemsetAsync(v.vb[l], 0, op * sizeof(float), h->stream));
+    }
+  }
+  hipLaunchKernelGGL(k_actrain_clear, dim3(1), dim3(1), 0, h->stream, t.c.ctl, t.a.ctl, t.x, t.var_start);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // which: 0 online, 1 target, 2 Adam's m, 3 Adam's v (the last three need a train configuration)
-static int net_which(aigar_handle *h, const char *who, int which, int layer, const float **wp, const float **bp) {
+// 4 the critic (needs only a critic), 5 its target, 6 / 7 its Adam state (an actrain configuration,
+// under which 2 / 3 are the actor's Adam state and 1 is refused).  *np: the network whose shape it has.
+static int net_which(aigar_handle *h, const char *who, int which, int layer, const Net **np, const float **wp,
+                     const float **bp) {
   if (need_net(h, who)) return -1;
-  if (which < 0 || which > 3) return fail("%s: which = %d is outside 0..3", who, which);
-  if (layer < 0 || layer >= h->net.n_layers) return fail("%s: layer %d is outside 0..%d", who, layer, h->net.n_layers - 1);
-  if (which && need_trn(h, who)) return -1;
-  const Train &t = h->trn;
-  *wp = which == 0 ? h->net.w[layer] : which == 1 ? t.tw[layer] : which == 2 ? t.mw[layer] : t.vw[layer];
-  *bp = which == 0 ? h->net.b[layer] : which == 1 ? t.tb[layer] : which == 2 ? t.mb[layer] : t.vb[layer];
+  if (which < 0 || which > 7) return fail("%s: which = %d is outside 0..7", who, which);
+  const bool crit = which >= 4;
+  if (crit && !h->crit.n_layers) return fail("%s: no critic is configured (aigar_critic_config)", who);
+  const Net &c = crit ? h->crit : h->net;
+  if (layer < 0 || layer >= c.n_layers) return fail("%s: layer %d is outside 0..%d", who, layer, c.n_layers - 1);
+  if (which == 1 && h->act.batch) return fail("%s: which = 1: CACLA keeps no actor target", who);
+  if (which > 4 && need_act(h, who)) return -1;
+  if (which >= 1 && which <= 3 && !h->act.batch && need_trn(h, who)) return -1;
+  const Train &t = crit ? h->act.c : h->act.batch ? h->act.a : h->trn;
+  const int k = which & 3;
+  *np = &c;
+  *wp = k == 0 ? c.w[layer] : k == 1 ? t.tw[layer] : k == 2 ? t.mw[layer] : t.vw[layer];
+  *bp = k == 0 ? c.b[layer] : k == 1 ? t.tb[layer] : k == 2 ? t.mb[layer] : t.vb[layer];
   return 0;
 }
 
 extern "C" int aigar_net_get_weights(aigar_handle *h, int which, int layer, float *W, float *b, int on_device) {
   const float *wp, *bp;
-  if (net_which(h, "net_get_weights", which, layer, &wp, &bp)) return -1;
+  const Net *np;
+  if (net_which(h, "net_get_weights", which, layer, &np, &wp, &bp)) return -1;
   if (h->conv.n_conv) return fail("net_get_weights: a network with a conv part has no read-back");
   if (!W || !b) return fail("net_get_weights: null argument");
   HIPCHK(hipSetDevice(h->cfg.device));
-  const int in = h->net.in[layer], out = h->net.out[layer];
+  const int in = np->in[layer], out = np->out[layer];
   const size_t nw = (size_t)in * out;
-  float *dW = on_device ? W : h->net_stage, *db = on_device ? b : h->net_stage + nw;
+  float *stage = which >= 4 ? h->crit_stage : h->net_stage;
+  float *dW = on_device ? W : stage, *db = on_device ? b : stage + nw;
   hipLaunchKernelGGL(k_net_unpack, dim3((unsigned)std::min<size_t>((nw + 255) / 256, 4096)), dim3(256), 0, h->stream, wp, bp,
                      dW, db, in, out, net_out_pad(out));
   HIPCHK(hipGetLastError());
@@ -2525,15 +2911,16 @@ extern "C" int aigar_net_get_weights(aigar_handle *h, int which, int layer, floa
 
 extern "C" int aigar_net_pad_check(aigar_handle *h, int which, int64_t *count) {
   const float *wp, *bp;
-  if (net_which(h, "net_pad_check", which, 0, &wp, &bp)) return -1;
+  const Net *np;
+  if (net_which(h, "net_pad_check", which, 0, &np, &wp, &bp)) return -1;
   if (!count) return fail("net_pad_check: null argument");
   HIPCHK(hipSetDevice(h->cfg.device));
   unsigned long long *dc = nullptr, n = 0;
   HIPCHK(hipMalloc((void **)&dc, sizeof n));
   hipError_t er = hipMemsetAsync(dc, 0, sizeof n, h->stream);
-  for (int l = 0; l < h->net.n_layers && er == hipSuccess; l++) {
-    (void)net_which(h, "net_pad_check", which, l, &wp, &bp);
-    const int in = h->net.in[l], out = h->net.out[l], ip = net_in_pad(in), op = net_out_pad(out);
+  for (int l = 0; l < np->n_layers && er == hipSuccess; l++) {
+    (void)net_which(h, "net_pad_check", which, l, &np, &wp, &bp);
+    const int in = np->in[l], out = np->out[l], ip = net_in_pad(in), op = net_out_pad(out);
     hipLaunchKernelGGL(k_net_pad_count, dim3((unsigned)std::min<size_t>(((size_t)ip * op + 255) / 256, 4096)), dim3(256), 0,
                        h->stream, wp, bp, in, out, ip, op, dc);
     er = hipGetLastError();

@@ -94,7 +94,17 @@ activations; what the device cannot evaluate is refused there); a (n_in, units, 
 overrides it.  The weights are zero until the first `set_weights`.  Epsilon, temperature and the
 noise level are read from `explore` / `noise_std` at every decision, so `collect(n)` uses what
 they hold for all n: a decay schedule is written between calls.
-The trainer (`train=True` or a dict, with `discrete=`, `network=` and `memory=`):
+The CACLA trainer (`train=True` or a dict, with `continuous=`, `network=` and `memory=`):
+the reference's default learner (actorCritic.py, ALGORITHM "CACLA", CACLA-Var included) on the device.
+The critic V(s) is a second network of the handle (`critic=` overrides aigar_amd.net.critic_spec's
+CACLA_CRITIC_LAYERS); `train(n)` makes n steps -- the critic's update, then the actor's epochs on the
+rows with a positive TD error, in place on the acting network's weights -- one graph replay each, and
+the next `collect` acts with the trained actor.  `set_critic_weights()`, `get_critic_weights(target=)`,
+`critic_value(states)` and `cacla_var()` reach the critic and the variance; `train_info()` has this
+learner's counters.  `train=True` reads CACLA_CRITIC_ALPHA, CACLA_ACTOR_ALPHA, DISCOUNT,
+TARGET_NETWORK_STEPS, NUM_EXPS_BEFORE_TRAIN, CACLA_VAR_ENABLED / _START / _BETA; what the device does
+not do is refused by name (aigar_amd.net.actrain_params).
+The Q-learning trainer (`train=True` or a dict, with `discrete=`, `network=` and `memory=`):
 the reference's Q-learning trainer (qLearning.py:116-193, Keras 2.2.4 Adam on the importance-weighted
 mse, a hard target copy every TARGET_NETWORK_STEPS) on the device, in place on the acting network's
 weights: `train(n)` makes n steps on the replay memory, one graph replay each, and the next decision
@@ -126,7 +136,7 @@ class AgarVecEnv:
     def __init__(self, n_players, parameters=None, n_arenas=1, virus=None, field_size=0, max_pellets=-1.0,
                  max_viruses=-1.0, device=0, torch_stream=True, roles=None, reset_limit=None, desync=True, seed=0,
                  score=False, pixels=None, pixel_dtype=None, memory=None, discrete=None, continuous=None, network=None,
-                 train=None):
+                 train=None, critic=None):
         import torch
         if continuous and discrete:
             raise ValueError("continuous= and discrete= exclude each other (one learner decides per env)")
@@ -310,7 +320,33 @@ class AgarVecEnv:
             self.net_output = None
 
         self.training = None
-        if train:  # (explicit only, as memory=)
+        self.cacla = False  # (the trainer is the CACLA learner's: DESIGN.md §4m)
+        self.critic = None
+        if critic is not None and not (train and self.continuous is not None):
+            raise ValueError("critic= needs continuous= and train= (the CACLA trainer's critic)")
+        if train and self.continuous is not None:  # (explicit only, as memory=)
+            if self.network is None or self.memory is None:
+                raise ValueError("train= with continuous= needs network= and memory= (CACLA on the device's replay "
+                                 "memory)")
+            if self.pixels is not None or hasattr(self.network, "convs"):
+                raise ValueError("train=: CNN / pixel states are not trained on the device")
+            tp = _net.actrain_params(parameters)
+            tp["batch"] = int(self.memory["batch"])
+            if isinstance(train, dict):
+                unknown = set(train) - set(tp)
+                if unknown:
+                    raise ValueError("train: unknown keys %s" % sorted(unknown))
+                tp.update(train)
+            n_in = int(self.stepper.obs_len)
+            cs = _net.critic_spec(parameters, n_in=n_in) if critic is None else _net.NetSpec(*critic)
+            if cs.n_in is None:
+                cs = cs._replace(n_in=n_in)
+            self.critic = cs
+            self.stepper.critic_config(cs, self.obs.dtype)
+            self.training = tp
+            self.cacla = True
+            self.stepper.actrain_config(**tp)
+        elif train:
             if self.discrete is None or self.network is None or self.memory is None:
                 raise ValueError("train= needs discrete=, network= and memory= (Q-learning on the device's replay memory)")
             if self.pixels is not None or hasattr(self.network, "convs"):
@@ -349,14 +385,18 @@ class AgarVecEnv:
             u = torch.as_tensor(u, dtype=torch.float64, device=self.dev).reshape(n, self.training["batch"]).contiguous()
         if self._mem_sync:
             torch.cuda.synchronize(self.dev)
-        self.stepper.train_step(n, u)
+        if self.cacla:
+            self.stepper.actrain_step(n, u)
+        else:
+            self.stepper.train_step(n, u)
         if self._mem_sync:
             self.stepper.sync()  # (u is freed when this returns)
 
     def train_info(self):
-        """{steps, skipped, since_target} (aigar_train_info: a host round trip)."""
+        """{steps, skipped, since_target} (aigar_train_info: a host round trip); the CACLA trainer's
+        also has actor_epochs, selected, epochs, cut and epochs_skipped (aigar_actrain_info)."""
         self._need_training()
-        return self.stepper.train_info()
+        return self.stepper.actrain_info() if self.cacla else self.stepper.train_info()
 
     def train_td(self):
         """(td [batch] float64, idx [batch] int64) of the last drawn training step, device tensors."""
@@ -367,7 +407,10 @@ class AgarVecEnv:
         idx = torch.empty(b, dtype=torch.int64, device=self.dev)
         if self._mem_sync:
             torch.cuda.synchronize(self.dev)
-        self.stepper.train_td(td, idx)
+        if self.cacla:
+            self.stepper.actrain_td(td, idx)
+        else:
+            self.stepper.train_td(td, idx)
         if self._mem_sync:
             self.stepper.sync()
         return td, idx
@@ -384,6 +427,58 @@ class AgarVecEnv:
         if self._mem_sync:
             self.torch.cuda.synchronize(self.dev)
         return self.stepper.net_get_weights("target" if target else "online")
+
+    # ---- the CACLA learner's critic
+    def _need_cacla(self):
+        if not self.cacla:
+            raise RuntimeError("AgarVecEnv was created without continuous= and train= (the CACLA trainer)")
+
+    def set_critic_weights(self, weights):
+        """The critic's weights, as set_weights takes the acting network's.  The trainer's target
+        keeps what it holds (train= copied the critic as it was then)."""
+        self._need_cacla()
+        torch = self.torch
+        pairs = isinstance(weights, (list, tuple)) and all(
+            isinstance(p, (list, tuple)) and len(p) == 2 and isinstance(p[0], torch.Tensor) and p[0].is_cuda
+            for p in weights)
+        if pairs:
+            ws = [(W.to(torch.float32).contiguous(), b.to(device=self.dev, dtype=torch.float32).contiguous())
+                  for W, b in weights]
+        else:
+            ws = _net.weights_from_torch(weights)
+        if self._mem_sync:
+            torch.cuda.synchronize(self.dev)
+        self.stepper.critic_set_weights(ws)
+        if self._mem_sync:
+            self.stepper.sync()  # (ws is freed when this returns)
+
+    def get_critic_weights(self, target=False):
+        """The critic's (target=True: its target's) weights as [(W [in, out], b [out])] float32 numpy arrays."""
+        self._need_cacla()
+        if self._mem_sync:
+            self.torch.cuda.synchronize(self.dev)
+        return self.stepper.critic_get_weights("target" if target else "online")
+
+    def critic_value(self, states):
+        """V(s) of states [rows, n_in] (a device tensor or an array) -> [rows] float64 device tensor."""
+        self._need_cacla()
+        torch = self.torch
+        x = torch.as_tensor(states, device=self.dev)
+        if x.dtype not in (torch.float64, torch.float32):
+            x = x.to(torch.float64)
+        x = x.contiguous()
+        out = torch.empty(x.shape[0], dtype=torch.float64, device=self.dev)
+        if self._mem_sync:
+            torch.cuda.synchronize(self.dev)
+        self.stepper.critic_forward(x, out)
+        if self._mem_sync:
+            self.stepper.sync()
+        return out
+
+    def cacla_var(self):
+        """CACLA-Var's running variance of the TD error (a host round trip)."""
+        self._need_cacla()
+        return self.stepper.actrain_var()
 
     def set_weights(self, weights):
         """The trainer's weight push: a list of (W [in, out], b [out]) float32 per layer as device

@@ -282,3 +282,51 @@ def train_params(parameters=None):
     return {"batch": int(g("MEMORY_BATCH_LEN", 32)), "min_size": int(g("NUM_EXPS_BEFORE_TRAIN", 32)),
             "target_steps": int(g("TARGET_NETWORK_STEPS", 1500)), "lr": float(g("ALPHA", 0.001)), "beta1": 0.9,
             "beta2": 0.999, "epsilon": 1e-7, "discount": float(g("DISCOUNT", 0.9))}
+
+
+def critic_spec(parameters=None, n_in=None):
+    """NetSpec of the CACLA learner's critic V(s) (actorCritic.py ValueNetwork): CACLA_CRITIC_LAYERS
+    hidden layers with ACTIVATION_FUNC_HIDDEN and one linear output.  n_in as in mlp_spec."""
+    g = lambda n, d: _get(parameters, n, d)
+    hidden = g("ACTIVATION_FUNC_HIDDEN", "relu")
+    if hidden not in ("relu", "linear"):
+        raise ValueError("critic_spec: hidden activation %r is not supported by the device network (relu, linear)"
+                         % (hidden,))
+    units = tuple(int(v) for v in g("CACLA_CRITIC_LAYERS", (100, 100)) if int(v) > 0)
+    if len(units) + 1 > _abi.NET_MAX_LAYERS:
+        raise ValueError("critic_spec: %d hidden layers, at most %d" % (len(units), _abi.NET_MAX_LAYERS - 1))
+    if any(v > _abi.NET_MAX_UNITS for v in units):
+        raise ValueError("critic_spec: a layer of %d units, at most %d" % (max(units), _abi.NET_MAX_UNITS))
+    if n_in is not None and not 1 <= int(n_in) <= _abi.NET_MAX_IN:
+        raise ValueError("critic_spec: %d inputs, at most %d" % (n_in, _abi.NET_MAX_IN))
+    return NetSpec(None if n_in is None else int(n_in), units + (1,), hidden, "linear")
+
+
+def actrain_params(parameters=None):
+    """The device's CACLA trainer's settings from the reference's parameters: what
+    actorCritic.py does for ALGORITHM == "CACLA" by default, CACLA-Var included (var_epochs is the
+    device's cap on a row's actor epochs, 8, when CACLA_VAR_ENABLED; 0: plain CACLA).  Everything
+    else the reference can train an actor-critic learner with is refused here, by the name of the
+    setting."""
+    g = lambda n, d: _get(parameters, n, d)
+    if g("ALGORITHM", "CACLA") != "CACLA":
+        raise ValueError("actrain: ALGORITHM = %r: the device's actor-critic trainer is CACLA" % (g("ALGORITHM", "CACLA"),))
+    for name in ("OPTIMIZER", "OPTIMIZER_POLICY"):
+        if g(name, "Adam") != "Adam":
+            raise ValueError("actrain: %s = %r: the device trainer is Adam" % (name, g(name, "Adam")))
+    for name in ("OCACLA_ENABLED", "CACLA_UPDATE_ON_NEGATIVE_TD", "CACLA_CRITIC_WEIGHT_DECAY", "CACLA_OFF_POLICY_CORR",
+                 "ACTOR_IS", "AC_ACTOR_TDE", "AC_DELAY_ACTOR_TRAINING", "AC_ACTOR_TRAINING_START", "AMSGRAD",
+                 "END_DISCOUNT", "DROPOUT", "GRADIENT_CLIP", "GRADIENT_CLIP_NORM", "USE_ACTION_AS_INPUT", "CNN_REPR",
+                 "BATCHNORM"):
+        if g(name, 0):
+            raise ValueError("actrain: %s = %r is not supported by the device trainer" % (name, g(name, 0)))
+    if g("NEURON_TYPE", "MLP") != "MLP":
+        raise ValueError("actrain: NEURON_TYPE = %r: the device trainer takes no LSTM" % (g("NEURON_TYPE", "MLP"),))
+    if g("TD", 0) != 0:
+        raise ValueError("actrain: TD = %r: only one-step targets (TD = 0)" % (g("TD", 0),))
+    return {"batch": int(g("MEMORY_BATCH_LEN", 32)), "min_size": int(g("NUM_EXPS_BEFORE_TRAIN", 32)),
+            "target_steps": int(g("TARGET_NETWORK_STEPS", 1500)),
+            "var_epochs": _abi.ACTRAIN_MAX_EPOCHS if g("CACLA_VAR_ENABLED", True) else 0,
+            "critic_lr": float(g("CACLA_CRITIC_ALPHA", 0.000075)), "actor_lr": float(g("CACLA_ACTOR_ALPHA", 0.0005)),
+            "beta1": 0.9, "beta2": 0.999, "epsilon": 1e-7, "discount": float(g("DISCOUNT", 0.9)),
+            "var_start": float(g("CACLA_VAR_START", 1)), "var_beta": float(g("CACLA_VAR_BETA", 0.001))}

@@ -754,6 +754,80 @@ int aigar_train_sync_target(aigar_handle *h);
 int aigar_train_reset(aigar_handle *h);
 int aigar_net_get_weights(aigar_handle *h, int which, int layer, float *W, float *b, int on_device);
 int aigar_net_pad_check(aigar_handle *h, int which, int64_t *count);
+/* The CACLA learner's critic and trainer on the device (actorCritic.py ActorCritic.learn for
+ * ALGORITHM == "CACLA": train_critic 1032-1065, train_actor_batch 791-858, the critic's hard
+ * target copy 745-746; tests/cacla_model.py is the specification in plain Python).
+ *
+ * The critic V(s) is a second network of the handle.  aigar_critic_config: a dense MLP under
+ * aigar_net_config's limits whose last layer is ONE unit with out_act AIGAR_ACT_LINEAR and
+ * whose n_in is the acting network's; it needs a dense acting network without a conv part.
+ * The parameters are checked before the handle, each refusal with its own message.  NULL turns
+ * it off and frees it; aigar_net_config* drops it.  aigar_critic_set_weights: as
+ * aigar_net_set_weights.  aigar_critic_forward: V(s) of rows >= 1 rows of the DEVICE buffer
+ * x [rows][n_in] into the DEVICE buffer out [rows] float64, stream-ordered, the arithmetic of
+ * aigar_net_forward.
+ *
+ * One training step on B drawn transitions (s, a[4], rew, s2, done, w); forward passes, the
+ * backward pass and Adam are aigar_train_step's, in the same orders and roundings:
+ *   v = forward(s, critic) with the activations kept; v2 = forward(s2, critic's target);
+ *   t = rew if done, else rew + discount * v2 (float64: one multiply, one add); td = t - v;
+ *   with a prioritized memory |td| + 1e-4 becomes the drawn slot's priority;
+ *   critic: delta_L[r][0] = float32(((2 w_r) (-td_r)) / (1 B)), backward, Adam with critic_lr
+ *   and the critic's own step counter t_c;
+ *   selection, on the td above, float64, over ascending r, count[r] = the actor epochs of row r:
+ *     var_epochs == 0: count[r] = 1 if td_r > 0, else 0;
+ *     var_epochs = E >= 1: for EVERY row var = (1 - var_beta) var + var_beta (td_r td_r); then
+ *     count[r] = 0 if td_r <= 0, else c = ceil(td_r / sqrt(var)) if 1 <= c <= E, else E (the
+ *     row is counted as cut; a c that is not finite or below 1 is cut too).  The reference's
+ *     epochs are unbounded: the cap E <= AIGAR_ACTRAIN_MAX_EPOCHS is this project's.  var
+ *     persists across steps and starts at var_start;
+ *   actor epochs e = 0 .. max_r count[r] - 1, rows with count[r] > e taking part, n_e of them:
+ *     mu = the sigmoid head of forward(s, actor) with the weights as they are NOW;
+ *     delta_L[r][j] = float32(((2 (mu_rj - a_rj)) / (n_out n_e)) (mu_rj (1 - mu_rj))) for the
+ *     rows taking part, +0.0f for the others; backward; Adam with actor_lr and the actor's own
+ *     counter t_a, which advances once an epoch.  No importance weights on the actor;
+ *   t_c += 1; after a step with t_c % target_steps == 0 (target_steps > 0) the critic's target
+ *   <- the critic.  CACLA keeps no actor target.
+ * A step is skipped -- no weight, counter, priority or var changes -- while the memory holds
+ * fewer than max(batch, min_size) transitions, and, with AIGAR_WARN_TRAIN_NONFINITE, when a td
+ * is not finite.  An epoch whose delta_L has a non-finite entry is skipped with the same bit,
+ * and so are the step's later epochs; each of them is counted.
+ *
+ * aigar_actrain_config: the parameters are checked before the handle, each refusal with its
+ * own message (batch 1..256, min_size >= 0, target_steps >= 0, var_epochs 0..8, both lr > 0,
+ * betas in [0, 1), epsilon > 0, discount in [0, 1], var_start > 0, var_beta in [0, 1)).  It
+ * needs an acting network with a sigmoid head, 1..4 outputs and no conv part, a critic, a
+ * replay memory whose state length is n_in, and no tiled handle.  It allocates the critic's
+ * target as a copy of the critic as it is NOW, zeroed Adam state for both networks, staging
+ * rows and activation buffers.  NULL turns it off; aigar_net_config*, aigar_critic_config and
+ * aigar_exp_config drop it.  It and aigar_train_config exclude each other by their heads.
+ * Training is in place on the acting network's packed weights.
+ * aigar_actrain_step: as aigar_train_step.  aigar_actrain_info: {critic steps applied, steps
+ * skipped, steps since the target copy, actor epochs applied (t_a), rows selected in the last
+ * step, epochs of the last step, rows cut to var_epochs (total), actor epochs skipped (total)};
+ * a synchronising read.  aigar_actrain_td: stream-ordered copies of the last drawn step's td
+ * [batch], indices [batch] and count [batch] into DEVICE buffers (each may be NULL).
+ * aigar_actrain_var: var into a host double, synchronising.  aigar_actrain_sync_target: the
+ * critic's target <- the critic now.  aigar_actrain_reset: both networks' m and v, t_c and t_a
+ * to zero, var to var_start.
+ * aigar_net_get_weights / aigar_net_pad_check: which 4 the critic (needs only a critic), 5 its
+ * target, 6 / 7 its Adam m / v; under an actrain configuration 2 / 3 are the actor's m / v and
+ * 1 is refused (CACLA keeps no actor target). */
+#define AIGAR_ACTRAIN_MAX_EPOCHS 8
+typedef struct aigar_actrain_params {
+  int32_t batch, min_size, target_steps, var_epochs;   /* 1..256, >=0, >=0, 0..8 */
+  double critic_lr, actor_lr, beta1, beta2, epsilon, discount, var_start, var_beta;
+} aigar_actrain_params;                                 /* 80 bytes */
+int aigar_critic_config(aigar_handle *h, const aigar_net_params *p);
+int aigar_critic_set_weights(aigar_handle *h, int layer, const float *W, const float *b, int on_device);
+int aigar_critic_forward(aigar_handle *h, const void *x, int x_dtype, int rows, double *out);
+int aigar_actrain_config(aigar_handle *h, const aigar_actrain_params *p);
+int aigar_actrain_step(aigar_handle *h, int n_steps, const double *u);
+int aigar_actrain_info(aigar_handle *h, int64_t info[8]);
+int aigar_actrain_td(aigar_handle *h, double *td, int64_t *idx, int32_t *count);
+int aigar_actrain_var(aigar_handle *h, double *var);
+int aigar_actrain_sync_target(aigar_handle *h);
+int aigar_actrain_reset(aigar_handle *h);
 /* The sticky quirk bits of one arena since its last reset (a host round trip): 1 a virus
  * made this tick ate, 2 a dead virus was met, 4 a tile observed past its held pellets,
  * 8 AIGAR_WARN_Q_NONFINITE, 16 AIGAR_WARN_NOISE_NONFINITE, 32 AIGAR_WARN_NOISE_EXHAUSTED,
