@@ -123,6 +123,13 @@ class ActrainParams(C.Structure):
                 ("epsilon", C.c_double), ("discount", C.c_double), ("var_start", C.c_double), ("var_beta", C.c_double)]
 
 
+class DpgParams(C.Structure):
+    """aigar_dpg_params (include/aigar.h): the DPG trainer (actorCritic.py:751-789, 986-1029)."""
+    _fields_ = [("batch", C.c_int32), ("min_size", C.c_int32), ("target_steps", C.c_int32), ("reserved", C.c_int32),
+                ("critic_lr", C.c_double), ("actor_lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("epsilon", C.c_double), ("discount", C.c_double), ("tau", C.c_double), ("q_increase", C.c_double)]
+
+
 CONV_MAX_LAYERS, CONV_MAX_SIDE, CONV_MAX_CHANNELS, CONV_MAX_KERNEL, CONV_MAX_FILTERS = 3, 128, 8, 8, 64
 
 

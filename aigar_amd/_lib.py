@@ -124,6 +124,13 @@ def load(build_if_missing=False):
         "aigar_actrain_var": [vp, C.POINTER(C.c_double)],
         "aigar_actrain_sync_target": [vp],
         "aigar_actrain_reset": [vp],
+        "aigar_qcritic_config": [vp, C.POINTER(_abi.NetParams)],
+        "aigar_dpg_config": [vp, C.POINTER(_abi.DpgParams)],
+        "aigar_dpg_step": [vp, i32, vp],
+        "aigar_dpg_info": [vp, C.POINTER(C.c_int64)],
+        "aigar_dpg_td": [vp, vp, vp],
+        "aigar_dpg_sync_target": [vp],
+        "aigar_dpg_reset": [vp],
         "aigar_net_get_weights": [vp, i32, i32, vp, vp, i32],
         "aigar_net_pad_check": [vp, i32, C.POINTER(C.c_int64)],
         "aigar_exp_extra_get": [vp, vp, i32, vp, vp],
@@ -221,6 +228,7 @@ class Stepper:
         self.trn = None  # the batch while a training is configured
         self.crit = None  # (n_in, units) while a critic is configured
         self.act = None  # the batch while a CACLA training is configured
+        self.dpg = None  # the batch while a DPG training is configured
 
     def _chk(self, r):
         if r < 0:
@@ -438,7 +446,7 @@ class Stepper:
         is set every env_step appends the NN players' transitions inside its graph.  extra:
         the ring also keeps the tuple's fifth field (exp_extra_get / exp_extra_set).
         exp_config(None) frees it."""
-        self.trn = self.act = None  # (the library drops the train configurations with the memory)
+        self.trn = self.act = self.dpg = None  # (the library drops the train configurations with the memory)
         if not capacity:
             self._chk(self.L.aigar_exp_config(self.h, None))
             self.exp = None
@@ -655,7 +663,7 @@ class Stepper:
         conv layers in front (aigar_net_config_cnn): the states are then images [side, side,
         channels] and n_in is n_flat.  The weights are zero until net_set_weights.
         net_config(None) turns it off."""
-        self.trn = self.crit = self.act = None  # (the library drops the train configurations and the critic with the network)
+        self.trn = self.crit = self.act = self.dpg = None  # (the library drops the train configurations and the critic with the network)
         if spec is None:
             self._chk(self.L.aigar_net_config(self.h, None))
             self.net = self.conv = None
@@ -820,13 +828,14 @@ class Stepper:
         self._chk(self.L.aigar_train_reset(self.h))
 
     # ---- the CACLA learner's critic and trainer (include/aigar.h: aigar_critic*, aigar_actrain*)
-    def critic_config(self, spec, x_dtype="float64"):
+    def critic_config(self, spec, x_dtype="float64", _entry="aigar_critic_config"):
         """The handle's critic V(s): spec is (n_in, units, hidden, "linear") with units[-1] == 1 and
         the acting network's n_in (aigar_critic_config).  The weights are zero until
         critic_set_weights.  critic_config(None) turns it off."""
-        self.act = None  # (the library drops the CACLA train configuration with the critic)
+        config = getattr(self.L, _entry)
+        self.act = self.dpg = None  # (the library drops the train configurations with the critic)
         if spec is None:
-            self._chk(self.L.aigar_critic_config(self.h, None))
+            self._chk(config(self.h, None))
             self.crit = None
             return
         n_in, units, hidden, out = spec
@@ -838,8 +847,15 @@ class Stepper:
         prm = _abi.NetParams(len(units), int(n_in), 0 if d == "float64" else 1, code(hidden), code(out), 0)
         for i, v in enumerate(units):
             prm.units[i] = v
-        self._chk(self.L.aigar_critic_config(self.h, C.byref(prm)))
+        self._chk(config(self.h, C.byref(prm)))
         self.crit = (int(n_in), tuple(units))
+
+    def qcritic_config(self, spec, x_dtype="float64"):
+        """The handle's critic Q(s, a) (aigar_qcritic_config): as critic_config, but n_in is the
+        acting network's n_in + n_out -- a row is the state, then the action -- and the acting
+        network has a sigmoid head.  critic_set_weights, critic_get_weights and critic_forward
+        serve it.  qcritic_config(None) turns it off."""
+        self.critic_config(spec, x_dtype, _entry="aigar_qcritic_config")
 
     def _need_crit(self, what):
         if getattr(self, "crit", None) is None:
@@ -957,6 +973,62 @@ class Stepper:
     def actrain_reset(self):
         self._need_act("actrain_reset")
         self._chk(self.L.aigar_actrain_reset(self.h))
+
+    # ---- the DPG trainer (include/aigar.h: aigar_dpg*)
+    def dpg_config(self, batch=32, min_size=0, target_steps=0, critic_lr=5e-4, actor_lr=1e-4, beta1=0.9, beta2=0.999,
+                   epsilon=1e-7, discount=0.9, tau=0.001, q_increase=2.0):
+        """The DPG trainer of the handle's actor and Q(s, a) critic on its replay memory
+        (aigar_dpg_config).  Needs net_config (dense, sigmoid head), qcritic_config and
+        exp_config.  tau > 0: soft target updates; tau == 0: a hard copy every target_steps
+        applied steps.  dpg_config(None) turns it off."""
+        if batch is None:
+            self._chk(self.L.aigar_dpg_config(self.h, None))
+            self.dpg = None
+            return
+        prm = _abi.DpgParams(int(batch), int(min_size), int(target_steps), 0, float(critic_lr), float(actor_lr),
+                             float(beta1), float(beta2), float(epsilon), float(discount), float(tau), float(q_increase))
+        self._chk(self.L.aigar_dpg_config(self.h, C.byref(prm)))
+        self.dpg = int(batch)
+
+    def _need_dpg(self, what):
+        if getattr(self, "dpg", None) is None:
+            raise RuntimeError("aigar: %s: no DPG training is configured (dpg_config)" % what)
+        return self.dpg
+
+    def dpg_step(self, n=1, u=None):
+        """n DPG training steps, one graph replay each (aigar_dpg_step); u as train_step's."""
+        batch = self._need_dpg("dpg_step")
+        up = None
+        if u is not None:
+            self._check_dev(u, (int(n), batch), ("float64",), "dpg_step")
+            up = C.c_void_p(u.data_ptr())
+        self._chk(self.L.aigar_dpg_step(self.h, int(n), up))
+
+    def dpg_info(self):
+        """The DPG trainer's counters (aigar_dpg_info: the one synchronising read)."""
+        self._need_dpg("dpg_info")
+        v = (C.c_int64 * 8)()
+        self._chk(self.L.aigar_dpg_info(self.h, v))
+        return {"steps": v[0], "skipped": v[1], "since_target": v[2], "actor_steps": v[3], "actor_skipped": v[4]}
+
+    def dpg_td(self, td=None, idx=None):
+        """The last drawn step's TD errors and memory indices into the device tensors td [batch]
+        float64 and idx [batch] int64."""
+        batch = self._need_dpg("dpg_td")
+        ptrs = []
+        for t, dt in ((td, "float64"), (idx, "int64")):
+            if t is not None:
+                self._check_dev(t, (batch,), (dt,), "dpg_td")
+            ptrs.append(None if t is None else C.c_void_p(t.data_ptr()))
+        self._chk(self.L.aigar_dpg_td(self.h, *ptrs))
+
+    def dpg_sync_target(self):
+        self._need_dpg("dpg_sync_target")
+        self._chk(self.L.aigar_dpg_sync_target(self.h))
+
+    def dpg_reset(self):
+        self._need_dpg("dpg_reset")
+        self._chk(self.L.aigar_dpg_reset(self.h))
 
     def net_forward(self, x, out):
         """The network alone on device tensors (aigar_net_forward): x [rows, n_in] float64 /

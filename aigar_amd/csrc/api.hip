@@ -59,6 +59,7 @@ using namespace aigar;
 #include "conv.inc"
 #include "train.inc"
 #include "actrain.inc"
+#include "dpg.inc"
 
 static thread_local std::string g_err;
 static int fail(const char *fmt, ...) {
@@ -323,7 +324,13 @@ struct aigar_handle {
   ACTrain act;
   DevBlock act_mem;
   KeyedSlot<TrainKey> actrain;
-  GraphSlot *const slots[9] = {&step, &run, &run_u, &env, &tb, &te, &tr, &train, &actrain};
+  // aigar_qcritic_config: the critic is Q(s, a), its rows are [state, action]
+  bool crit_q = false;
+  // aigar_dpg_config: the DPG trainer (dpg.inc; batch 0: off) and its step's graph
+  DPGTrain dpg;
+  DevBlock dpg_mem;
+  KeyedSlot<TrainKey> dpgs;
+  GraphSlot *const slots[10] = {&step, &run, &run_u, &env, &tb, &te, &tr, &train, &actrain, &dpgs};
 };
 
 void GraphSlot::drop(aigar_handle *h) {
@@ -387,7 +394,7 @@ static void free_all(aigar_handle *h) {
   h->pix_bytes = 0;
   if (h->d_pix_hist) (void)hipFree(h->d_pix_hist);
   h->d_pix_hist = nullptr;
-  for (DevBlock *m : {&h->exp_mem, &h->dec_mem, &h->noi_mem, &h->net_mem, &h->trn_mem, &h->crit_mem, &h->act_mem}) m->release();
+  for (DevBlock *m : {&h->exp_mem, &h->dec_mem, &h->noi_mem, &h->net_mem, &h->trn_mem, &h->crit_mem, &h->act_mem, &h->dpg_mem}) m->release();
   if (h->d_exp_off) (void)hipFree(h->d_exp_off);
   h->d_exp_off = nullptr;
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1480,8 +1487,15 @@ static void actrain_free(aigar_handle *h) {
   h->act_mem.release();
   h->act = ACTrain{};
 }
+static void dpg_free(aigar_handle *h) {
+  h->dpgs.drop(h);
+  h->dpg_mem.release();
+  h->dpg = DPGTrain{};
+}
 static void critic_free(aigar_handle *h) {
   actrain_free(h);
+  dpg_free(h);
+  h->crit_q = false;
   h->crit_mem.release();
   h->crit = Net{};
   h->crit_stage = nullptr;
@@ -2094,6 +2108,7 @@ extern "C" int aigar_exp_config(aigar_handle *h, const aigar_exp_params *p) {
   if (begin_reconfig(h)) return -1;  // (no reader of the memory is pending either)
   train_free(h);
   actrain_free(h);
+  dpg_free(h);
   h->exp_mem.release();
   h->exp = Exp{};
   if (!on) return 0;
@@ -2522,28 +2537,39 @@ static int need_act(aigar_handle *h, const char *who) {
   return need(h, h && h->act.batch, who, "no CACLA training is configured (aigar_actrain_config)");
 }
 
-extern "C" int aigar_critic_config(aigar_handle *h, const aigar_net_params *p) {
+// aigar_critic_config (V(s): q false) and aigar_qcritic_config (Q(s, a): the rows are [state, action])
+static int critic_config(aigar_handle *h, const aigar_net_params *p, bool q) {
+  const char *who = q ? "qcritic_config" : "critic_config";
   if (p) {  // (before the handle: a bad set has its own message)
     if (p->n_layers < 1 || p->n_layers > kNetMaxLayers)
-      return fail("critic_config: n_layers = %d is outside 1..%d", p->n_layers, kNetMaxLayers);
-    if (p->n_in < 1 || p->n_in > kNetMaxIn) return fail("critic_config: n_in = %d is outside 1..%d", p->n_in, kNetMaxIn);
+      return fail("%s: n_layers = %d is outside 1..%d", who, p->n_layers, kNetMaxLayers);
+    if (p->n_in < 1 || p->n_in > kNetMaxIn) return fail("%s: n_in = %d is outside 1..%d", who, p->n_in, kNetMaxIn);
     for (int l = 0; l < p->n_layers; l++)
       if (p->units[l] < 1 || p->units[l] > kNetMaxUnits)
-        return fail("critic_config: layer %d has %d units, outside 1..%d", l, p->units[l], kNetMaxUnits);
-    if (p->x_dtype != 0 && p->x_dtype != 1) return fail("critic_config: x_dtype must be 0 (float64) or 1 (float32)");
+        return fail("%s: layer %d has %d units, outside 1..%d", who, l, p->units[l], kNetMaxUnits);
+    if (p->x_dtype != 0 && p->x_dtype != 1) return fail("%s: x_dtype must be 0 (float64) or 1 (float32)", who);
     if (p->hidden_act != AIGAR_ACT_RELU && p->hidden_act != AIGAR_ACT_LINEAR)
-      return fail("critic_config: hidden activation %d (%s) is not supported: relu or linear", p->hidden_act,
+      return fail("%s: hidden activation %d (%s) is not supported: relu or linear", who, p->hidden_act,
                   net_act_name(p->hidden_act));
     if (p->units[p->n_layers - 1] != 1 || p->out_act != AIGAR_ACT_LINEAR)
-      return fail("critic_config: the head has %d units with activation %d (%s), V(s) is one linear unit",
-                  p->units[p->n_layers - 1], p->out_act, net_act_name(p->out_act));
+      return fail("%s: the head has %d units with activation %d (%s), %s is one linear unit", who,
+                  p->units[p->n_layers - 1], p->out_act, net_act_name(p->out_act), q ? "Q(s, a)" : "V(s)");
   }
   if (!h) return fail("null handle");
   if (p) {
-    if (need_net(h, "critic_config")) return -1;
-    if (h->conv.n_conv) return fail("critic_config: the acting network has a conv part, the critic is a dense network");
-    if (p->n_in != h->net.in[0])
-      return fail("critic_config: n_in = %d differs from the acting network's %d", p->n_in, h->net.in[0]);
+    if (need_net(h, who)) return -1;
+    if (h->conv.n_conv) return fail("%s: the acting network has a conv part, the critic is a dense network", who);
+    if (!q && p->n_in != h->net.in[0])
+      return fail("%s: n_in = %d differs from the acting network's %d", who, p->n_in, h->net.in[0]);
+    if (q) {
+      const int n_act = h->net.out[h->net.n_layers - 1];
+      if (h->net.out_act != AIGAR_ACT_SIGMOID)
+        return fail("%s: the network's head is %s, the DPG actor needs a sigmoid head", who, net_act_name(h->net.out_act));
+      if (n_act > 4) return fail("%s: the actor has %d outputs, a stored action has at most 4", who, n_act);
+      if (p->n_in != h->net.in[0] + n_act)
+        return fail("%s: n_in = %d differs from the acting network's n_in + n_out = %d + %d", who, p->n_in, h->net.in[0],
+                    n_act);
+    }
   }
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipStreamSynchronize(h->stream));  // (no training step or forward pass is pending)
@@ -2568,12 +2594,15 @@ extern "C" int aigar_critic_config(aigar_handle *h, const aigar_net_params *p) {
   if (ok) ok = (h->crit_stage = (float *)h->crit_mem.alloc(stage * sizeof(float), true, h->stream)) != nullptr;
   if (!ok) {
     critic_free(h);
-    return fail("critic_config: out of device memory");
+    return fail("%s: out of device memory", who);
   }
   HIPCHK(hipGetLastError());
   h->crit = c;
+  h->crit_q = q;
   return 0;
 }
+extern "C" int aigar_critic_config(aigar_handle *h, const aigar_net_params *p) { return critic_config(h, p, false); }
+extern "C" int aigar_qcritic_config(aigar_handle *h, const aigar_net_params *p) { return critic_config(h, p, true); }
 
 extern "C" int aigar_critic_set_weights(aigar_handle *h, int layer, const float *W, const float *b, int on_device) {
   if (need_crit(h, "critic_set_weights")) return -1;
@@ -2612,6 +2641,44 @@ extern "C" int aigar_critic_forward(aigar_handle *h, const void *x, int x_dtype,
   return 0;
 }
 
+// One network's view of an actor-critic trainer (actrain.inc, dpg.inc): s, the settings and the
+// staged batch that the views share, and the network's own Adam state, buffers, counters and,
+// with `target`, a target that starts as a copy of the network as it is now.
+static Train train_view(aigar_handle *h, DevBlock &mem, bool &ok, const Train &s, const Net &c, double lr, bool target) {
+  auto get = [&](size_t bytes) -> void * {
+    if (!ok) return nullptr;
+    void *q = mem.alloc(bytes, true, h->stream);
+    ok = q != nullptr;
+    return q;
+  };
+  const size_t B = (size_t)s.batch;
+  Train v = s;
+  v.lr = lr;
+  for (int l = 0; l < c.n_layers; l++) {
+    const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
+    if (target) {
+      v.tw[l] = (float *)get(nw);
+      v.tb[l] = (float *)get(op * sizeof(float));
+    }
+    v.mw[l] = (float *)get(nw);
+    v.mb[l] = (float *)get(op * sizeof(float));
+    v.vw[l] = (float *)get(nw);
+    v.vb[l] = (float *)get(op * sizeof(float));
+    v.tile0[l + 1] = v.tile0[l] + (c.in[l] + 15) / 16 * (int)(op / 16);
+    if (ok && target) {
+      (void)hipMemcpyAsync(v.tw[l], c.w[l], nw, hipMemcpyDeviceToDevice, h->stream);
+      (void)hipMemcpyAsync(v.tb[l], c.b[l], op * sizeof(float), hipMemcpyDeviceToDevice, h->stream);
+    }
+  }
+  const size_t n_out = (size_t)c.out[c.n_layers - 1];
+  v.q = (double *)get(B * n_out * sizeof(double));
+  if (target) v.q2 = (double *)get(B * n_out * sizeof(double));
+  v.hsave = (float *)get((size_t)std::max(c.n_layers - 1, 1) * v.bpad * kNetMaxUnits * sizeof(float));
+  v.delta = (float *)get((size_t)c.n_layers * v.bpad * kNetMaxUnits * sizeof(float));
+  v.ctl = (TrainCtl *)get(sizeof(TrainCtl));
+  return v;
+}
+
 extern "C" int aigar_actrain_config(aigar_handle *h, const aigar_actrain_params *p) {
   if (p) {  // (before the handle: a bad set has its own message)
     const double inf = __builtin_inf();
@@ -2645,6 +2712,7 @@ extern "C" int aigar_actrain_config(aigar_handle *h, const aigar_actrain_params 
     if (h->net.out[h->net.n_layers - 1] > 4)
       return fail("actrain_config: the actor has %d outputs, a stored action has at most 4", h->net.out[h->net.n_layers - 1]);
     if (need_crit(h, "actrain_config")) return -1;
+    if (h->crit_q) return fail("actrain_config: the critic is Q(s, a) (aigar_qcritic_config), CACLA trains V(s)");
     if (need_exp(h, "actrain_config")) return -1;
     if (h->net.in[0] != h->exp.L)
       return fail("actrain_config: the network has %d inputs, the memory's states %d values", h->net.in[0], h->exp.L);
@@ -2686,35 +2754,8 @@ extern "C" int aigar_actrain_config(aigar_handle *h, const aigar_actrain_params 
   s.idx = (int64_t *)get(B * sizeof(int64_t));
   s.td = (double *)get(B * sizeof(double));
   s.prio = (double *)get(B * sizeof(double));
-  auto view = [&](const Net &c, double lr, bool target) {
-    Train v = s;
-    v.lr = lr;
-    for (int l = 0; l < c.n_layers; l++) {
-      const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
-      if (target) {
-        v.tw[l] = (float *)get(nw);
-        v.tb[l] = (float *)get(op * sizeof(float));
-      }
-      v.mw[l] = (float *)get(nw);
-      v.mb[l] = (float *)get(op * sizeof(float));
-      v.vw[l] = (float *)get(nw);
-      v.vb[l] = (float *)get(op * sizeof(float));
-      v.tile0[l + 1] = v.tile0[l] + (c.in[l] + 15) / 16 * (int)(op / 16);
-      if (ok && target) {
-        (void)hipMemcpyAsync(v.tw[l], c.w[l], nw, hipMemcpyDeviceToDevice, h->stream);
-        (void)hipMemcpyAsync(v.tb[l], c.b[l], op * sizeof(float), hipMemcpyDeviceToDevice, h->stream);
-      }
-    }
-    const size_t n_out = (size_t)c.out[c.n_layers - 1];
-    v.q = (double *)get(B * n_out * sizeof(double));
-    if (target) v.q2 = (double *)get(B * n_out * sizeof(double));
-    v.hsave = (float *)get((size_t)std::max(c.n_layers - 1, 1) * v.bpad * kNetMaxUnits * sizeof(float));
-    v.delta = (float *)get((size_t)c.n_layers * v.bpad * kNetMaxUnits * sizeof(float));
-    v.ctl = (TrainCtl *)get(sizeof(TrainCtl));
-    return v;
-  };
-  t.c = view(h->crit, p->critic_lr, true);
-  t.a = view(h->net, p->actor_lr, false);
+  t.c = train_view(h, h->act_mem, ok, s, h->crit, p->critic_lr, true);
+  t.a = train_view(h, h->act_mem, ok, s, h->net, p->actor_lr, false);
   t.count = (int32_t *)get(B * sizeof(int32_t));
   t.x = (ACtl *)get(sizeof(ACtl));
   if (!ok) {
@@ -2865,9 +2906,250 @@ extern "C" int aigar_actrain_reset(aigar_handle *h) {
   return 0;
 }
 
+// ------------------------------------------------------------ DPG: the Q(s, a) critic's trainer
+static_assert(sizeof(DPGTrain) + 2 * sizeof(Net) + sizeof(Dev) <= 4096, "k_dpg_tail's arguments");
+static int need_dpg(aigar_handle *h, const char *who) {
+  return need(h, h && h->dpg.batch, who, "no DPG training is configured (aigar_dpg_config)");
+}
+
+extern "C" int aigar_dpg_config(aigar_handle *h, const aigar_dpg_params *p) {
+  if (p) {  // (before the handle: a bad set has its own message)
+    const double inf = __builtin_inf();
+    if (p->batch < 1 || p->batch > kTrainMaxBatch)
+      return fail("dpg_config: batch = %d is outside 1..%d", p->batch, kTrainMaxBatch);
+    if (p->min_size < 0) return fail("dpg_config: min_size = %d is negative", p->min_size);
+    if (p->target_steps < 0) return fail("dpg_config: target_steps = %d is negative", p->target_steps);
+    if (p->reserved != 0) return fail("dpg_config: reserved = %d must be 0", p->reserved);
+    if (!(p->critic_lr > 0) || !(p->critic_lr < inf))
+      return fail("dpg_config: critic_lr = %g must be positive and finite", p->critic_lr);
+    if (!(p->actor_lr > 0) || !(p->actor_lr < inf))
+      return fail("dpg_config: actor_lr = %g must be positive and finite", p->actor_lr);
+    if (!(p->beta1 >= 0 && p->beta1 < 1)) return fail("dpg_config: beta1 = %g is outside [0, 1)", p->beta1);
+    if (!(p->beta2 >= 0 && p->beta2 < 1)) return fail("dpg_config: beta2 = %g is outside [0, 1)", p->beta2);
+    if (!(p->epsilon > 0) || !(p->epsilon < inf))
+      return fail("dpg_config: epsilon = %g must be positive and finite", p->epsilon);
+    if (!(p->discount >= 0 && p->discount <= 1)) return fail("dpg_config: discount = %g is outside [0, 1]", p->discount);
+    if (!(p->tau >= 0 && p->tau <= 1)) return fail("dpg_config: tau = %g is outside [0, 1]", p->tau);
+    if (!(fabs(p->q_increase) < inf)) return fail("dpg_config: q_increase = %g must be finite", p->q_increase);
+  }
+  if (!h) return fail("null handle");
+  if (p) {
+    if (h->d.tiled) return fail("dpg_config: a tiled handle has no training");
+    if (need_net(h, "dpg_config")) return -1;
+    if (h->conv.n_conv) return fail("dpg_config: a network with a conv part is not trained on the device");
+    if (need_crit(h, "dpg_config")) return -1;
+    if (!h->crit_q) return fail("dpg_config: the critic is V(s) (aigar_critic_config), DPG trains Q(s, a) (aigar_qcritic_config)");
+    if (need_exp(h, "dpg_config")) return -1;
+    if (h->net.in[0] != h->exp.L)
+      return fail("dpg_config: the network has %d inputs, the memory's states %d values", h->net.in[0], h->exp.L);
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  dpg_free(h);
+  if (!p) return 0;
+  const Exp &e = h->exp;
+  DPGTrain t;
+  t.batch = p->batch;
+  t.n_s = h->net.in[0];
+  t.n_act = h->net.out[h->net.n_layers - 1];
+  t.soft = p->tau > 0 ? 1 : 0;
+  t.tau = (float)p->tau;
+  t.keep = (float)(1.0 - p->tau);
+  t.q_increase = p->q_increase;
+  bool ok = true;
+  auto get = [&](size_t bytes) -> void * {
+    if (!ok) return nullptr;
+    void *q = h->dpg_mem.alloc(bytes, true, h->stream);
+    ok = q != nullptr;
+    return q;
+  };
+  const size_t B = (size_t)p->batch, row = (size_t)e.L * e.esz, xrow = (size_t)(t.n_s + t.n_act) * e.esz;
+  Train s;  // what the views share: the settings and the staged batch
+  s.batch = p->batch;
+  s.bpad = (p->batch + kNetRows - 1) / kNetRows * kNetRows;
+  s.min_size = p->min_size;
+  s.target_steps = p->target_steps;
+  s.beta1 = p->beta1;
+  s.beta2 = p->beta2;
+  s.epsilon = p->epsilon;
+  s.discount = p->discount;
+  s.s = (char *)get(B * row);
+  s.s2 = (char *)get(B * row);
+  s.a = (double *)get(B * 4 * sizeof(double));
+  s.r = (double *)get(B * sizeof(double));
+  s.w = (double *)get(B * sizeof(double));
+  s.u = (double *)get(B * sizeof(double));
+  s.done = (uint8_t *)get(B);
+  s.idx = (int64_t *)get(B * sizeof(int64_t));
+  s.td = (double *)get(B * sizeof(double));
+  s.prio = (double *)get(B * sizeof(double));
+  t.c = train_view(h, h->dpg_mem, ok, s, h->crit, p->critic_lr, true);
+  t.a = train_view(h, h->dpg_mem, ok, s, h->net, p->actor_lr, true);
+  t.c.s = (char *)get(B * xrow);  // (the critic's first layer reads the packed rows)
+  t.c.s2 = (char *)get(B * xrow);
+  t.xm = (char *)get(B * xrow);
+  t.xt = (char *)get(B * xrow);
+  t.mut = (double *)get(B * t.n_act * sizeof(double));
+  t.qm = (double *)get(B * sizeof(double));
+  t.qt = (double *)get(B * sizeof(double));
+  t.ca = t.c;
+  t.ca.ctl = (TrainCtl *)get(sizeof(TrainCtl));
+  if (!ok) {
+    h->dpg_mem.release();
+    return fail("dpg_config: out of device memory");
+  }
+  HIPCHK(hipGetLastError());
+  h->dpg = t;  // (the blocks are zeroed: every counter starts at 0)
+  return 0;
+}
+
+// One DPG training step's launches on stream s (dpg.inc).
+static void launch_dpg_step(aigar_handle *h, hipStream_t s, int has_u) {
+  const DPGTrain &t = h->dpg;
+  const Train &c = t.c, &a = t.a, &ca = t.ca;
+  const Exp &e = h->exp;
+  Net cr = h->crit, ct = h->crit, ac = h->net, at = h->net;
+  cr.x_dtype = ct.x_dtype = ac.x_dtype = at.x_dtype = e.dtype;
+  for (int l = 0; l < ct.n_layers; l++) {
+    ct.w[l] = c.tw[l];
+    ct.b[l] = c.tb[l];
+  }
+  for (int l = 0; l < at.n_layers; l++) {
+    at.w[l] = a.tw[l];
+    at.b[l] = a.tb[l];
+  }
+  const int B = t.batch;
+  const dim3 rows16((unsigned)(c.bpad / kNetRows)), net_block(64 * kNetWaves);
+  auto save = [&](const Net &n, const char *x, double *y, float *hsave) {
+    if (e.dtype == 0) hipLaunchKernelGGL(k_net_save<double>, rows16, net_block, 0, s, n, (const double *)x, B, y, hsave);
+    else hipLaunchKernelGGL(k_net_save<float>, rows16, net_block, 0, s, n, (const float *)x, B, y, hsave);
+  };
+  auto pack = [&](const char *s0, const double *a0, int st0, char *o0, const char *s1, const double *a1, int st1, char *o1) {
+    if (e.dtype == 0)
+      hipLaunchKernelGGL(k_sa_pack<double>, dim3(2 * B), dim3(64), 0, s, B, t.n_s, t.n_act, (const double *)s0, a0, st0,
+                         (double *)o0, (const double *)s1, a1, st1, (double *)o1);
+    else
+      hipLaunchKernelGGL(k_sa_pack<float>, dim3(2 * B), dim3(64), 0, s, B, t.n_s, t.n_act, (const float *)s0, a0, st0,
+                         (float *)o0, (const float *)s1, a1, st1, (float *)o1);
+  };
+  auto update = [&](const Net &n, const Train &v) {
+    if (n.n_layers > 1) hipLaunchKernelGGL(k_net_bwd, rows16, net_block, 0, s, n, v);
+    if (e.dtype == 0) hipLaunchKernelGGL(k_net_grad_adam<double>, dim3(v.tile0[n.n_layers]), dim3(64), 0, s, n, v);
+    else hipLaunchKernelGGL(k_net_grad_adam<float>, dim3(v.tile0[n.n_layers]), dim3(64), 0, s, n, v);
+  };
+  hipLaunchKernelGGL(k_exp_draw, dim3((B + 255) / 256), dim3(256), 0, s, e, B, has_u ? a.u : (const double *)nullptr, a.w,
+                     a.idx);
+  if (e.dtype == 0) hipLaunchKernelGGL(k_exp_fetch<uint64_t>, dim3(B), dim3(256), 0, s, e, a.idx, a.s, a.a, a.r, a.s2, a.done, 0);
+  else hipLaunchKernelGGL(k_exp_fetch<uint32_t>, dim3(B), dim3(256), 0, s, e, a.idx, a.s, a.a, a.r, a.s2, a.done, 0);
+  // the critic half
+  launch_net(s, at, a.s2, B, a.q2, nullptr, nullptr);
+  pack(a.s, a.a, 4, c.s, a.s2, a.q2, t.n_act, c.s2);
+  save(cr, c.s, c.q, c.hsave);
+  launch_net(s, ct, c.s2, B, c.q2, nullptr, nullptr);
+  hipLaunchKernelGGL(k_td_q, dim3(1), dim3(kTrainMaxBatch), 0, s, c, e, h->d, cr.n_layers);
+  update(cr, c);
+  if (e.prio) hipLaunchKernelGGL(k_exp_update, dim3(1), dim3(kExpPlanThreads), 0, s, e, c.idx, c.prio, B);
+  // the actor half
+  save(ac, a.s, a.q, a.hsave);
+  launch_net(s, at, a.s, B, t.mut, nullptr, nullptr);
+  pack(a.s, a.q, t.n_act, t.xm, a.s, t.mut, t.n_act, t.xt);
+  save(cr, t.xm, t.qm, ca.hsave);  // (the critic's update is done: its buffers serve the actor pass)
+  launch_net(s, ct, t.xt, B, t.qt, nullptr, nullptr);
+  hipLaunchKernelGGL(k_dpg_delta, dim3(1), dim3(kTrainMaxBatch), 0, s, t, h->d, cr.n_layers);
+  if (cr.n_layers > 1) hipLaunchKernelGGL(k_net_bwd, rows16, net_block, 0, s, cr, ca);
+  hipLaunchKernelGGL(k_net_bwd_in, dim3(1), dim3(64 * (c.bpad / kNetRows)), 0, s, cr, t, h->d, ac.n_layers);
+  update(ac, a);
+  hipLaunchKernelGGL(k_dpg_tail, dim3(64), dim3(256), 0, s, cr, ac, t);
+}
+
+extern "C" int aigar_dpg_step(aigar_handle *h, int n_steps, const double *u) {
+  if (need_dpg(h, "dpg_step")) return -1;
+  if (n_steps < 1) return fail("dpg_step: n_steps = %d is below 1", n_steps);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  TrainKey k;
+  key_clear(k);
+  k.has_u = u ? 1 : 0;
+  const bool graph = h->use_graph;
+  if (graph && !h->dpgs.ensure(h, k, [&](hipStream_t cs) { launch_dpg_step(h, cs, k.has_u); }))
+    return fail("dpg_step: graph capture failed");
+  Mark m(h, "dpg_step");
+  const size_t B = (size_t)h->dpg.batch;
+  for (int i = 0; i < n_steps; i++) {
+    if (u) HIPCHK(hipMemcpyAsync(h->dpg.a.u, u + (size_t)i * B, B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (graph) HIPCHK(h->dpgs.launch(h));
+    else launch_dpg_step(h, h->stream, k.has_u);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int aigar_dpg_info(aigar_handle *h, int64_t info[8]) {
+  if (need_dpg(h, "dpg_info")) return -1;
+  if (!info) return fail("dpg_info: null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  TrainCtl c, a;
+  HIPCHK(hipMemcpyAsync(&c, h->dpg.c.ctl, sizeof c, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(&a, h->dpg.a.ctl, sizeof a, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  info[0] = c.t;
+  info[1] = c.skipped;
+  info[2] = c.since;
+  info[3] = a.t;
+  info[4] = a.skipped;
+  info[5] = info[6] = info[7] = 0;
+  return 0;
+}
+
+extern "C" int aigar_dpg_td(aigar_handle *h, double *td, int64_t *idx) {
+  if (need_dpg(h, "dpg_td")) return -1;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const size_t B = (size_t)h->dpg.batch;
+  if (td) HIPCHK(hipMemcpyAsync(td, h->dpg.c.td, B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  if (idx) HIPCHK(hipMemcpyAsync(idx, h->dpg.c.idx, B * sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream));
+  return 0;
+}
+
+extern "C" int aigar_dpg_sync_target(aigar_handle *h) {
+  if (need_dpg(h, "dpg_sync_target")) return -1;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  for (int k = 0; k < 2; k++) {
+    const Net &c = k ? h->net : h->crit;
+    const Train &t = k ? h->dpg.a : h->dpg.c;
+    for (int l = 0; l < c.n_layers; l++) {
+      const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
+      HIPCHK(hipMemcpyAsync(t.tw[l], c.w[l], nw, hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(t.tb[l], c.b[l], op * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    }
+  }
+  hipLaunchKernelGGL(k_train_clear, dim3(1), dim3(1), 0, h->stream, h->dpg.c.ctl, 1);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int aigar_dpg_reset(aigar_handle *h) {
+  if (need_dpg(h, "dpg_reset")) return -1;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const DPGTrain &t = h->dpg;
+  for (int k = 0; k < 2; k++) {
+    const Net &c = k ? h->net : h->crit;
+    const Train &v = k ? t.a : t.c;
+    for (int l = 0; l < c.n_layers; l++) {
+      const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
+      HIPCHK(hipMemsetAsync(v.mw[l], 0, nw, h->stream));
+      HIPCHK(hipMemsetAsync(v.vw[l], 0, nw, h->stream));
+      HIPCHK(hipMemsetAsync(v.mb[l], 0, op * sizeof(float), h->stream));
+      HIPCHK(hipMemsetAsync(v.vb[l], 0, op * sizeof(float), h->stream));
+    }
+  }
+  hipLaunchKernelGGL(k_dpg_clear, dim3(1), dim3(1), 0, h->stream, t.c.ctl, t.a.ctl);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // which: 0 online, 1 target, 2 Adam's m, 3 Adam's v (the last three need a train configuration)
 // 4 the critic (needs only a critic), 5 its target, 6 / 7 its Adam state (an actrain configuration,
-// under which 2 / 3 are the actor's Adam state and 1 is refused).  *np: the network whose shape it has.
+// under which 2 / 3 are the actor's Adam state and 1 is refused; or a DPG configuration, under
+// which 1 is the actor's target too).  *np: the network whose shape it has.
 static int net_which(aigar_handle *h, const char *who, int which, int layer, const Net **np, const float **wp,
                      const float **bp) {
   if (need_net(h, who)) return -1;
@@ -2876,10 +3158,11 @@ static int net_which(aigar_handle *h, const char *who, int which, int layer, con
   if (crit && !h->crit.n_layers) return fail("%s: no critic is configured (aigar_critic_config)", who);
   const Net &c = crit ? h->crit : h->net;
   if (layer < 0 || layer >= c.n_layers) return fail("%s: layer %d is outside 0..%d", who, layer, c.n_layers - 1);
+  const bool dpg = h->dpg.batch != 0;
   if (which == 1 && h->act.batch) return fail("%s: which = 1: CACLA keeps no actor target", who);
-  if (which > 4 && need_act(h, who)) return -1;
-  if (which >= 1 && which <= 3 && !h->act.batch && need_trn(h, who)) return -1;
-  const Train &t = crit ? h->act.c : h->act.batch ? h->act.a : h->trn;
+  if (which > 4 && !dpg && need_act(h, who)) return -1;
+  if (which >= 1 && which <= 3 && !dpg && !h->act.batch && need_trn(h, who)) return -1;
+  const Train &t = dpg ? (crit ? h->dpg.c : h->dpg.a) : crit ? h->act.c : h->act.batch ? h->act.a : h->trn;
   const int k = which & 3;
   *np = &c;
   *wp = k == 0 ? c.w[layer] : k == 1 ? t.tw[layer] : k == 2 ? t.mw[layer] : t.vw[layer];

@@ -104,6 +104,16 @@ the next `collect` acts with the trained actor.  `set_critic_weights()`, `get_cr
 learner's counters.  `train=True` reads CACLA_CRITIC_ALPHA, CACLA_ACTOR_ALPHA, DISCOUNT,
 TARGET_NETWORK_STEPS, NUM_EXPS_BEFORE_TRAIN, CACLA_VAR_ENABLED / _START / _BETA; what the device does
 not do is refused by name (aigar_amd.net.actrain_params).
+The DPG trainer (`train="dpg"` or `train=dict(algorithm="dpg", ...)`, with `continuous=`, `network=` and
+`memory=`): the reference's third learner (actorCritic.py, ALGORITHM "DPG") on the device.
+The critic Q(s, a) takes the action beside the state (`critic=` overrides aigar_amd.net.qcritic_spec's
+DPG_CRITIC_LAYERS / DPG_CRITIC_FUNC; its n_in is the actor's n_in + n_out); the actor and the critic
+each have a target, updated softly (SOFT_TARGET_UPDATES, DPG_TAU) or by a hard copy every
+TARGET_NETWORK_STEPS.  `train(n)` makes n steps -- the critic's TD update, then the actor's step along
+dQ/da through the updated critic, then the target update -- one graph replay each.  `get_weights(target=True)`
+is the actor's target, `get_critic_weights(target=)` the critic's, `q_value(states, actions)` evaluates
+the critic; `train_info()` has steps, skipped, since_target, actor_steps and actor_skipped.  What the
+device does not do is refused by name (aigar_amd.net.dpg_params).
 The Q-learning trainer (`train=True` or a dict, with `discrete=`, `network=` and `memory=`):
 the reference's Q-learning trainer (qLearning.py:116-193, Keras 2.2.4 Adam on the importance-weighted
 mse, a hard target copy every TARGET_NETWORK_STEPS) on the device, in place on the acting network's
@@ -321,10 +331,40 @@ class AgarVecEnv:
 
         self.training = None
         self.cacla = False  # (the trainer is the CACLA learner's: DESIGN.md §4m)
+        self.dpg = False  # (... the DPG learner's: §4n)
         self.critic = None
         if critic is not None and not (train and self.continuous is not None):
-            raise ValueError("critic= needs continuous= and train= (the CACLA trainer's critic)")
-        if train and self.continuous is not None:  # (explicit only, as memory=)
+            raise ValueError("critic= needs continuous= and train= (the CACLA or DPG trainer's critic)")
+        dpg = train == "dpg" or (isinstance(train, dict) and str(train.get("algorithm", "")).lower() == "dpg")
+        if isinstance(train, str) and not dpg:
+            raise ValueError("train=%r: True, a dict or 'dpg'" % (train,))
+        if isinstance(train, dict) and "algorithm" in train and not dpg:
+            raise ValueError("train: algorithm = %r: 'dpg' (the other trainers follow from discrete= / continuous=)"
+                             % (train["algorithm"],))
+        if dpg:
+            if self.continuous is None or self.network is None or self.memory is None:
+                raise ValueError("train='dpg' needs continuous=, network= and memory= (DPG on the device's replay "
+                                 "memory)")
+            if self.pixels is not None or hasattr(self.network, "convs"):
+                raise ValueError("train=: CNN / pixel states are not trained on the device")
+            tp = _net.dpg_params(parameters)
+            tp["batch"] = int(self.memory["batch"])
+            if isinstance(train, dict):
+                over = {k: v for k, v in train.items() if k != "algorithm"}
+                unknown = set(over) - set(tp)
+                if unknown:
+                    raise ValueError("train: unknown keys %s" % sorted(unknown))
+                tp.update(over)
+            n_in, n_act = int(self.stepper.obs_len), int(self.network.units[-1])
+            cs = _net.qcritic_spec(parameters, n_in=n_in, n_act=n_act) if critic is None else _net.NetSpec(*critic)
+            if cs.n_in is None:
+                cs = cs._replace(n_in=n_in + n_act)
+            self.critic = cs
+            self.stepper.qcritic_config(cs, self.obs.dtype)
+            self.training = tp
+            self.dpg = True
+            self.stepper.dpg_config(**tp)
+        elif train and self.continuous is not None:  # (explicit only, as memory=)
             if self.network is None or self.memory is None:
                 raise ValueError("train= with continuous= needs network= and memory= (CACLA on the device's replay "
                                  "memory)")
@@ -387,6 +427,8 @@ class AgarVecEnv:
             torch.cuda.synchronize(self.dev)
         if self.cacla:
             self.stepper.actrain_step(n, u)
+        elif self.dpg:
+            self.stepper.dpg_step(n, u)
         else:
             self.stepper.train_step(n, u)
         if self._mem_sync:
@@ -394,8 +436,11 @@ class AgarVecEnv:
 
     def train_info(self):
         """{steps, skipped, since_target} (aigar_train_info: a host round trip); the CACLA trainer's
-        also has actor_epochs, selected, epochs, cut and epochs_skipped (aigar_actrain_info)."""
+        also has actor_epochs, selected, epochs, cut and epochs_skipped (aigar_actrain_info), the
+        DPG trainer's actor_steps and actor_skipped (aigar_dpg_info)."""
         self._need_training()
+        if self.dpg:
+            return self.stepper.dpg_info()
         return self.stepper.actrain_info() if self.cacla else self.stepper.train_info()
 
     def train_td(self):
@@ -409,6 +454,8 @@ class AgarVecEnv:
             torch.cuda.synchronize(self.dev)
         if self.cacla:
             self.stepper.actrain_td(td, idx)
+        elif self.dpg:
+            self.stepper.dpg_td(td, idx)
         else:
             self.stepper.train_td(td, idx)
         if self._mem_sync:
@@ -428,15 +475,19 @@ class AgarVecEnv:
             self.torch.cuda.synchronize(self.dev)
         return self.stepper.net_get_weights("target" if target else "online")
 
-    # ---- the CACLA learner's critic
+    # ---- the CACLA learner's critic and the DPG learner's (§4n)
     def _need_cacla(self):
         if not self.cacla:
             raise RuntimeError("AgarVecEnv was created without continuous= and train= (the CACLA trainer)")
 
+    def _need_critic(self):
+        if not (self.cacla or self.dpg):
+            raise RuntimeError("AgarVecEnv was created without continuous= and train= (the CACLA or DPG trainer)")
+
     def set_critic_weights(self, weights):
         """The critic's weights, as set_weights takes the acting network's.  The trainer's target
         keeps what it holds (train= copied the critic as it was then)."""
-        self._need_cacla()
+        self._need_critic()
         torch = self.torch
         pairs = isinstance(weights, (list, tuple)) and all(
             isinstance(p, (list, tuple)) and len(p) == 2 and isinstance(p[0], torch.Tensor) and p[0].is_cuda
@@ -454,7 +505,7 @@ class AgarVecEnv:
 
     def get_critic_weights(self, target=False):
         """The critic's (target=True: its target's) weights as [(W [in, out], b [out])] float32 numpy arrays."""
-        self._need_cacla()
+        self._need_critic()
         if self._mem_sync:
             self.torch.cuda.synchronize(self.dev)
         return self.stepper.critic_get_weights("target" if target else "online")
@@ -467,6 +518,30 @@ class AgarVecEnv:
         if x.dtype not in (torch.float64, torch.float32):
             x = x.to(torch.float64)
         x = x.contiguous()
+        out = torch.empty(x.shape[0], dtype=torch.float64, device=self.dev)
+        if self._mem_sync:
+            torch.cuda.synchronize(self.dev)
+        self.stepper.critic_forward(x, out)
+        if self._mem_sync:
+            self.stepper.sync()
+        return out
+
+    def q_value(self, states, actions):
+        """Q(s, a) of states [rows, n_in] and actions [rows, n_act] (device tensors or arrays) with
+        the DPG trainer's critic -> [rows] float64 device tensor.  The row [s, a] is built in the
+        states' dtype (float64 unless they are float32)."""
+        if not self.dpg:
+            raise RuntimeError("AgarVecEnv was created without train='dpg' (the DPG trainer)")
+        torch = self.torch
+        s = torch.as_tensor(states, device=self.dev)
+        if s.dtype not in (torch.float64, torch.float32):
+            s = s.to(torch.float64)
+        a = torch.as_tensor(actions, device=self.dev).to(s.dtype)
+        n_act = self.critic.n_in - int(self.stepper.obs_len)
+        if s.ndim != 2 or a.ndim != 2 or a.shape[0] != s.shape[0] or a.shape[1] != n_act:
+            raise ValueError("q_value: states [rows, n_in] and actions [rows, %d], got %s and %s"
+                             % (n_act, tuple(s.shape), tuple(a.shape)))
+        x = torch.cat([s, a], dim=1).contiguous()
         out = torch.empty(x.shape[0], dtype=torch.float64, device=self.dev)
         if self._mem_sync:
             torch.cuda.synchronize(self.dev)

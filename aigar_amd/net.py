@@ -310,7 +310,8 @@ def actrain_params(parameters=None):
     setting."""
     g = lambda n, d: _get(parameters, n, d)
     if g("ALGORITHM", "CACLA") != "CACLA":
-        raise ValueError("actrain: ALGORITHM = %r: the device's actor-critic trainer is CACLA" % (g("ALGORITHM", "CACLA"),))
+        raise ValueError("actrain: ALGORITHM = %r: the device's actor-critic trainer is CACLA (for DPG pass train='dpg')"
+                         % (g("ALGORITHM", "CACLA"),))
     for name in ("OPTIMIZER", "OPTIMIZER_POLICY"):
         if g(name, "Adam") != "Adam":
             raise ValueError("actrain: %s = %r: the device trainer is Adam" % (name, g(name, "Adam")))
@@ -330,3 +331,63 @@ def actrain_params(parameters=None):
             "critic_lr": float(g("CACLA_CRITIC_ALPHA", 0.000075)), "actor_lr": float(g("CACLA_ACTOR_ALPHA", 0.0005)),
             "beta1": 0.9, "beta2": 0.999, "epsilon": 1e-7, "discount": float(g("DISCOUNT", 0.9)),
             "var_start": float(g("CACLA_VAR_START", 1)), "var_beta": float(g("CACLA_VAR_BETA", 0.001))}
+
+
+def qcritic_spec(parameters=None, n_in=None, n_act=None):
+    """NetSpec of the DPG learner's critic Q(s, a) (actorCritic.py ActionValueNetwork with
+    DPG_FEED_ACTION_IN_LAYER = 1): the input row is the state, then the action, so its n_in is
+    n_in + n_act (None while either is); DPG_CRITIC_LAYERS hidden layers with DPG_CRITIC_FUNC and
+    one linear output."""
+    g = lambda n, d: _get(parameters, n, d)
+    hidden = g("DPG_CRITIC_FUNC", "relu")
+    if hidden not in ("relu", "linear"):
+        raise ValueError("qcritic_spec: DPG_CRITIC_FUNC = %r is not supported by the device network (relu, linear)"
+                         % (hidden,))
+    units = tuple(int(v) for v in g("DPG_CRITIC_LAYERS", (100, 100)) if int(v) > 0)
+    if len(units) + 1 > _abi.NET_MAX_LAYERS:
+        raise ValueError("qcritic_spec: %d hidden layers, at most %d" % (len(units), _abi.NET_MAX_LAYERS - 1))
+    if any(v > _abi.NET_MAX_UNITS for v in units):
+        raise ValueError("qcritic_spec: a layer of %d units, at most %d" % (max(units), _abi.NET_MAX_UNITS))
+    if n_act is not None and not 1 <= int(n_act) <= 4:
+        raise ValueError("qcritic_spec: %d actions, 1..4" % (n_act,))
+    n = None if n_in is None or n_act is None else int(n_in) + int(n_act)
+    if n is not None and not 1 <= n <= _abi.NET_MAX_IN:
+        raise ValueError("qcritic_spec: %d inputs, at most %d" % (n, _abi.NET_MAX_IN))
+    return NetSpec(n, units + (1,), hidden, "linear")
+
+
+def dpg_params(parameters=None):
+    """The device's DPG trainer's settings from the reference's parameters: what
+    actorCritic.py does for ALGORITHM == "DPG" by default (an absent ALGORITHM counts as "DPG"
+    here).  SOFT_TARGET_UPDATES picks tau = DPG_TAU; without it tau = 0 and both targets are copied
+    every TARGET_NETWORK_STEPS.  Everything else the reference can train a DPG learner with is
+    refused here, by the name of the setting."""
+    g = lambda n, d: _get(parameters, n, d)
+    if g("ALGORITHM", "DPG") != "DPG":
+        raise ValueError("dpg: ALGORITHM = %r: this is the device's DPG trainer" % (g("ALGORITHM", "DPG"),))
+    for name in ("OPTIMIZER", "OPTIMIZER_POLICY", "DPG_ACTOR_OPTIMIZER"):
+        if g(name, "Adam") != "Adam":
+            raise ValueError("dpg: %s = %r: the device trainer is Adam" % (name, g(name, "Adam")))
+    for name in ("OCACLA_ENABLED", "CACLA_UPDATE_ON_NEGATIVE_TD", "CACLA_CRITIC_WEIGHT_DECAY", "CACLA_OFF_POLICY_CORR",
+                 "ACTOR_IS", "AC_ACTOR_TDE", "AC_DELAY_ACTOR_TRAINING", "AC_ACTOR_TRAINING_START", "AMSGRAD",
+                 "END_DISCOUNT", "DROPOUT", "GRADIENT_CLIP", "GRADIENT_CLIP_NORM", "USE_ACTION_AS_INPUT", "CNN_REPR",
+                 "BATCHNORM", "DPG_USE_CACLA", "DPG_CACLA_ALTERNATION", "DPG_CACLA_INV_ALTERNATION",
+                 "DPG_CRITIC_WEIGHT_DECAY", "DPG_ACTOR_NESTEROV"):
+        if g(name, 0):
+            raise ValueError("dpg: %s = %r is not supported by the device trainer" % (name, g(name, 0)))
+    if g("DPG_FEED_ACTION_IN_LAYER", 1) != 1:
+        raise ValueError("dpg: DPG_FEED_ACTION_IN_LAYER = %r: the action enters the critic beside the state (1)"
+                         % (g("DPG_FEED_ACTION_IN_LAYER", 1),))
+    for name in ("DPG_USE_TARGET_MODELS", "DPG_USE_DPG_ACTOR_TRAINING"):
+        if not g(name, True):
+            raise ValueError("dpg: %s = %r: the device trainer always does" % (name, g(name, True)))
+    if g("NEURON_TYPE", "MLP") != "MLP":
+        raise ValueError("dpg: NEURON_TYPE = %r: the device trainer takes no LSTM" % (g("NEURON_TYPE", "MLP"),))
+    if g("TD", 0) != 0:
+        raise ValueError("dpg: TD = %r: only one-step targets (TD = 0)" % (g("TD", 0),))
+    soft = bool(g("SOFT_TARGET_UPDATES", True))
+    return {"batch": int(g("MEMORY_BATCH_LEN", 32)), "min_size": int(g("NUM_EXPS_BEFORE_TRAIN", 32)),
+            "target_steps": int(g("TARGET_NETWORK_STEPS", 1500)),
+            "critic_lr": float(g("DPG_CRITIC_ALPHA", 0.0005)), "actor_lr": float(g("DPG_ACTOR_ALPHA", 0.0001)),
+            "beta1": 0.9, "beta2": 0.999, "epsilon": 1e-7, "discount": float(g("DISCOUNT", 0.9)),
+            "tau": float(g("DPG_TAU", 0.001)) if soft else 0.0, "q_increase": float(g("DPG_Q_VAL_INCREASE", 2))}

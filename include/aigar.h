@@ -828,6 +828,68 @@ int aigar_actrain_td(aigar_handle *h, double *td, int64_t *idx, int32_t *count);
 int aigar_actrain_var(aigar_handle *h, double *var);
 int aigar_actrain_sync_target(aigar_handle *h);
 int aigar_actrain_reset(aigar_handle *h);
+/* The DPG learner's critic and trainer on the device (actorCritic.py ActorCritic.learn for
+ * ALGORITHM == "DPG": train_critic_DPG 986-1029, train_actor_DPG 751-789 on
+ * createCombinedActorCritic 581-598, softlyUpdateTargetModel 366-373; DESIGN.md §4n;
+ * tests/dpg_model.py is the specification in plain Python).
+ *
+ * aigar_qcritic_config: the critic Q(s, a) in the handle's critic slot.  aigar_critic_config's
+ * checks, but n_in is the acting network's n_in + n_out (DPG_FEED_ACTION_IN_LAYER = 1: a row is
+ * the state, then the action), and the acting network must be dense with a sigmoid head and
+ * 1..4 outputs.  aigar_critic_set_weights, aigar_critic_forward (rows of the critic's own n_in)
+ * and which 4..7 serve it unchanged.  NULL turns it off.  aigar_actrain_config refuses a
+ * Q(s, a) critic, aigar_dpg_config a V(s) one.
+ *
+ * One training step on B drawn transitions (s, a[4], rew, s2, done, w); forward passes, the
+ * backward pass and Adam are aigar_train_step's.  An action entering the critic is the float64
+ * action rounded once to float32, as every input is.
+ *   critic half: mu2 = forward(s2, actor's target); q2 = forward([s2, mu2], critic's target);
+ *   q = forward([s, a], critic) with the activations kept; t = rew if done, else
+ *   rew + discount * q2 (float64: one multiply, one add); td = t - q; a prioritized memory gets
+ *   |td| + 1e-4; delta_L[r][0] = float32(((2 w_r) (-td_r)) / (1 B)), backward, Adam with
+ *   critic_lr and the counter t_c;
+ *   actor half, with the critic as just updated and both targets as before this step:
+ *   mu = forward(s, actor) with the activations kept, mu- = forward(s, actor's target);
+ *   qmu = forward([s, mu], critic) with the activations kept; qt = forward([s, mu-], critic's
+ *   target); dq[r][0] = float32((2.0 (qmu_r - (qt_r + q_increase))) / (1 B)) on every row;
+ *   backward through the critic's layers L-1 .. 1 to delta_0 (no critic gradient is formed);
+ *   ea[r][k] = ONE fmaf chain over ascending unit j of delta_0[r][j] W_0[n_s + k][j] from
+ *   +0.0f; the actor's delta_L[r][k] = float32((double)ea[r][k] (mu_rk (1.0 - mu_rk)));
+ *   backward through the actor; Adam with actor_lr and the actor's own m, v and counter t_a;
+ *   t_c += 1; tau > 0: both targets, every entry, theta- = float32(float32(theta- float32(1.0 -
+ *   tau)) + float32(theta float32(tau))); tau == 0: both targets are copied after a step with
+ *   t_c % target_steps == 0 (target_steps > 0).
+ * A step is skipped -- nothing changes -- while the memory holds fewer than max(batch,
+ * min_size) transitions, and, with AIGAR_WARN_TRAIN_NONFINITE, when a td is not finite.  A
+ * non-finite dq or actor delta_L entry skips the actor half only, with the same bit: the critic's
+ * update and the target update apply, t_a stays, the half is counted.
+ *
+ * aigar_dpg_config: the parameters are checked before the handle, each refusal with its own
+ * message (batch 1..256, min_size >= 0, target_steps >= 0, reserved 0, both lr > 0, betas in
+ * [0, 1), epsilon > 0, discount in [0, 1], tau in [0, 1], q_increase finite).  It needs a Q(s, a)
+ * critic, a replay memory whose state length is the actor's n_in, no conv part and no tiled
+ * handle.  It allocates both targets as copies of the networks as they are NOW and zeroed Adam
+ * state.  NULL turns it off; aigar_net_config*, aigar_critic_config, aigar_qcritic_config and
+ * aigar_exp_config drop it.  The three train configurations exclude one another by the head of
+ * the acting network and the kind of the critic.
+ * aigar_dpg_step: as aigar_actrain_step.  aigar_dpg_info: {critic steps applied, steps skipped,
+ * steps since the hard copy, actor steps applied (t_a), actor halves skipped, 0, 0, 0}; a
+ * synchronising read.  aigar_dpg_td: stream-ordered copies of the last drawn step's td [batch]
+ * and indices [batch] into DEVICE buffers (each may be NULL).  aigar_dpg_sync_target: both
+ * targets <- online now.  aigar_dpg_reset: both networks' m and v, t_c and t_a to zero.
+ * aigar_net_get_weights / aigar_net_pad_check under a DPG configuration: which 1 is the actor's
+ * target, 2 / 3 the actor's m / v, 5..7 the critic's target, m, v. */
+typedef struct aigar_dpg_params {
+  int32_t batch, min_size, target_steps, reserved;   /* 1..256, >=0, >=0, 0 */
+  double critic_lr, actor_lr, beta1, beta2, epsilon, discount, tau, q_increase;
+} aigar_dpg_params;                                   /* 80 bytes */
+int aigar_qcritic_config(aigar_handle *h, const aigar_net_params *p);
+int aigar_dpg_config(aigar_handle *h, const aigar_dpg_params *p);
+int aigar_dpg_step(aigar_handle *h, int n_steps, const double *u);
+int aigar_dpg_info(aigar_handle *h, int64_t info[8]);
+int aigar_dpg_td(aigar_handle *h, double *td, int64_t *idx);
+int aigar_dpg_sync_target(aigar_handle *h);
+int aigar_dpg_reset(aigar_handle *h);
 /* The sticky quirk bits of one arena since its last reset (a host round trip): 1 a virus
  * made this tick ate, 2 a dead virus was met, 4 a tile observed past its held pellets,
  * 8 AIGAR_WARN_Q_NONFINITE, 16 AIGAR_WARN_NOISE_NONFINITE, 32 AIGAR_WARN_NOISE_EXHAUSTED,
