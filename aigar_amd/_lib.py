@@ -767,6 +767,38 @@ class Stepper:
         self._chk(self.L.aigar_net_pad_check(self.h, code[which], C.byref(v)))
         return int(v.value)
 
+    # ---- the three trainers' shared plumbing: kind is the entry points' prefix
+    _TRAINERS = {"train": ("trn", "no training is configured (train_config)"),
+                 "actrain": ("act", "no CACLA training is configured (actrain_config)"),
+                 "dpg": ("dpg", "no DPG training is configured (dpg_config)")}
+
+    def _need_trainer(self, kind, what):
+        """The batch of the configured trainer of this kind; what: the caller, for the message."""
+        attr, msg = self._TRAINERS[kind]
+        if getattr(self, attr, None) is None:
+            raise RuntimeError("aigar: %s: %s" % (what, msg))
+        return getattr(self, attr)
+
+    def _trainer_call(self, kind, name, *args):
+        """aigar_<kind>_<name>(handle, *args) once the trainer is known to be configured."""
+        self._need_trainer(kind, "%s_%s" % (kind, name))
+        self._chk(getattr(self.L, "aigar_%s_%s" % (kind, name))(self.h, *args))
+
+    def _trainer_step(self, kind, n, u):
+        batch, up = self._need_trainer(kind, kind + "_step"), None
+        if u is not None:
+            self._check_dev(u, (int(n), batch), ("float64",), kind + "_step")
+            up = C.c_void_p(u.data_ptr())
+        self._trainer_call(kind, "step", int(n), up)
+
+    def _trainer_td(self, kind, *outs):
+        """outs: (tensor or None, dtype) of every optional [batch] output, in the call's order."""
+        batch = self._need_trainer(kind, kind + "_td")
+        for t, dt in outs:
+            if t is not None:
+                self._check_dev(t, (batch,), (dt,), kind + "_td")
+        self._trainer_call(kind, "td", *(None if t is None else C.c_void_p(t.data_ptr()) for t, _ in outs))
+
     # ---- the Q-learning trainer (include/aigar.h: aigar_train*)
     def train_config(self, batch=32, min_size=0, target_steps=0, lr=1e-4, beta1=0.9, beta2=0.999, epsilon=1e-7,
                      discount=0.85):
@@ -783,49 +815,28 @@ class Stepper:
         self._chk(self.L.aigar_train_config(self.h, C.byref(prm)))
         self.trn = int(batch)
 
-    def _need_trn(self, what):
-        if getattr(self, "trn", None) is None:
-            raise RuntimeError("aigar: %s: no training is configured (train_config)" % what)
-        return self.trn
-
     def train_step(self, n=1, u=None):
         """n training steps, one graph replay each with no host work in between
         (aigar_train_step).  u: None (the memory's own stream) or a device tensor [n, batch]
         float64 of draws in [0, 1)."""
-        batch = self._need_trn("train_step")
-        up = None
-        if u is not None:
-            self._check_dev(u, (int(n), batch), ("float64",), "train_step")
-            up = C.c_void_p(u.data_ptr())
-        self._chk(self.L.aigar_train_step(self.h, int(n), up))
+        self._trainer_step("train", n, u)
 
     def train_info(self):
         """{steps, skipped, since_target} of the trainer (the one synchronising read)."""
-        self._need_trn("train_info")
         v = (C.c_int64 * 4)()
-        self._chk(self.L.aigar_train_info(self.h, v))
+        self._trainer_call("train", "info", v)
         return {"steps": v[0], "skipped": v[1], "since_target": v[2]}
 
     def train_td(self, td=None, idx=None):
         """The last drawn step's TD errors and memory indices into the device tensors td [batch]
         float64 and idx [batch] int64 (stream-ordered copies)."""
-        batch = self._need_trn("train_td")
-        tp = ip = None
-        if td is not None:
-            self._check_dev(td, (batch,), ("float64",), "train_td")
-            tp = C.c_void_p(td.data_ptr())
-        if idx is not None:
-            self._check_dev(idx, (batch,), ("int64",), "train_td")
-            ip = C.c_void_p(idx.data_ptr())
-        self._chk(self.L.aigar_train_td(self.h, tp, ip))
+        self._trainer_td("train", (td, "float64"), (idx, "int64"))
 
     def train_sync_target(self):
-        self._need_trn("train_sync_target")
-        self._chk(self.L.aigar_train_sync_target(self.h))
+        self._trainer_call("train", "sync_target")
 
     def train_reset(self):
-        self._need_trn("train_reset")
-        self._chk(self.L.aigar_train_reset(self.h))
+        self._trainer_call("train", "reset")
 
     # ---- the CACLA learner's critic and trainer (include/aigar.h: aigar_critic*, aigar_actrain*)
     def critic_config(self, spec, x_dtype="float64", _entry="aigar_critic_config"):
@@ -926,53 +937,33 @@ class Stepper:
         self._chk(self.L.aigar_actrain_config(self.h, C.byref(prm)))
         self.act = int(batch)
 
-    def _need_act(self, what):
-        if getattr(self, "act", None) is None:
-            raise RuntimeError("aigar: %s: no CACLA training is configured (actrain_config)" % what)
-        return self.act
-
     def actrain_step(self, n=1, u=None):
         """n CACLA training steps, one graph replay each (aigar_actrain_step); u as train_step's."""
-        batch = self._need_act("actrain_step")
-        up = None
-        if u is not None:
-            self._check_dev(u, (int(n), batch), ("float64",), "actrain_step")
-            up = C.c_void_p(u.data_ptr())
-        self._chk(self.L.aigar_actrain_step(self.h, int(n), up))
+        self._trainer_step("actrain", n, u)
 
     def actrain_info(self):
         """The CACLA trainer's counters (aigar_actrain_info: the one synchronising read)."""
-        self._need_act("actrain_info")
         v = (C.c_int64 * 8)()
-        self._chk(self.L.aigar_actrain_info(self.h, v))
+        self._trainer_call("actrain", "info", v)
         return {"steps": v[0], "skipped": v[1], "since_target": v[2], "actor_epochs": v[3], "selected": v[4],
                 "epochs": v[5], "cut": v[6], "epochs_skipped": v[7]}
 
     def actrain_td(self, td=None, idx=None, count=None):
         """The last drawn step's TD errors, memory indices and per-row actor epochs into the device
         tensors td [batch] float64, idx [batch] int64 and count [batch] int32."""
-        batch = self._need_act("actrain_td")
-        ptrs = []
-        for t, dt in ((td, "float64"), (idx, "int64"), (count, "int32")):
-            if t is not None:
-                self._check_dev(t, (batch,), (dt,), "actrain_td")
-            ptrs.append(None if t is None else C.c_void_p(t.data_ptr()))
-        self._chk(self.L.aigar_actrain_td(self.h, *ptrs))
+        self._trainer_td("actrain", (td, "float64"), (idx, "int64"), (count, "int32"))
 
     def actrain_var(self):
         """CACLA-Var's running variance (a host round trip)."""
-        self._need_act("actrain_var")
         v = C.c_double()
-        self._chk(self.L.aigar_actrain_var(self.h, C.byref(v)))
+        self._trainer_call("actrain", "var", C.byref(v))
         return float(v.value)
 
     def actrain_sync_target(self):
-        self._need_act("actrain_sync_target")
-        self._chk(self.L.aigar_actrain_sync_target(self.h))
+        self._trainer_call("actrain", "sync_target")
 
     def actrain_reset(self):
-        self._need_act("actrain_reset")
-        self._chk(self.L.aigar_actrain_reset(self.h))
+        self._trainer_call("actrain", "reset")
 
     # ---- the DPG trainer (include/aigar.h: aigar_dpg*)
     def dpg_config(self, batch=32, min_size=0, target_steps=0, critic_lr=5e-4, actor_lr=1e-4, beta1=0.9, beta2=0.999,
@@ -990,45 +981,26 @@ class Stepper:
         self._chk(self.L.aigar_dpg_config(self.h, C.byref(prm)))
         self.dpg = int(batch)
 
-    def _need_dpg(self, what):
-        if getattr(self, "dpg", None) is None:
-            raise RuntimeError("aigar: %s: no DPG training is configured (dpg_config)" % what)
-        return self.dpg
-
     def dpg_step(self, n=1, u=None):
         """n DPG training steps, one graph replay each (aigar_dpg_step); u as train_step's."""
-        batch = self._need_dpg("dpg_step")
-        up = None
-        if u is not None:
-            self._check_dev(u, (int(n), batch), ("float64",), "dpg_step")
-            up = C.c_void_p(u.data_ptr())
-        self._chk(self.L.aigar_dpg_step(self.h, int(n), up))
+        self._trainer_step("dpg", n, u)
 
     def dpg_info(self):
         """The DPG trainer's counters (aigar_dpg_info: the one synchronising read)."""
-        self._need_dpg("dpg_info")
         v = (C.c_int64 * 8)()
-        self._chk(self.L.aigar_dpg_info(self.h, v))
+        self._trainer_call("dpg", "info", v)
         return {"steps": v[0], "skipped": v[1], "since_target": v[2], "actor_steps": v[3], "actor_skipped": v[4]}
 
     def dpg_td(self, td=None, idx=None):
         """The last drawn step's TD errors and memory indices into the device tensors td [batch]
         float64 and idx [batch] int64."""
-        batch = self._need_dpg("dpg_td")
-        ptrs = []
-        for t, dt in ((td, "float64"), (idx, "int64")):
-            if t is not None:
-                self._check_dev(t, (batch,), (dt,), "dpg_td")
-            ptrs.append(None if t is None else C.c_void_p(t.data_ptr()))
-        self._chk(self.L.aigar_dpg_td(self.h, *ptrs))
+        self._trainer_td("dpg", (td, "float64"), (idx, "int64"))
 
     def dpg_sync_target(self):
-        self._need_dpg("dpg_sync_target")
-        self._chk(self.L.aigar_dpg_sync_target(self.h))
+        self._trainer_call("dpg", "sync_target")
 
     def dpg_reset(self):
-        self._need_dpg("dpg_reset")
-        self._chk(self.L.aigar_dpg_reset(self.h))
+        self._trainer_call("dpg", "reset")
 
     def net_forward(self, x, out):
         """The network alone on device tensors (aigar_net_forward): x [rows, n_in] float64 /

@@ -45,39 +45,18 @@ __global__ void __launch_bounds__(kTrainMaxBatch) k_td_v(ACTrain t, Exp e, Dev d
   __shared__ int emax;
   const Train &c = t.c;
   const int r = threadIdx.x, B = t.batch, E = t.var_epochs;
-  const int64_t size = e.ctl->size;
-  const int64_t need = c.batch > c.min_size ? c.batch : c.min_size;
-  const bool small = size < need || (e.prio && size < 2);
-  TrainCtl *ctl = c.ctl;
+  const bool small = train_small(c, e);
   ACtl *x = t.x;
   double td = 0.0;
   bool bad = false;
-  if (r < B && !small) {
-    double tg = c.r[r];
-    if (!c.done[r]) tg = tg + c.discount * c.q2[r];
-    td = tg - c.q[r];
-    bad = !(fabs(td) < __builtin_inf());
-    c.td[r] = td;
-  }
+  if (r < B && !small) td = td_scalar(c, r, bad);
   tds[r] = td;
   if (r == 0) emax = 0;
   const bool any_bad = __syncthreads_or(bad ? 1 : 0) != 0;
   const bool skip = small || any_bad;
-  if (r < B) {
-    c.prio[r] = skip ? 0.0 : fabs(td) + 1e-4;
-    float g = 0.0f;
-    if (!skip) g = (float)(((2.0 * c.w[r]) * (-td)) / (double)(1 * B));
-    float *row = c.delta + ((size_t)(n_layers - 1) * c.bpad + r) * kNetMaxUnits;
-    for (int j = 0; j < 16; j++) row[j] = j == 0 ? g : -0.0f;
-  }
+  if (r < B) delta_scalar(c, n_layers, r, td_prio_grad(c, r, skip, td, 1));
   if (r == 0) {
-    const int64_t tn = ctl->t + 1;
-    ctl->skip = skip ? 1 : 0;
-    ctl->due = (!skip && c.target_steps > 0 && tn % c.target_steps == 0) ? 1 : 0;
-    ctl->lr_t = c.lr * sqrt(1.0 - aigar_math::pow_glibc(c.beta2, (double)tn)) /
-                (1.0 - aigar_math::pow_glibc(c.beta1, (double)tn));
-    if (!small) e.ctl->calls += 1;
-    if (any_bad) atomicOr(&d.ctl[0].warn, (uint32_t)WARN_TRAIN_NONFINITE);
+    td_decide(c, e, d, small, any_bad);
     x->stop = 0;
     if (!skip && E > 0) {
       double var = x->var;
@@ -145,8 +124,7 @@ __global__ void __launch_bounds__(kTrainMaxBatch) k_actor_delta(ACTrain t, Dev d
     ctl->skip = apply ? 0 : 1;
     if (apply) {
       const int64_t tn = ctl->t + 1;
-      ctl->lr_t = a.lr * sqrt(1.0 - aigar_math::pow_glibc(a.beta2, (double)tn)) /
-                  (1.0 - aigar_math::pow_glibc(a.beta1, (double)tn));
+      ctl->lr_t = adam_lr_t(a, tn);
       ctl->t = tn;
     } else if (live) {
       x->eskipped += 1;

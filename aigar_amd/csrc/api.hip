@@ -157,9 +157,11 @@ struct TileKey {  // aigar_tile_begin, aigar_tile_end: the tick before the first
   void *out;           // (tile_begin: none)
   int dtype;           // -1: no observation
 };
-struct TrainKey {  // aigar_train_step: one training step (every buffer is the train configuration's own)
+struct TrainKey {  // aigar_*_step: one training step (every buffer is the train configuration's own)
+  int kind;   // whose step it is: kTrainQ, kTrainCacla, kTrainDpg
   int has_u;  // the draws come from the handle's u row (the caller's draws are copied there)
 };
+enum { kTrainQ, kTrainCacla, kTrainDpg };
 struct EnvKey {  // aigar_env_step*: one learner decision
   const double *act;
   int n_act, enable_split, skip, dtype;
@@ -312,25 +314,20 @@ struct aigar_handle {
   DevBlock exp_mem;
   int *d_exp_off = nullptr;  // aigar_exp_add's slot offsets, [exp_off_n]
   size_t exp_off_n = 0;
-  // aigar_train_config: the Q-learning trainer (train.inc; batch 0: off) and its step's graph
-  Train trn;
-  DevBlock trn_mem;
-  KeyedSlot<TrainKey> train;
-  // aigar_critic_config: the CACLA learner's critic, a second network (n_layers 0: off)
+  // aigar_critic_config: the actor-critic learners' critic, a second network (n_layers 0: off)
   Net crit{};
   DevBlock crit_mem;
   float *crit_stage = nullptr;  // aigar_critic_set_weights' staging of host weights (one of crit_mem)
-  // aigar_actrain_config: the CACLA trainer (actrain.inc; batch 0: off) and its step's graph
-  ACTrain act;
-  DevBlock act_mem;
-  KeyedSlot<TrainKey> actrain;
   // aigar_qcritic_config: the critic is Q(s, a), its rows are [state, action]
   bool crit_q = false;
-  // aigar_dpg_config: the DPG trainer (dpg.inc; batch 0: off) and its step's graph
-  DPGTrain dpg;
-  DevBlock dpg_mem;
-  KeyedSlot<TrainKey> dpgs;
-  GraphSlot *const slots[10] = {&step, &run, &run_u, &env, &tb, &te, &tr, &train, &actrain, &dpgs};
+  // The trainer (batch 0: off).  At most one is configured -- each needs another head or critic --
+  // so they share one block of buffers and one step graph (trainer_free).
+  Train trn;     // aigar_train_config: Q-learning (train.inc)
+  ACTrain act;   // aigar_actrain_config: CACLA (actrain.inc)
+  DPGTrain dpg;  // aigar_dpg_config: DPG (dpg.inc)
+  DevBlock trn_mem;
+  KeyedSlot<TrainKey> train;
+  GraphSlot *const slots[8] = {&step, &run, &run_u, &env, &tb, &te, &tr, &train};
 };
 
 void GraphSlot::drop(aigar_handle *h) {
@@ -394,7 +391,7 @@ static void free_all(aigar_handle *h) {
   h->pix_bytes = 0;
   if (h->d_pix_hist) (void)hipFree(h->d_pix_hist);
   h->d_pix_hist = nullptr;
-  for (DevBlock *m : {&h->exp_mem, &h->dec_mem, &h->noi_mem, &h->net_mem, &h->trn_mem, &h->crit_mem, &h->act_mem, &h->dpg_mem}) m->release();
+  for (DevBlock *m : {&h->exp_mem, &h->dec_mem, &h->noi_mem, &h->net_mem, &h->trn_mem, &h->crit_mem}) m->release();
   if (h->d_exp_off) (void)hipFree(h->d_exp_off);
   h->d_exp_off = nullptr;
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1474,27 +1471,17 @@ static int begin_reconfig(aigar_handle *h) {
   h->env.drop(h);
   return 0;
 }
-// The train configuration goes with the network or the memory it was made for
-// (after begin_reconfig: no training step is pending).
-static void train_free(aigar_handle *h) {
+// The train configuration, whichever it is, goes with the network, the memory or the critic it
+// was made for (after begin_reconfig: no training step is pending).
+static void trainer_free(aigar_handle *h) {
   h->train.drop(h);
   h->trn_mem.release();
   h->trn = Train{};
-}
-// ... and so does the CACLA trainer's, which also goes with the critic
-static void actrain_free(aigar_handle *h) {
-  h->actrain.drop(h);
-  h->act_mem.release();
   h->act = ACTrain{};
-}
-static void dpg_free(aigar_handle *h) {
-  h->dpgs.drop(h);
-  h->dpg_mem.release();
   h->dpg = DPGTrain{};
 }
 static void critic_free(aigar_handle *h) {
-  actrain_free(h);
-  dpg_free(h);
+  if (!h->trn.batch) trainer_free(h);  // (Q-learning trains without the critic: it stays)
   h->crit_q = false;
   h->crit_mem.release();
   h->crit = Net{};
@@ -1685,18 +1672,24 @@ static const char *net_act_name(int a) {
   return "unknown";
 }
 
+// A dense network's shape, as the acting network and the critic take it: every check up to the head's.
+static int net_shape_check(const char *who, const aigar_net_params *p) {
+  if (p->n_layers < 1 || p->n_layers > kNetMaxLayers)
+    return fail("%s: n_layers = %d is outside 1..%d", who, p->n_layers, kNetMaxLayers);
+  if (p->n_in < 1 || p->n_in > kNetMaxIn) return fail("%s: n_in = %d is outside 1..%d", who, p->n_in, kNetMaxIn);
+  for (int l = 0; l < p->n_layers; l++)
+    if (p->units[l] < 1 || p->units[l] > kNetMaxUnits)
+      return fail("%s: layer %d has %d units, outside 1..%d", who, l, p->units[l], kNetMaxUnits);
+  if (p->x_dtype != 0 && p->x_dtype != 1) return fail("%s: x_dtype must be 0 (float64) or 1 (float32)", who);
+  if (p->hidden_act != AIGAR_ACT_RELU && p->hidden_act != AIGAR_ACT_LINEAR)
+    return fail("%s: hidden activation %d (%s) is not supported: relu or linear", who, p->hidden_act,
+                net_act_name(p->hidden_act));
+  return 0;
+}
+
 extern "C" int aigar_net_config(aigar_handle *h, const aigar_net_params *p) {
   if (p) {  // (before the handle: a bad set has its own message)
-    if (p->n_layers < 1 || p->n_layers > kNetMaxLayers)
-      return fail("net_config: n_layers = %d is outside 1..%d", p->n_layers, kNetMaxLayers);
-    if (p->n_in < 1 || p->n_in > kNetMaxIn) return fail("net_config: n_in = %d is outside 1..%d", p->n_in, kNetMaxIn);
-    for (int l = 0; l < p->n_layers; l++)
-      if (p->units[l] < 1 || p->units[l] > kNetMaxUnits)
-        return fail("net_config: layer %d has %d units, outside 1..%d", l, p->units[l], kNetMaxUnits);
-    if (p->x_dtype != 0 && p->x_dtype != 1) return fail("net_config: x_dtype must be 0 (float64) or 1 (float32)");
-    if (p->hidden_act != AIGAR_ACT_RELU && p->hidden_act != AIGAR_ACT_LINEAR)
-      return fail("net_config: hidden activation %d (%s) is not supported: relu or linear", p->hidden_act,
-                  net_act_name(p->hidden_act));
+    if (net_shape_check("net_config", p)) return -1;
     if (p->out_act != AIGAR_ACT_LINEAR && p->out_act != AIGAR_ACT_SIGMOID)
       return fail("net_config: output activation %d (%s) is not supported: linear or sigmoid", p->out_act,
                   net_act_name(p->out_act));
@@ -1704,7 +1697,7 @@ extern "C" int aigar_net_config(aigar_handle *h, const aigar_net_params *p) {
   if (!h) return fail("null handle");
   if (p && h->d.tiled) return fail("net_config: a tiled handle has no acting network");
   if (begin_reconfig(h)) return -1;
-  train_free(h);
+  trainer_free(h);
   critic_free(h);
   net_free(h);
   if (!p) return 0;
@@ -1736,19 +1729,20 @@ extern "C" int aigar_net_config(aigar_handle *h, const aigar_net_params *p) {
   return 0;
 }
 
-extern "C" int aigar_net_set_weights(aigar_handle *h, int layer, const float *W, const float *b, int on_device) {
-  if (need_net(h, "net_set_weights")) return -1;
-  const Net &c = h->net;
-  if (layer < 0 || layer >= c.n_layers) return fail("net_set_weights: layer %d is outside 0..%d", layer, c.n_layers - 1);
-  if (!W || !b) return fail("net_set_weights: null argument");
+// aigar_net_set_weights, aigar_critic_set_weights: layer `layer` of the dense network c from Keras'
+// layout, through c's staging when the caller's arrays are the host's
+static int set_dense_weights(aigar_handle *h, const char *who, const Net &c, float *stage, int layer, const float *W,
+                             const float *b, int on_device) {
+  if (layer < 0 || layer >= c.n_layers) return fail("%s: layer %d is outside 0..%d", who, layer, c.n_layers - 1);
+  if (!W || !b) return fail("%s: null argument", who);
   HIPCHK(hipSetDevice(h->cfg.device));
   const int in = c.in[layer], out = c.out[layer];
   const size_t nw = (size_t)in * out;
   if (!on_device) {
-    HIPCHK(hipMemcpyAsync(h->net_stage, W, nw * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->net_stage + nw, b, (size_t)out * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    W = h->net_stage;
-    b = h->net_stage + nw;
+    HIPCHK(hipMemcpyAsync(stage, W, nw * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(stage + nw, b, (size_t)out * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    W = stage;
+    b = stage + nw;
   }
   const int ip = net_in_pad(in), op = net_out_pad(out);
   const size_t n = (size_t)ip * op;
@@ -1757,6 +1751,10 @@ extern "C" int aigar_net_set_weights(aigar_handle *h, int layer, const float *W,
   HIPCHK(hipGetLastError());
   if (!on_device) HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's arrays are read, the staging is free)
   return 0;
+}
+extern "C" int aigar_net_set_weights(aigar_handle *h, int layer, const float *W, const float *b, int on_device) {
+  if (need_net(h, "net_set_weights")) return -1;
+  return set_dense_weights(h, "net_set_weights", h->net, h->net_stage, layer, W, b, on_device);
 }
 
 extern "C" int aigar_net_forward(aigar_handle *h, const void *x, int x_dtype, int rows, double *out) {
@@ -2106,9 +2104,7 @@ extern "C" int aigar_exp_config(aigar_handle *h, const aigar_exp_params *p) {
       return fail("exp_config: need alpha >= 0 and beta > 0 (got %g, %g)", p->alpha, p->beta);
   }
   if (begin_reconfig(h)) return -1;  // (no reader of the memory is pending either)
-  train_free(h);
-  actrain_free(h);
-  dpg_free(h);
+  trainer_free(h);
   h->exp_mem.release();
   h->exp = Exp{};
   if (!on) return 0;
@@ -2251,15 +2247,13 @@ extern "C" int aigar_exp_add(aigar_handle *h, const void *s, const double *a, co
   return 0;
 }
 
-static void launch_exp_fetch(aigar_handle *h, const int64_t *idx, int batch, void *s, double *a, double *r, void *s2,
-                             uint8_t *done, int count) {
+static void launch_exp_fetch(aigar_handle *h, hipStream_t st, const int64_t *idx, int batch, void *s, double *a, double *r,
+                             void *s2, uint8_t *done, int count) {
   const Exp &e = h->exp;
   if (e.dtype == 0)
-    hipLaunchKernelGGL(k_exp_fetch<uint64_t>, dim3(batch), dim3(256), 0, h->stream, e, idx, (char *)s, a, r, (char *)s2,
-                       done, count);
+    hipLaunchKernelGGL(k_exp_fetch<uint64_t>, dim3(batch), dim3(256), 0, st, e, idx, (char *)s, a, r, (char *)s2, done, count);
   else
-    hipLaunchKernelGGL(k_exp_fetch<uint32_t>, dim3(batch), dim3(256), 0, h->stream, e, idx, (char *)s, a, r, (char *)s2,
-                       done, count);
+    hipLaunchKernelGGL(k_exp_fetch<uint32_t>, dim3(batch), dim3(256), 0, st, e, idx, (char *)s, a, r, (char *)s2, done, count);
 }
 
 extern "C" int aigar_exp_sample(aigar_handle *h, int batch, const double *u, void *s, double *a, double *r, void *s2,
@@ -2269,7 +2263,7 @@ extern "C" int aigar_exp_sample(aigar_handle *h, int batch, const double *u, voi
   if (!w || !idx) return fail("exp_sample: w and idx are needed");
   HIPCHK(hipSetDevice(h->cfg.device));
   hipLaunchKernelGGL(k_exp_draw, dim3((batch + 255) / 256), dim3(256), 0, h->stream, h->exp, batch, u, w, idx);
-  launch_exp_fetch(h, idx, batch, s, a, r, s2, done, 1);
+  launch_exp_fetch(h, h->stream, idx, batch, s, a, r, s2, done, 1);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2281,7 +2275,7 @@ extern "C" int aigar_exp_gather(aigar_handle *h, const int64_t *idx, int batch, 
   if (batch == 0) return 0;
   if (!idx) return fail("exp_gather: null idx");
   HIPCHK(hipSetDevice(h->cfg.device));
-  launch_exp_fetch(h, idx, batch, s, a, r, s2, done, 0);
+  launch_exp_fetch(h, h->stream, idx, batch, s, a, r, s2, done, 0);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2322,93 +2316,235 @@ extern "C" int aigar_exp_extra_set(aigar_handle *h, const int64_t *idx, const do
   return 0;
 }
 
-// ------------------------------------------------------------ Q-learning trainer
+// ------------------------------------------------------------ the trainers: what the three share
 static int need_trn(aigar_handle *h, const char *who) {
   return need(h, h && h->trn.batch, who, "no training is configured (aigar_train_config)");
 }
+static int need_crit(aigar_handle *h, const char *who) {
+  return need(h, h && h->crit.n_layers, who, "no critic is configured (aigar_critic_config)");
+}
+static int need_act(aigar_handle *h, const char *who) {
+  return need(h, h && h->act.batch, who, "no CACLA training is configured (aigar_actrain_config)");
+}
+static int need_dpg(aigar_handle *h, const char *who) {
+  return need(h, h && h->dpg.batch, who, "no DPG training is configured (aigar_dpg_config)");
+}
 
-extern "C" int aigar_train_config(aigar_handle *h, const aigar_train_params *p) {
-  if (p) {  // (before the handle: a bad set has its own message)
-    if (p->batch < 1 || p->batch > kTrainMaxBatch)
-      return fail("train_config: batch = %d is outside 1..%d", p->batch, kTrainMaxBatch);
-    if (p->min_size < 0) return fail("train_config: min_size = %d is negative", p->min_size);
-    if (p->target_steps < 0) return fail("train_config: target_steps = %d is negative", p->target_steps);
-    if (!(p->lr > 0) || !(p->lr < __builtin_inf())) return fail("train_config: lr = %g must be positive and finite", p->lr);
-    if (!(p->beta1 >= 0 && p->beta1 < 1)) return fail("train_config: beta1 = %g is outside [0, 1)", p->beta1);
-    if (!(p->beta2 >= 0 && p->beta2 < 1)) return fail("train_config: beta2 = %g is outside [0, 1)", p->beta2);
-    if (!(p->epsilon > 0) || !(p->epsilon < __builtin_inf()))
-      return fail("train_config: epsilon = %g must be positive and finite", p->epsilon);
-    if (!(p->discount >= 0 && p->discount <= 1)) return fail("train_config: discount = %g is outside [0, 1]", p->discount);
+// A *_config's parameter checks (before the handle: a bad set has its own message), in the order
+// every trainer reports them: the sizes, its own integers, the learning rates, Adam's constants
+// and the discount, its own doubles.  P: aigar_train_params, aigar_actrain_params, aigar_dpg_params.
+static int check_positive(const char *who, const char *name, double v) {
+  return v > 0 && v < __builtin_inf() ? 0 : fail("%s: %s = %g must be positive and finite", who, name, v);
+}
+static int check_fraction(const char *who, const char *name, double v) {
+  return v >= 0 && v < 1 ? 0 : fail("%s: %s = %g is outside [0, 1)", who, name, v);
+}
+template <class P>
+static int check_train_sizes(const char *who, const P *p) {
+  if (p->batch < 1 || p->batch > kTrainMaxBatch) return fail("%s: batch = %d is outside 1..%d", who, p->batch, kTrainMaxBatch);
+  if (p->min_size < 0) return fail("%s: min_size = %d is negative", who, p->min_size);
+  if (p->target_steps < 0) return fail("%s: target_steps = %d is negative", who, p->target_steps);
+  return 0;
+}
+template <class P>
+static int check_train_adam(const char *who, const P *p) {
+  if (check_fraction(who, "beta1", p->beta1) || check_fraction(who, "beta2", p->beta2) ||
+      check_positive(who, "epsilon", p->epsilon))
+    return -1;
+  if (!(p->discount >= 0 && p->discount <= 1)) return fail("%s: discount = %g is outside [0, 1]", who, p->discount);
+  return 0;
+}
+
+// ... and its handle checks: these first for every trainer, then its own (head, critic,
+// selection) around need_exp, and the widths last.
+static int check_train_net(aigar_handle *h, const char *who) {
+  if (h->d.tiled) return fail("%s: a tiled handle has no training", who);
+  if (need_net(h, who)) return -1;
+  if (h->conv.n_conv) return fail("%s: a network with a conv part is not trained on the device", who);
+  return 0;
+}
+static int check_train_widths(aigar_handle *h, const char *who) {
+  if (h->net.in[0] == h->exp.L) return 0;
+  return fail("%s: the network has %d inputs, the memory's states %d values", who, h->net.in[0], h->exp.L);
+}
+
+// One zeroed buffer of the trainer's block; null, and ok false from then on, when one is refused
+static void *train_get(aigar_handle *h, bool &ok, size_t bytes) {
+  if (!ok) return nullptr;
+  void *q = h->trn_mem.alloc(bytes, true, h->stream);
+  ok = q != nullptr;
+  return q;
+}
+
+// What a trainer's views share: the settings and the staged batch.
+template <class P>
+static Train train_shared(aigar_handle *h, bool &ok, const P *p) {
+  const size_t B = (size_t)p->batch, row = (size_t)h->exp.L * h->exp.esz;
+  Train s;
+  s.batch = p->batch;
+  s.bpad = (p->batch + kNetRows - 1) / kNetRows * kNetRows;
+  s.min_size = p->min_size;
+  s.target_steps = p->target_steps;
+  s.beta1 = p->beta1;
+  s.beta2 = p->beta2;
+  s.epsilon = p->epsilon;
+  s.discount = p->discount;
+  s.s = (char *)train_get(h, ok, B * row);
+  s.s2 = (char *)train_get(h, ok, B * row);
+  s.a = (double *)train_get(h, ok, B * 4 * sizeof(double));
+  s.r = (double *)train_get(h, ok, B * sizeof(double));
+  s.w = (double *)train_get(h, ok, B * sizeof(double));
+  s.u = (double *)train_get(h, ok, B * sizeof(double));
+  s.done = (uint8_t *)train_get(h, ok, B);
+  s.idx = (int64_t *)train_get(h, ok, B * sizeof(int64_t));
+  s.td = (double *)train_get(h, ok, B * sizeof(double));
+  s.prio = (double *)train_get(h, ok, B * sizeof(double));
+  return s;
+}
+
+// One network's view of a trainer: s, and the network's own Adam state, buffers, counters and,
+// with `target`, a target that starts as a copy of the network as it is now.
+static Train train_view(aigar_handle *h, bool &ok, const Train &s, const Net &c, double lr, bool target) {
+  const size_t B = (size_t)s.batch;
+  Train v = s;
+  v.lr = lr;
+  for (int l = 0; l < c.n_layers; l++) {
+    const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
+    if (target) {
+      v.tw[l] = (float *)train_get(h, ok, nw);
+      v.tb[l] = (float *)train_get(h, ok, op * sizeof(float));
+    }
+    v.mw[l] = (float *)train_get(h, ok, nw);
+    v.mb[l] = (float *)train_get(h, ok, op * sizeof(float));
+    v.vw[l] = (float *)train_get(h, ok, nw);
+    v.vb[l] = (float *)train_get(h, ok, op * sizeof(float));
+    v.tile0[l + 1] = v.tile0[l] + (c.in[l] + 15) / 16 * (int)(op / 16);
+    if (ok && target) {
+      (void)hipMemcpyAsync(v.tw[l], c.w[l], nw, hipMemcpyDeviceToDevice, h->stream);
+      (void)hipMemcpyAsync(v.tb[l], c.b[l], op * sizeof(float), hipMemcpyDeviceToDevice, h->stream);
+    }
   }
+  const size_t n_out = (size_t)c.out[c.n_layers - 1];
+  v.q = (double *)train_get(h, ok, B * n_out * sizeof(double));
+  if (target) v.q2 = (double *)train_get(h, ok, B * n_out * sizeof(double));
+  v.hsave = (float *)train_get(h, ok, (size_t)std::max(c.n_layers - 1, 1) * v.bpad * kNetMaxUnits * sizeof(float));
+  v.delta = (float *)train_get(h, ok, (size_t)c.n_layers * v.bpad * kNetMaxUnits * sizeof(float));
+  v.ctl = (TrainCtl *)train_get(h, ok, sizeof(TrainCtl));
+  return v;
+}
+
+// The launches that every trainer's step is made of, on stream s.  The mini-batch into a view's
+// staging rows (replay.inc):
+static void launch_draw_fetch(aigar_handle *h, hipStream_t s, const Train &v, int has_u) {
+  const int B = v.batch;
+  hipLaunchKernelGGL(k_exp_draw, dim3((B + 255) / 256), dim3(256), 0, s, h->exp, B, has_u ? v.u : (const double *)nullptr, v.w,
+                     v.idx);
+  launch_exp_fetch(h, s, v.idx, B, v.s, v.a, v.r, v.s2, v.done, 0);
+}
+// n with the weights of view v's target
+static Net target_net(Net n, const Train &v) {
+  for (int l = 0; l < n.n_layers; l++) {
+    n.w[l] = v.tw[l];
+    n.b[l] = v.tb[l];
+  }
+  return n;
+}
+// n on the B rows x of its x_dtype, every hidden layer's activations kept (net.inc)
+static void launch_net_save(hipStream_t s, const Net &n, int B, const char *x, double *y, float *hsave) {
+  const dim3 rows16((unsigned)((B + kNetRows - 1) / kNetRows)), net_block(64 * kNetWaves);
+  if (n.x_dtype == 0) hipLaunchKernelGGL(k_net_save<double>, rows16, net_block, 0, s, n, (const double *)x, B, y, hsave);
+  else hipLaunchKernelGGL(k_net_save<float>, rows16, net_block, 0, s, n, (const float *)x, B, y, hsave);
+}
+// view v's output delta back through n's layers, then every layer's gradient and Adam in place (train.inc)
+static void launch_net_update(hipStream_t s, const Net &n, const Train &v) {
+  if (n.n_layers > 1)
+    hipLaunchKernelGGL(k_net_bwd, dim3((unsigned)(v.bpad / kNetRows)), dim3(64 * kNetWaves), 0, s, n, v);
+  if (n.x_dtype == 0) hipLaunchKernelGGL(k_net_grad_adam<double>, dim3(v.tile0[n.n_layers]), dim3(64), 0, s, n, v);
+  else hipLaunchKernelGGL(k_net_grad_adam<float>, dim3(v.tile0[n.n_layers]), dim3(64), 0, s, n, v);
+}
+
+// aigar_*_step after its need_*: n_steps replays of the kind's step graph, each after the copy of
+// its draws into the view's u row.
+static int trainer_step(aigar_handle *h, const char *who, int kind, int n_steps, const double *u, const Train &v,
+                        void (*launch)(aigar_handle *, hipStream_t, int)) {
+  if (n_steps < 1) return fail("%s: n_steps = %d is below 1", who, n_steps);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  TrainKey k;
+  key_clear(k);
+  k.kind = kind;
+  k.has_u = u ? 1 : 0;
+  const bool graph = h->use_graph;
+  if (graph && !h->train.ensure(h, k, [&](hipStream_t cs) { launch(h, cs, k.has_u); }))
+    return fail("%s: graph capture failed", who);
+  Mark m(h, who);
+  const size_t B = (size_t)v.batch;
+  for (int i = 0; i < n_steps; i++) {
+    if (u) HIPCHK(hipMemcpyAsync(v.u, u + (size_t)i * B, B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (graph) HIPCHK(h->train.launch(h));
+    else launch(h, h->stream, k.has_u);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// aigar_*_td: the last drawn step's TD errors and memory indices (stream-ordered copies)
+static int trainer_td(aigar_handle *h, const Train &v, double *td, int64_t *idx) {
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const size_t B = (size_t)v.batch;
+  if (td) HIPCHK(hipMemcpyAsync(td, v.td, B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  if (idx) HIPCHK(hipMemcpyAsync(idx, v.idx, B * sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream));
+  return 0;
+}
+
+// aigar_*_sync_target: view v's target <- its network c, the padded copies whole
+static int target_copy(aigar_handle *h, const Net &c, const Train &v) {
+  for (int l = 0; l < c.n_layers; l++) {
+    const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
+    HIPCHK(hipMemcpyAsync(v.tw[l], c.w[l], nw, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(v.tb[l], c.b[l], op * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  }
+  return 0;
+}
+
+// aigar_*_reset: view v's Adam state to zero
+static int adam_clear(aigar_handle *h, const Net &c, const Train &v) {
+  for (int l = 0; l < c.n_layers; l++) {
+    const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
+    HIPCHK(hipMemsetAsync(v.mw[l], 0, nw, h->stream));
+    HIPCHK(hipMemsetAsync(v.vw[l], 0, nw, h->stream));
+    HIPCHK(hipMemsetAsync(v.mb[l], 0, op * sizeof(float), h->stream));
+    HIPCHK(hipMemsetAsync(v.vb[l], 0, op * sizeof(float), h->stream));
+  }
+  return 0;
+}
+
+__global__ void k_train_clear(TrainCtl *ctl, int target) {  // target: the copy was made; else Adam starts over
+  if (target) ctl->since = 0;
+  else ctl->t = 0;
+}
+
+// ------------------------------------------------------------ Q-learning trainer
+extern "C" int aigar_train_config(aigar_handle *h, const aigar_train_params *p) {
+  const char *who = "train_config";
+  if (p && (check_train_sizes(who, p) || check_positive(who, "lr", p->lr) || check_train_adam(who, p))) return -1;
   if (!h) return fail("null handle");
   if (p) {
-    if (h->d.tiled) return fail("train_config: a tiled handle has no training");
-    if (need_net(h, "train_config")) return -1;
-    if (h->conv.n_conv) return fail("train_config: a network with a conv part is not trained on the device");
+    if (check_train_net(h, who)) return -1;
     if (h->net.out_act != AIGAR_ACT_LINEAR)
       return fail("train_config: the network's head is %s, Q-learning needs a linear head", net_act_name(h->net.out_act));
-    if (need_exp(h, "train_config")) return -1;
-    if (need_dec(h, "train_config")) return -1;
+    if (need_exp(h, who)) return -1;
+    if (need_dec(h, who)) return -1;
     if (h->dec.n_out != h->net.out[h->net.n_layers - 1])
       return fail("train_config: the network has %d outputs, the action selection %d", h->net.out[h->net.n_layers - 1],
                   h->dec.n_out);
-    if (h->net.in[0] != h->exp.L)
-      return fail("train_config: the network has %d inputs, the memory's states %d values", h->net.in[0], h->exp.L);
+    if (check_train_widths(h, who)) return -1;
   }
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipStreamSynchronize(h->stream));
-  train_free(h);
+  if (p || h->trn.batch) trainer_free(h);  // (a null p turns off this trainer, not another)
   if (!p) return 0;
-  const Net &c = h->net;
-  const Exp &e = h->exp;
-  Train t;
-  t.batch = p->batch;
-  t.bpad = (p->batch + kNetRows - 1) / kNetRows * kNetRows;
-  t.min_size = p->min_size;
-  t.target_steps = p->target_steps;
-  t.lr = p->lr;
-  t.beta1 = p->beta1;
-  t.beta2 = p->beta2;
-  t.epsilon = p->epsilon;
-  t.discount = p->discount;
   bool ok = true;
-  auto get = [&](size_t bytes) -> void * {
-    if (!ok) return nullptr;
-    void *q = h->trn_mem.alloc(bytes, true, h->stream);
-    ok = q != nullptr;
-    return q;
-  };
-  const size_t B = (size_t)t.batch, n_out = (size_t)c.out[c.n_layers - 1];
-  for (int l = 0; l < c.n_layers; l++) {
-    const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
-    t.tw[l] = (float *)get(nw);
-    t.tb[l] = (float *)get(op * sizeof(float));
-    t.mw[l] = (float *)get(nw);
-    t.mb[l] = (float *)get(op * sizeof(float));
-    t.vw[l] = (float *)get(nw);
-    t.vb[l] = (float *)get(op * sizeof(float));
-    t.tile0[l + 1] = t.tile0[l] + (c.in[l] + 15) / 16 * (int)(op / 16);
-    if (ok) {
-      (void)hipMemcpyAsync(t.tw[l], c.w[l], nw, hipMemcpyDeviceToDevice, h->stream);
-      (void)hipMemcpyAsync(t.tb[l], c.b[l], op * sizeof(float), hipMemcpyDeviceToDevice, h->stream);
-    }
-  }
-  const size_t row = (size_t)e.L * e.esz;
-  t.s = (char *)get(B * row);
-  t.s2 = (char *)get(B * row);
-  t.a = (double *)get(B * 4 * sizeof(double));
-  t.r = (double *)get(B * sizeof(double));
-  t.w = (double *)get(B * sizeof(double));
-  t.u = (double *)get(B * sizeof(double));
-  t.done = (uint8_t *)get(B);
-  t.idx = (int64_t *)get(B * sizeof(int64_t));
-  t.q = (double *)get(B * n_out * sizeof(double));
-  t.q2 = (double *)get(B * n_out * sizeof(double));
-  t.td = (double *)get(B * sizeof(double));
-  t.prio = (double *)get(B * sizeof(double));
-  t.hsave = (float *)get((size_t)std::max(c.n_layers - 1, 1) * t.bpad * kNetMaxUnits * sizeof(float));
-  t.delta = (float *)get((size_t)c.n_layers * t.bpad * kNetMaxUnits * sizeof(float));
-  t.ctl = (TrainCtl *)get(sizeof(TrainCtl));
+  const Train t = train_view(h, ok, train_shared(h, ok, p), h->net, p->lr, true);
   if (!ok) {
     h->trn_mem.release();
     return fail("train_config: out of device memory");
@@ -2422,52 +2558,22 @@ extern "C" int aigar_train_config(aigar_handle *h, const aigar_train_params *p) 
 static void launch_train_step(aigar_handle *h, hipStream_t s, int has_u) {
   const Train &t = h->trn;
   const Exp &e = h->exp;
-  Net on = h->net, tg = h->net;
-  on.x_dtype = tg.x_dtype = e.dtype;
-  for (int l = 0; l < tg.n_layers; l++) {
-    tg.w[l] = t.tw[l];
-    tg.b[l] = t.tb[l];
-  }
-  const int B = t.batch, n_out = on.out[on.n_layers - 1];
-  const dim3 rows16((unsigned)(t.bpad / kNetRows)), net_block(64 * kNetWaves);
-  hipLaunchKernelGGL(k_exp_draw, dim3((B + 255) / 256), dim3(256), 0, s, e, B, has_u ? t.u : (const double *)nullptr, t.w,
-                     t.idx);
-  if (e.dtype == 0) {
-    hipLaunchKernelGGL(k_exp_fetch<uint64_t>, dim3(B), dim3(256), 0, s, e, t.idx, t.s, t.a, t.r, t.s2, t.done, 0);
-    hipLaunchKernelGGL(k_net_save<double>, rows16, net_block, 0, s, on, (const double *)t.s, B, t.q, t.hsave);
-  } else {
-    hipLaunchKernelGGL(k_exp_fetch<uint32_t>, dim3(B), dim3(256), 0, s, e, t.idx, t.s, t.a, t.r, t.s2, t.done, 0);
-    hipLaunchKernelGGL(k_net_save<float>, rows16, net_block, 0, s, on, (const float *)t.s, B, t.q, t.hsave);
-  }
+  Net on = h->net;
+  on.x_dtype = e.dtype;
+  const Net tg = target_net(on, t);
+  const int B = t.batch;
+  launch_draw_fetch(h, s, t, has_u);
+  launch_net_save(s, on, B, t.s, t.q, t.hsave);
   launch_net(s, tg, t.s2, B, t.q2, nullptr, nullptr);
-  hipLaunchKernelGGL(k_td, dim3(1), dim3(kTrainMaxBatch), 0, s, t, e, h->d, on.n_layers, n_out);
-  if (on.n_layers > 1) hipLaunchKernelGGL(k_net_bwd, rows16, net_block, 0, s, on, t);
-  if (e.dtype == 0) hipLaunchKernelGGL(k_net_grad_adam<double>, dim3(t.tile0[on.n_layers]), dim3(64), 0, s, on, t);
-  else hipLaunchKernelGGL(k_net_grad_adam<float>, dim3(t.tile0[on.n_layers]), dim3(64), 0, s, on, t);
+  hipLaunchKernelGGL(k_td, dim3(1), dim3(kTrainMaxBatch), 0, s, t, e, h->d, on.n_layers, on.out[on.n_layers - 1]);
+  launch_net_update(s, on, t);
   if (e.prio) hipLaunchKernelGGL(k_exp_update, dim3(1), dim3(kExpPlanThreads), 0, s, e, t.idx, t.prio, B);
   hipLaunchKernelGGL(k_train_tail, dim3(64), dim3(256), 0, s, on, t);
 }
 
 extern "C" int aigar_train_step(aigar_handle *h, int n_steps, const double *u) {
   if (need_trn(h, "train_step")) return -1;
-  if (n_steps < 1) return fail("train_step: n_steps = %d is below 1", n_steps);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  TrainKey k;
-  key_clear(k);
-  k.has_u = u ? 1 : 0;
-  const bool graph = h->use_graph;
-  if (graph && !h->train.ensure(h, k, [&](hipStream_t cs) { launch_train_step(h, cs, k.has_u); }))
-    return fail("train_step: graph capture failed");
-  Mark m(h, "train_step");
-  for (int i = 0; i < n_steps; i++) {
-    if (u)
-      HIPCHK(hipMemcpyAsync(h->trn.u, u + (size_t)i * h->trn.batch, (size_t)h->trn.batch * sizeof(double),
-                            hipMemcpyDeviceToDevice, h->stream));
-    if (graph) HIPCHK(h->train.launch(h));
-    else launch_train_step(h, h->stream, k.has_u);
-  }
-  HIPCHK(hipGetLastError());
-  return 0;
+  return trainer_step(h, "train_step", kTrainQ, n_steps, u, h->trn, launch_train_step);
 }
 
 extern "C" int aigar_train_info(aigar_handle *h, int64_t info[4]) {
@@ -2486,27 +2592,13 @@ extern "C" int aigar_train_info(aigar_handle *h, int64_t info[4]) {
 
 extern "C" int aigar_train_td(aigar_handle *h, double *td, int64_t *idx) {
   if (need_trn(h, "train_td")) return -1;
-  HIPCHK(hipSetDevice(h->cfg.device));
-  const size_t B = (size_t)h->trn.batch;
-  if (td) HIPCHK(hipMemcpyAsync(td, h->trn.td, B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  if (idx) HIPCHK(hipMemcpyAsync(idx, h->trn.idx, B * sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream));
-  return 0;
-}
-
-__global__ void k_train_clear(TrainCtl *ctl, int target) {  // target: the copy was made; else Adam starts over
-  if (target) ctl->since = 0;
-  else ctl->t = 0;
+  return trainer_td(h, h->trn, td, idx);
 }
 
 extern "C" int aigar_train_sync_target(aigar_handle *h) {
   if (need_trn(h, "train_sync_target")) return -1;
   HIPCHK(hipSetDevice(h->cfg.device));
-  const Net &c = h->net;
-  for (int l = 0; l < c.n_layers; l++) {
-    const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
-    HIPCHK(hipMemcpyAsync(h->trn.tw[l], c.w[l], nw, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->trn.tb[l], c.b[l], op * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-  }
+  if (target_copy(h, h->net, h->trn)) return -1;
   hipLaunchKernelGGL(k_train_clear, dim3(1), dim3(1), 0, h->stream, h->trn.ctl, 1);
   HIPCHK(hipGetLastError());
   return 0;
@@ -2515,42 +2607,18 @@ extern "C" int aigar_train_sync_target(aigar_handle *h) {
 extern "C" int aigar_train_reset(aigar_handle *h) {
   if (need_trn(h, "train_reset")) return -1;
   HIPCHK(hipSetDevice(h->cfg.device));
-  const Net &c = h->net;
-  const Train &t = h->trn;
-  for (int l = 0; l < c.n_layers; l++) {
-    const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
-    HIPCHK(hipMemsetAsync(t.mw[l], 0, nw, h->stream));
-    HIPCHK(hipMemsetAsync(t.vw[l], 0, nw, h->stream));
-    HIPCHK(hipMemsetAsync(t.mb[l], 0, op * sizeof(float), h->stream));
-    HIPCHK(hipMemsetAsync(t.vb[l], 0, op * sizeof(float), h->stream));
-  }
-  hipLaunchKernelGGL(k_train_clear, dim3(1), dim3(1), 0, h->stream, t.ctl, 0);
+  if (adam_clear(h, h->net, h->trn)) return -1;
+  hipLaunchKernelGGL(k_train_clear, dim3(1), dim3(1), 0, h->stream, h->trn.ctl, 0);
   HIPCHK(hipGetLastError());
   return 0;
 }
 
 // ------------------------------------------------------------ CACLA: the critic and the trainer
-static int need_crit(aigar_handle *h, const char *who) {
-  return need(h, h && h->crit.n_layers, who, "no critic is configured (aigar_critic_config)");
-}
-static int need_act(aigar_handle *h, const char *who) {
-  return need(h, h && h->act.batch, who, "no CACLA training is configured (aigar_actrain_config)");
-}
-
 // aigar_critic_config (V(s): q false) and aigar_qcritic_config (Q(s, a): the rows are [state, action])
 static int critic_config(aigar_handle *h, const aigar_net_params *p, bool q) {
   const char *who = q ? "qcritic_config" : "critic_config";
   if (p) {  // (before the handle: a bad set has its own message)
-    if (p->n_layers < 1 || p->n_layers > kNetMaxLayers)
-      return fail("%s: n_layers = %d is outside 1..%d", who, p->n_layers, kNetMaxLayers);
-    if (p->n_in < 1 || p->n_in > kNetMaxIn) return fail("%s: n_in = %d is outside 1..%d", who, p->n_in, kNetMaxIn);
-    for (int l = 0; l < p->n_layers; l++)
-      if (p->units[l] < 1 || p->units[l] > kNetMaxUnits)
-        return fail("%s: layer %d has %d units, outside 1..%d", who, l, p->units[l], kNetMaxUnits);
-    if (p->x_dtype != 0 && p->x_dtype != 1) return fail("%s: x_dtype must be 0 (float64) or 1 (float32)", who);
-    if (p->hidden_act != AIGAR_ACT_RELU && p->hidden_act != AIGAR_ACT_LINEAR)
-      return fail("%s: hidden activation %d (%s) is not supported: relu or linear", who, p->hidden_act,
-                  net_act_name(p->hidden_act));
+    if (net_shape_check(who, p)) return -1;
     if (p->units[p->n_layers - 1] != 1 || p->out_act != AIGAR_ACT_LINEAR)
       return fail("%s: the head has %d units with activation %d (%s), %s is one linear unit", who,
                   p->units[p->n_layers - 1], p->out_act, net_act_name(p->out_act), q ? "Q(s, a)" : "V(s)");
@@ -2606,26 +2674,7 @@ extern "C" int aigar_qcritic_config(aigar_handle *h, const aigar_net_params *p) 
 
 extern "C" int aigar_critic_set_weights(aigar_handle *h, int layer, const float *W, const float *b, int on_device) {
   if (need_crit(h, "critic_set_weights")) return -1;
-  const Net &c = h->crit;
-  if (layer < 0 || layer >= c.n_layers)
-    return fail("critic_set_weights: layer %d is outside 0..%d", layer, c.n_layers - 1);
-  if (!W || !b) return fail("critic_set_weights: null argument");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  const int in = c.in[layer], out = c.out[layer];
-  const size_t nw = (size_t)in * out;
-  if (!on_device) {
-    HIPCHK(hipMemcpyAsync(h->crit_stage, W, nw * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->crit_stage + nw, b, (size_t)out * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    W = h->crit_stage;
-    b = h->crit_stage + nw;
-  }
-  const int ip = net_in_pad(in), op = net_out_pad(out);
-  const size_t n = (size_t)ip * op;
-  hipLaunchKernelGGL(k_net_pack, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, h->stream, W, b,
-                     c.w[layer], c.b[layer], in, out, ip, op);
-  HIPCHK(hipGetLastError());
-  if (!on_device) HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's arrays are read, the staging is free)
-  return 0;
+  return set_dense_weights(h, "critic_set_weights", h->crit, h->crit_stage, layer, W, b, on_device);
 }
 
 extern "C" int aigar_critic_forward(aigar_handle *h, const void *x, int x_dtype, int rows, double *out) {
@@ -2641,125 +2690,47 @@ extern "C" int aigar_critic_forward(aigar_handle *h, const void *x, int x_dtype,
   return 0;
 }
 
-// One network's view of an actor-critic trainer (actrain.inc, dpg.inc): s, the settings and the
-// staged batch that the views share, and the network's own Adam state, buffers, counters and,
-// with `target`, a target that starts as a copy of the network as it is now.
-static Train train_view(aigar_handle *h, DevBlock &mem, bool &ok, const Train &s, const Net &c, double lr, bool target) {
-  auto get = [&](size_t bytes) -> void * {
-    if (!ok) return nullptr;
-    void *q = mem.alloc(bytes, true, h->stream);
-    ok = q != nullptr;
-    return q;
-  };
-  const size_t B = (size_t)s.batch;
-  Train v = s;
-  v.lr = lr;
-  for (int l = 0; l < c.n_layers; l++) {
-    const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
-    if (target) {
-      v.tw[l] = (float *)get(nw);
-      v.tb[l] = (float *)get(op * sizeof(float));
-    }
-    v.mw[l] = (float *)get(nw);
-    v.mb[l] = (float *)get(op * sizeof(float));
-    v.vw[l] = (float *)get(nw);
-    v.vb[l] = (float *)get(op * sizeof(float));
-    v.tile0[l + 1] = v.tile0[l] + (c.in[l] + 15) / 16 * (int)(op / 16);
-    if (ok && target) {
-      (void)hipMemcpyAsync(v.tw[l], c.w[l], nw, hipMemcpyDeviceToDevice, h->stream);
-      (void)hipMemcpyAsync(v.tb[l], c.b[l], op * sizeof(float), hipMemcpyDeviceToDevice, h->stream);
-    }
-  }
-  const size_t n_out = (size_t)c.out[c.n_layers - 1];
-  v.q = (double *)get(B * n_out * sizeof(double));
-  if (target) v.q2 = (double *)get(B * n_out * sizeof(double));
-  v.hsave = (float *)get((size_t)std::max(c.n_layers - 1, 1) * v.bpad * kNetMaxUnits * sizeof(float));
-  v.delta = (float *)get((size_t)c.n_layers * v.bpad * kNetMaxUnits * sizeof(float));
-  v.ctl = (TrainCtl *)get(sizeof(TrainCtl));
-  return v;
-}
-
 extern "C" int aigar_actrain_config(aigar_handle *h, const aigar_actrain_params *p) {
-  if (p) {  // (before the handle: a bad set has its own message)
-    const double inf = __builtin_inf();
-    if (p->batch < 1 || p->batch > kTrainMaxBatch)
-      return fail("actrain_config: batch = %d is outside 1..%d", p->batch, kTrainMaxBatch);
-    if (p->min_size < 0) return fail("actrain_config: min_size = %d is negative", p->min_size);
-    if (p->target_steps < 0) return fail("actrain_config: target_steps = %d is negative", p->target_steps);
+  const char *who = "actrain_config";
+  if (p) {
+    if (check_train_sizes(who, p)) return -1;
     if (p->var_epochs < 0 || p->var_epochs > AIGAR_ACTRAIN_MAX_EPOCHS)
       return fail("actrain_config: var_epochs = %d is outside 0..%d", p->var_epochs, AIGAR_ACTRAIN_MAX_EPOCHS);
-    if (!(p->critic_lr > 0) || !(p->critic_lr < inf))
-      return fail("actrain_config: critic_lr = %g must be positive and finite", p->critic_lr);
-    if (!(p->actor_lr > 0) || !(p->actor_lr < inf))
-      return fail("actrain_config: actor_lr = %g must be positive and finite", p->actor_lr);
-    if (!(p->beta1 >= 0 && p->beta1 < 1)) return fail("actrain_config: beta1 = %g is outside [0, 1)", p->beta1);
-    if (!(p->beta2 >= 0 && p->beta2 < 1)) return fail("actrain_config: beta2 = %g is outside [0, 1)", p->beta2);
-    if (!(p->epsilon > 0) || !(p->epsilon < inf))
-      return fail("actrain_config: epsilon = %g must be positive and finite", p->epsilon);
-    if (!(p->discount >= 0 && p->discount <= 1)) return fail("actrain_config: discount = %g is outside [0, 1]", p->discount);
-    if (!(p->var_start > 0) || !(p->var_start < inf))
-      return fail("actrain_config: var_start = %g must be positive and finite", p->var_start);
-    if (!(p->var_beta >= 0 && p->var_beta < 1)) return fail("actrain_config: var_beta = %g is outside [0, 1)", p->var_beta);
+    if (check_positive(who, "critic_lr", p->critic_lr) || check_positive(who, "actor_lr", p->actor_lr) ||
+        check_train_adam(who, p) || check_positive(who, "var_start", p->var_start) ||
+        check_fraction(who, "var_beta", p->var_beta))
+      return -1;
   }
   if (!h) return fail("null handle");
   if (p) {
-    if (h->d.tiled) return fail("actrain_config: a tiled handle has no training");
-    if (need_net(h, "actrain_config")) return -1;
-    if (h->conv.n_conv) return fail("actrain_config: a network with a conv part is not trained on the device");
+    if (check_train_net(h, who)) return -1;
     if (h->net.out_act != AIGAR_ACT_SIGMOID)
       return fail("actrain_config: the network's head is %s, the CACLA actor needs a sigmoid head",
                   net_act_name(h->net.out_act));
     if (h->net.out[h->net.n_layers - 1] > 4)
       return fail("actrain_config: the actor has %d outputs, a stored action has at most 4", h->net.out[h->net.n_layers - 1]);
-    if (need_crit(h, "actrain_config")) return -1;
+    if (need_crit(h, who)) return -1;
     if (h->crit_q) return fail("actrain_config: the critic is Q(s, a) (aigar_qcritic_config), CACLA trains V(s)");
-    if (need_exp(h, "actrain_config")) return -1;
-    if (h->net.in[0] != h->exp.L)
-      return fail("actrain_config: the network has %d inputs, the memory's states %d values", h->net.in[0], h->exp.L);
+    if (need_exp(h, who)) return -1;
+    if (check_train_widths(h, who)) return -1;
   }
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipStreamSynchronize(h->stream));
-  actrain_free(h);
+  if (p || h->act.batch) trainer_free(h);  // (a null p turns off this trainer, not another)
   if (!p) return 0;
-  const Exp &e = h->exp;
   ACTrain t;
   t.batch = p->batch;
   t.var_epochs = p->var_epochs;
   t.var_start = p->var_start;
   t.var_beta = p->var_beta;
   bool ok = true;
-  auto get = [&](size_t bytes) -> void * {
-    if (!ok) return nullptr;
-    void *q = h->act_mem.alloc(bytes, true, h->stream);
-    ok = q != nullptr;
-    return q;
-  };
-  const size_t B = (size_t)p->batch, row = (size_t)e.L * e.esz;
-  Train s;  // what the two views share: the settings and the staged batch
-  s.batch = p->batch;
-  s.bpad = (p->batch + kNetRows - 1) / kNetRows * kNetRows;
-  s.min_size = p->min_size;
-  s.target_steps = p->target_steps;
-  s.beta1 = p->beta1;
-  s.beta2 = p->beta2;
-  s.epsilon = p->epsilon;
-  s.discount = p->discount;
-  s.s = (char *)get(B * row);
-  s.s2 = (char *)get(B * row);
-  s.a = (double *)get(B * 4 * sizeof(double));
-  s.r = (double *)get(B * sizeof(double));
-  s.w = (double *)get(B * sizeof(double));
-  s.u = (double *)get(B * sizeof(double));
-  s.done = (uint8_t *)get(B);
-  s.idx = (int64_t *)get(B * sizeof(int64_t));
-  s.td = (double *)get(B * sizeof(double));
-  s.prio = (double *)get(B * sizeof(double));
-  t.c = train_view(h, h->act_mem, ok, s, h->crit, p->critic_lr, true);
-  t.a = train_view(h, h->act_mem, ok, s, h->net, p->actor_lr, false);
-  t.count = (int32_t *)get(B * sizeof(int32_t));
-  t.x = (ACtl *)get(sizeof(ACtl));
+  const Train s = train_shared(h, ok, p);
+  t.c = train_view(h, ok, s, h->crit, p->critic_lr, true);
+  t.a = train_view(h, ok, s, h->net, p->actor_lr, false);
+  t.count = (int32_t *)train_get(h, ok, (size_t)p->batch * sizeof(int32_t));
+  t.x = (ACtl *)train_get(h, ok, sizeof(ACtl));
   if (!ok) {
-    h->act_mem.release();
+    h->trn_mem.release();
     return fail("actrain_config: out of device memory");
   }
   hipLaunchKernelGGL(k_actrain_clear, dim3(1), dim3(1), 0, h->stream, t.c.ctl, t.a.ctl, t.x, t.var_start);
@@ -2773,59 +2744,27 @@ static void launch_actrain_step(aigar_handle *h, hipStream_t s, int has_u) {
   const ACTrain &t = h->act;
   const Train &c = t.c, &a = t.a;
   const Exp &e = h->exp;
-  Net cr = h->crit, tg = h->crit, ac = h->net;
-  cr.x_dtype = tg.x_dtype = ac.x_dtype = e.dtype;
-  for (int l = 0; l < tg.n_layers; l++) {
-    tg.w[l] = c.tw[l];
-    tg.b[l] = c.tb[l];
-  }
+  Net cr = h->crit, ac = h->net;
+  cr.x_dtype = ac.x_dtype = e.dtype;
+  const Net tg = target_net(cr, c);
   const int B = t.batch, n_out = ac.out[ac.n_layers - 1];
-  const dim3 rows16((unsigned)(c.bpad / kNetRows)), net_block(64 * kNetWaves);
-  auto save = [&](const Net &n, const Train &v) {
-    if (e.dtype == 0) hipLaunchKernelGGL(k_net_save<double>, rows16, net_block, 0, s, n, (const double *)v.s, B, v.q, v.hsave);
-    else hipLaunchKernelGGL(k_net_save<float>, rows16, net_block, 0, s, n, (const float *)v.s, B, v.q, v.hsave);
-  };
-  auto update = [&](const Net &n, const Train &v) {
-    if (n.n_layers > 1) hipLaunchKernelGGL(k_net_bwd, rows16, net_block, 0, s, n, v);
-    if (e.dtype == 0) hipLaunchKernelGGL(k_net_grad_adam<double>, dim3(v.tile0[n.n_layers]), dim3(64), 0, s, n, v);
-    else hipLaunchKernelGGL(k_net_grad_adam<float>, dim3(v.tile0[n.n_layers]), dim3(64), 0, s, n, v);
-  };
-  hipLaunchKernelGGL(k_exp_draw, dim3((B + 255) / 256), dim3(256), 0, s, e, B, has_u ? c.u : (const double *)nullptr, c.w,
-                     c.idx);
-  if (e.dtype == 0) hipLaunchKernelGGL(k_exp_fetch<uint64_t>, dim3(B), dim3(256), 0, s, e, c.idx, c.s, c.a, c.r, c.s2, c.done, 0);
-  else hipLaunchKernelGGL(k_exp_fetch<uint32_t>, dim3(B), dim3(256), 0, s, e, c.idx, c.s, c.a, c.r, c.s2, c.done, 0);
-  save(cr, c);
+  launch_draw_fetch(h, s, c, has_u);
+  launch_net_save(s, cr, B, c.s, c.q, c.hsave);
   launch_net(s, tg, c.s2, B, c.q2, nullptr, nullptr);
   hipLaunchKernelGGL(k_td_v, dim3(1), dim3(kTrainMaxBatch), 0, s, t, e, h->d, cr.n_layers);
-  update(cr, c);
+  launch_net_update(s, cr, c);
   if (e.prio) hipLaunchKernelGGL(k_exp_update, dim3(1), dim3(kExpPlanThreads), 0, s, e, c.idx, c.prio, B);
   for (int ep = 0; ep < std::max(t.var_epochs, 1); ep++) {
-    save(ac, a);
+    launch_net_save(s, ac, B, a.s, a.q, a.hsave);
     hipLaunchKernelGGL(k_actor_delta, dim3(1), dim3(kTrainMaxBatch), 0, s, t, h->d, ep, ac.n_layers, n_out);
-    update(ac, a);
+    launch_net_update(s, ac, a);
   }
   hipLaunchKernelGGL(k_train_tail, dim3(64), dim3(256), 0, s, cr, c);
 }
 
 extern "C" int aigar_actrain_step(aigar_handle *h, int n_steps, const double *u) {
   if (need_act(h, "actrain_step")) return -1;
-  if (n_steps < 1) return fail("actrain_step: n_steps = %d is below 1", n_steps);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  TrainKey k;
-  key_clear(k);
-  k.has_u = u ? 1 : 0;
-  const bool graph = h->use_graph;
-  if (graph && !h->actrain.ensure(h, k, [&](hipStream_t cs) { launch_actrain_step(h, cs, k.has_u); }))
-    return fail("actrain_step: graph capture failed");
-  Mark m(h, "actrain_step");
-  const size_t B = (size_t)h->act.batch;
-  for (int i = 0; i < n_steps; i++) {
-    if (u) HIPCHK(hipMemcpyAsync(h->act.c.u, u + (size_t)i * B, B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    if (graph) HIPCHK(h->actrain.launch(h));
-    else launch_actrain_step(h, h->stream, k.has_u);
-  }
-  HIPCHK(hipGetLastError());
-  return 0;
+  return trainer_step(h, "actrain_step", kTrainCacla, n_steps, u, h->act.c, launch_actrain_step);
 }
 
 extern "C" int aigar_actrain_info(aigar_handle *h, int64_t info[8]) {
@@ -2851,12 +2790,9 @@ extern "C" int aigar_actrain_info(aigar_handle *h, int64_t info[8]) {
 
 extern "C" int aigar_actrain_td(aigar_handle *h, double *td, int64_t *idx, int32_t *count) {
   if (need_act(h, "actrain_td")) return -1;
-  HIPCHK(hipSetDevice(h->cfg.device));
   const ACTrain &t = h->act;
-  const size_t B = (size_t)t.batch;
-  if (td) HIPCHK(hipMemcpyAsync(td, t.c.td, B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  if (idx) HIPCHK(hipMemcpyAsync(idx, t.c.idx, B * sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream));
-  if (count) HIPCHK(hipMemcpyAsync(count, t.count, B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+  if (trainer_td(h, t.c, td, idx)) return -1;
+  if (count) HIPCHK(hipMemcpyAsync(count, t.count, (size_t)t.batch * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
   return 0;
 }
 
@@ -2874,14 +2810,8 @@ extern "C" int aigar_actrain_var(aigar_handle *h, double *var) {
 extern "C" int aigar_actrain_sync_target(aigar_handle *h) {
   if (need_act(h, "actrain_sync_target")) return -1;
   HIPCHK(hipSetDevice(h->cfg.device));
-  const Net &c = h->crit;
-  const Train &t = h->act.c;
-  for (int l = 0; l < c.n_layers; l++) {
-    const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
-    HIPCHK(hipMemcpyAsync(t.tw[l], c.w[l], nw, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(t.tb[l], c.b[l], op * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-  }
-  hipLaunchKernelGGL(k_train_clear, dim3(1), dim3(1), 0, h->stream, t.ctl, 1);
+  if (target_copy(h, h->crit, h->act.c)) return -1;
+  hipLaunchKernelGGL(k_train_clear, dim3(1), dim3(1), 0, h->stream, h->act.c.ctl, 1);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2890,17 +2820,7 @@ extern "C" int aigar_actrain_reset(aigar_handle *h) {
   if (need_act(h, "actrain_reset")) return -1;
   HIPCHK(hipSetDevice(h->cfg.device));
   const ACTrain &t = h->act;
-  for (int k = 0; k < 2; k++) {
-    const Net &c = k ? h->net : h->crit;
-    const Train &v = k ? t.a : t.c;
-    for (int l = 0; l < c.n_layers; l++) {
-      const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
-      HIPCHK(hipMemsetAsync(v.mw[l], 0, nw, h->stream));
-      HIPCHK(hipMemsetAsync(v.vw[l], 0, nw, h->stream));
-      HIPCHK(hipMemsetAsync(v.mb[l], 0, op * sizeof(float), h->stream));
-      HIPCHK(hipMemsetAsync(v.vb[l], 0, op * sizeof(float), h->stream));
-    }
-  }
+  if (adam_clear(h, h->crit, t.c) || adam_clear(h, h->net, t.a)) return -1;
   hipLaunchKernelGGL(k_actrain_clear, dim3(1), dim3(1), 0, h->stream, t.c.ctl, t.a.ctl, t.x, t.var_start);
   HIPCHK(hipGetLastError());
   return 0;
@@ -2908,46 +2828,30 @@ extern "C" int aigar_actrain_reset(aigar_handle *h) {
 
 // ------------------------------------------------------------ DPG: the Q(s, a) critic's trainer
 static_assert(sizeof(DPGTrain) + 2 * sizeof(Net) + sizeof(Dev) <= 4096, "k_dpg_tail's arguments");
-static int need_dpg(aigar_handle *h, const char *who) {
-  return need(h, h && h->dpg.batch, who, "no DPG training is configured (aigar_dpg_config)");
-}
 
 extern "C" int aigar_dpg_config(aigar_handle *h, const aigar_dpg_params *p) {
-  if (p) {  // (before the handle: a bad set has its own message)
-    const double inf = __builtin_inf();
-    if (p->batch < 1 || p->batch > kTrainMaxBatch)
-      return fail("dpg_config: batch = %d is outside 1..%d", p->batch, kTrainMaxBatch);
-    if (p->min_size < 0) return fail("dpg_config: min_size = %d is negative", p->min_size);
-    if (p->target_steps < 0) return fail("dpg_config: target_steps = %d is negative", p->target_steps);
+  const char *who = "dpg_config";
+  if (p) {
+    if (check_train_sizes(who, p)) return -1;
     if (p->reserved != 0) return fail("dpg_config: reserved = %d must be 0", p->reserved);
-    if (!(p->critic_lr > 0) || !(p->critic_lr < inf))
-      return fail("dpg_config: critic_lr = %g must be positive and finite", p->critic_lr);
-    if (!(p->actor_lr > 0) || !(p->actor_lr < inf))
-      return fail("dpg_config: actor_lr = %g must be positive and finite", p->actor_lr);
-    if (!(p->beta1 >= 0 && p->beta1 < 1)) return fail("dpg_config: beta1 = %g is outside [0, 1)", p->beta1);
-    if (!(p->beta2 >= 0 && p->beta2 < 1)) return fail("dpg_config: beta2 = %g is outside [0, 1)", p->beta2);
-    if (!(p->epsilon > 0) || !(p->epsilon < inf))
-      return fail("dpg_config: epsilon = %g must be positive and finite", p->epsilon);
-    if (!(p->discount >= 0 && p->discount <= 1)) return fail("dpg_config: discount = %g is outside [0, 1]", p->discount);
+    if (check_positive(who, "critic_lr", p->critic_lr) || check_positive(who, "actor_lr", p->actor_lr) ||
+        check_train_adam(who, p))
+      return -1;
     if (!(p->tau >= 0 && p->tau <= 1)) return fail("dpg_config: tau = %g is outside [0, 1]", p->tau);
-    if (!(fabs(p->q_increase) < inf)) return fail("dpg_config: q_increase = %g must be finite", p->q_increase);
+    if (!(fabs(p->q_increase) < __builtin_inf())) return fail("dpg_config: q_increase = %g must be finite", p->q_increase);
   }
   if (!h) return fail("null handle");
   if (p) {
-    if (h->d.tiled) return fail("dpg_config: a tiled handle has no training");
-    if (need_net(h, "dpg_config")) return -1;
-    if (h->conv.n_conv) return fail("dpg_config: a network with a conv part is not trained on the device");
-    if (need_crit(h, "dpg_config")) return -1;
+    if (check_train_net(h, who)) return -1;
+    if (need_crit(h, who)) return -1;
     if (!h->crit_q) return fail("dpg_config: the critic is V(s) (aigar_critic_config), DPG trains Q(s, a) (aigar_qcritic_config)");
-    if (need_exp(h, "dpg_config")) return -1;
-    if (h->net.in[0] != h->exp.L)
-      return fail("dpg_config: the network has %d inputs, the memory's states %d values", h->net.in[0], h->exp.L);
+    if (need_exp(h, who)) return -1;
+    if (check_train_widths(h, who)) return -1;
   }
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipStreamSynchronize(h->stream));
-  dpg_free(h);
+  if (p || h->dpg.batch) trainer_free(h);  // (a null p turns off this trainer, not another)
   if (!p) return 0;
-  const Exp &e = h->exp;
   DPGTrain t;
   t.batch = p->batch;
   t.n_s = h->net.in[0];
@@ -2957,45 +2861,21 @@ extern "C" int aigar_dpg_config(aigar_handle *h, const aigar_dpg_params *p) {
   t.keep = (float)(1.0 - p->tau);
   t.q_increase = p->q_increase;
   bool ok = true;
-  auto get = [&](size_t bytes) -> void * {
-    if (!ok) return nullptr;
-    void *q = h->dpg_mem.alloc(bytes, true, h->stream);
-    ok = q != nullptr;
-    return q;
-  };
-  const size_t B = (size_t)p->batch, row = (size_t)e.L * e.esz, xrow = (size_t)(t.n_s + t.n_act) * e.esz;
-  Train s;  // what the views share: the settings and the staged batch
-  s.batch = p->batch;
-  s.bpad = (p->batch + kNetRows - 1) / kNetRows * kNetRows;
-  s.min_size = p->min_size;
-  s.target_steps = p->target_steps;
-  s.beta1 = p->beta1;
-  s.beta2 = p->beta2;
-  s.epsilon = p->epsilon;
-  s.discount = p->discount;
-  s.s = (char *)get(B * row);
-  s.s2 = (char *)get(B * row);
-  s.a = (double *)get(B * 4 * sizeof(double));
-  s.r = (double *)get(B * sizeof(double));
-  s.w = (double *)get(B * sizeof(double));
-  s.u = (double *)get(B * sizeof(double));
-  s.done = (uint8_t *)get(B);
-  s.idx = (int64_t *)get(B * sizeof(int64_t));
-  s.td = (double *)get(B * sizeof(double));
-  s.prio = (double *)get(B * sizeof(double));
-  t.c = train_view(h, h->dpg_mem, ok, s, h->crit, p->critic_lr, true);
-  t.a = train_view(h, h->dpg_mem, ok, s, h->net, p->actor_lr, true);
-  t.c.s = (char *)get(B * xrow);  // (the critic's first layer reads the packed rows)
-  t.c.s2 = (char *)get(B * xrow);
-  t.xm = (char *)get(B * xrow);
-  t.xt = (char *)get(B * xrow);
-  t.mut = (double *)get(B * t.n_act * sizeof(double));
-  t.qm = (double *)get(B * sizeof(double));
-  t.qt = (double *)get(B * sizeof(double));
+  const size_t B = (size_t)p->batch, xrow = (size_t)(t.n_s + t.n_act) * h->exp.esz;
+  const Train s = train_shared(h, ok, p);
+  t.c = train_view(h, ok, s, h->crit, p->critic_lr, true);
+  t.a = train_view(h, ok, s, h->net, p->actor_lr, true);
+  t.c.s = (char *)train_get(h, ok, B * xrow);  // (the critic's first layer reads the packed rows)
+  t.c.s2 = (char *)train_get(h, ok, B * xrow);
+  t.xm = (char *)train_get(h, ok, B * xrow);
+  t.xt = (char *)train_get(h, ok, B * xrow);
+  t.mut = (double *)train_get(h, ok, B * t.n_act * sizeof(double));
+  t.qm = (double *)train_get(h, ok, B * sizeof(double));
+  t.qt = (double *)train_get(h, ok, B * sizeof(double));
   t.ca = t.c;
-  t.ca.ctl = (TrainCtl *)get(sizeof(TrainCtl));
+  t.ca.ctl = (TrainCtl *)train_get(h, ok, sizeof(TrainCtl));
   if (!ok) {
-    h->dpg_mem.release();
+    h->trn_mem.release();
     return fail("dpg_config: out of device memory");
   }
   HIPCHK(hipGetLastError());
@@ -3008,22 +2888,10 @@ static void launch_dpg_step(aigar_handle *h, hipStream_t s, int has_u) {
   const DPGTrain &t = h->dpg;
   const Train &c = t.c, &a = t.a, &ca = t.ca;
   const Exp &e = h->exp;
-  Net cr = h->crit, ct = h->crit, ac = h->net, at = h->net;
-  cr.x_dtype = ct.x_dtype = ac.x_dtype = at.x_dtype = e.dtype;
-  for (int l = 0; l < ct.n_layers; l++) {
-    ct.w[l] = c.tw[l];
-    ct.b[l] = c.tb[l];
-  }
-  for (int l = 0; l < at.n_layers; l++) {
-    at.w[l] = a.tw[l];
-    at.b[l] = a.tb[l];
-  }
+  Net cr = h->crit, ac = h->net;
+  cr.x_dtype = ac.x_dtype = e.dtype;
+  const Net ct = target_net(cr, c), at = target_net(ac, a);
   const int B = t.batch;
-  const dim3 rows16((unsigned)(c.bpad / kNetRows)), net_block(64 * kNetWaves);
-  auto save = [&](const Net &n, const char *x, double *y, float *hsave) {
-    if (e.dtype == 0) hipLaunchKernelGGL(k_net_save<double>, rows16, net_block, 0, s, n, (const double *)x, B, y, hsave);
-    else hipLaunchKernelGGL(k_net_save<float>, rows16, net_block, 0, s, n, (const float *)x, B, y, hsave);
-  };
   auto pack = [&](const char *s0, const double *a0, int st0, char *o0, const char *s1, const double *a1, int st1, char *o1) {
     if (e.dtype == 0)
       hipLaunchKernelGGL(k_sa_pack<double>, dim3(2 * B), dim3(64), 0, s, B, t.n_s, t.n_act, (const double *)s0, a0, st0,
@@ -3032,55 +2900,32 @@ static void launch_dpg_step(aigar_handle *h, hipStream_t s, int has_u) {
       hipLaunchKernelGGL(k_sa_pack<float>, dim3(2 * B), dim3(64), 0, s, B, t.n_s, t.n_act, (const float *)s0, a0, st0,
                          (float *)o0, (const float *)s1, a1, st1, (float *)o1);
   };
-  auto update = [&](const Net &n, const Train &v) {
-    if (n.n_layers > 1) hipLaunchKernelGGL(k_net_bwd, rows16, net_block, 0, s, n, v);
-    if (e.dtype == 0) hipLaunchKernelGGL(k_net_grad_adam<double>, dim3(v.tile0[n.n_layers]), dim3(64), 0, s, n, v);
-    else hipLaunchKernelGGL(k_net_grad_adam<float>, dim3(v.tile0[n.n_layers]), dim3(64), 0, s, n, v);
-  };
-  hipLaunchKernelGGL(k_exp_draw, dim3((B + 255) / 256), dim3(256), 0, s, e, B, has_u ? a.u : (const double *)nullptr, a.w,
-                     a.idx);
-  if (e.dtype == 0) hipLaunchKernelGGL(k_exp_fetch<uint64_t>, dim3(B), dim3(256), 0, s, e, a.idx, a.s, a.a, a.r, a.s2, a.done, 0);
-  else hipLaunchKernelGGL(k_exp_fetch<uint32_t>, dim3(B), dim3(256), 0, s, e, a.idx, a.s, a.a, a.r, a.s2, a.done, 0);
+  launch_draw_fetch(h, s, a, has_u);
   // the critic half
   launch_net(s, at, a.s2, B, a.q2, nullptr, nullptr);
   pack(a.s, a.a, 4, c.s, a.s2, a.q2, t.n_act, c.s2);
-  save(cr, c.s, c.q, c.hsave);
+  launch_net_save(s, cr, B, c.s, c.q, c.hsave);
   launch_net(s, ct, c.s2, B, c.q2, nullptr, nullptr);
   hipLaunchKernelGGL(k_td_q, dim3(1), dim3(kTrainMaxBatch), 0, s, c, e, h->d, cr.n_layers);
-  update(cr, c);
+  launch_net_update(s, cr, c);
   if (e.prio) hipLaunchKernelGGL(k_exp_update, dim3(1), dim3(kExpPlanThreads), 0, s, e, c.idx, c.prio, B);
   // the actor half
-  save(ac, a.s, a.q, a.hsave);
+  launch_net_save(s, ac, B, a.s, a.q, a.hsave);
   launch_net(s, at, a.s, B, t.mut, nullptr, nullptr);
   pack(a.s, a.q, t.n_act, t.xm, a.s, t.mut, t.n_act, t.xt);
-  save(cr, t.xm, t.qm, ca.hsave);  // (the critic's update is done: its buffers serve the actor pass)
+  launch_net_save(s, cr, B, t.xm, t.qm, ca.hsave);  // (the critic's update is done: its buffers serve the actor pass)
   launch_net(s, ct, t.xt, B, t.qt, nullptr, nullptr);
   hipLaunchKernelGGL(k_dpg_delta, dim3(1), dim3(kTrainMaxBatch), 0, s, t, h->d, cr.n_layers);
-  if (cr.n_layers > 1) hipLaunchKernelGGL(k_net_bwd, rows16, net_block, 0, s, cr, ca);
+  if (cr.n_layers > 1)
+    hipLaunchKernelGGL(k_net_bwd, dim3((unsigned)(c.bpad / kNetRows)), dim3(64 * kNetWaves), 0, s, cr, ca);
   hipLaunchKernelGGL(k_net_bwd_in, dim3(1), dim3(64 * (c.bpad / kNetRows)), 0, s, cr, t, h->d, ac.n_layers);
-  update(ac, a);
+  launch_net_update(s, ac, a);
   hipLaunchKernelGGL(k_dpg_tail, dim3(64), dim3(256), 0, s, cr, ac, t);
 }
 
 extern "C" int aigar_dpg_step(aigar_handle *h, int n_steps, const double *u) {
   if (need_dpg(h, "dpg_step")) return -1;
-  if (n_steps < 1) return fail("dpg_step: n_steps = %d is below 1", n_steps);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  TrainKey k;
-  key_clear(k);
-  k.has_u = u ? 1 : 0;
-  const bool graph = h->use_graph;
-  if (graph && !h->dpgs.ensure(h, k, [&](hipStream_t cs) { launch_dpg_step(h, cs, k.has_u); }))
-    return fail("dpg_step: graph capture failed");
-  Mark m(h, "dpg_step");
-  const size_t B = (size_t)h->dpg.batch;
-  for (int i = 0; i < n_steps; i++) {
-    if (u) HIPCHK(hipMemcpyAsync(h->dpg.a.u, u + (size_t)i * B, B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    if (graph) HIPCHK(h->dpgs.launch(h));
-    else launch_dpg_step(h, h->stream, k.has_u);
-  }
-  HIPCHK(hipGetLastError());
-  return 0;
+  return trainer_step(h, "dpg_step", kTrainDpg, n_steps, u, h->dpg.a, launch_dpg_step);
 }
 
 extern "C" int aigar_dpg_info(aigar_handle *h, int64_t info[8]) {
@@ -3102,25 +2947,13 @@ extern "C" int aigar_dpg_info(aigar_handle *h, int64_t info[8]) {
 
 extern "C" int aigar_dpg_td(aigar_handle *h, double *td, int64_t *idx) {
   if (need_dpg(h, "dpg_td")) return -1;
-  HIPCHK(hipSetDevice(h->cfg.device));
-  const size_t B = (size_t)h->dpg.batch;
-  if (td) HIPCHK(hipMemcpyAsync(td, h->dpg.c.td, B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  if (idx) HIPCHK(hipMemcpyAsync(idx, h->dpg.c.idx, B * sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream));
-  return 0;
+  return trainer_td(h, h->dpg.c, td, idx);
 }
 
 extern "C" int aigar_dpg_sync_target(aigar_handle *h) {
   if (need_dpg(h, "dpg_sync_target")) return -1;
   HIPCHK(hipSetDevice(h->cfg.device));
-  for (int k = 0; k < 2; k++) {
-    const Net &c = k ? h->net : h->crit;
-    const Train &t = k ? h->dpg.a : h->dpg.c;
-    for (int l = 0; l < c.n_layers; l++) {
-      const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
-      HIPCHK(hipMemcpyAsync(t.tw[l], c.w[l], nw, hipMemcpyDeviceToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(t.tb[l], c.b[l], op * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    }
-  }
+  if (target_copy(h, h->crit, h->dpg.c) || target_copy(h, h->net, h->dpg.a)) return -1;
   hipLaunchKernelGGL(k_train_clear, dim3(1), dim3(1), 0, h->stream, h->dpg.c.ctl, 1);
   HIPCHK(hipGetLastError());
   return 0;
@@ -3130,20 +2963,17 @@ extern "C" int aigar_dpg_reset(aigar_handle *h) {
   if (need_dpg(h, "dpg_reset")) return -1;
   HIPCHK(hipSetDevice(h->cfg.device));
   const DPGTrain &t = h->dpg;
-  for (int k = 0; k < 2; k++) {
-    const Net &c = k ? h->net : h->crit;
-    const Train &v = k ? t.a : t.c;
-    for (int l = 0; l < c.n_layers; l++) {
-      const size_t op = net_out_pad(c.out[l]), nw = (size_t)net_in_pad(c.in[l]) * op * sizeof(float);
-      HIPCHK(hipMemsetAsync(v.mw[l], 0, nw, h->stream));
-      HIPCHK(hipMemsetAsync(v.vw[l], 0, nw, h->stream));
-      HIPCHK(hipMemsetAsync(v.mb[l], 0, op * sizeof(float), h->stream));
-      HIPCHK(hipMemsetAsync(v.vb[l], 0, op * sizeof(float), h->stream));
-    }
-  }
+  if (adam_clear(h, h->crit, t.c) || adam_clear(h, h->net, t.a)) return -1;
   hipLaunchKernelGGL(k_dpg_clear, dim3(1), dim3(1), 0, h->stream, t.c.ctl, t.a.ctl);
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+// The configured trainer's view of the acting network, or (crit) of the critic.
+static const Train &trainer_view(const aigar_handle *h, bool crit) {
+  if (h->dpg.batch) return crit ? h->dpg.c : h->dpg.a;
+  if (h->act.batch) return crit ? h->act.c : h->act.a;
+  return h->trn;
 }
 
 // which: 0 online, 1 target, 2 Adam's m, 3 Adam's v (the last three need a train configuration)
@@ -3162,7 +2992,7 @@ static int net_which(aigar_handle *h, const char *who, int which, int layer, con
   if (which == 1 && h->act.batch) return fail("%s: which = 1: CACLA keeps no actor target", who);
   if (which > 4 && !dpg && need_act(h, who)) return -1;
   if (which >= 1 && which <= 3 && !dpg && !h->act.batch && need_trn(h, who)) return -1;
-  const Train &t = dpg ? (crit ? h->dpg.c : h->dpg.a) : crit ? h->act.c : h->act.batch ? h->act.a : h->trn;
+  const Train &t = trainer_view(h, crit);
   const int k = which & 3;
   *np = &c;
   *wp = k == 0 ? c.w[layer] : k == 1 ? t.tw[layer] : k == 2 ? t.mw[layer] : t.vw[layer];

@@ -58,41 +58,17 @@ __global__ void __launch_bounds__(64) k_sa_pack(int B, int n_s, int n_act, const
   for (int i = threadIdx.x; i < n; i += 64) o[i] = i < n_s ? s[i] : (T)a[i - n_s];
 }
 
-// k_td_v's targets, TD errors (float64), priorities, critic delta and step decisions, restated
-// without the selection.
+// k_td_v without the selection: targets, TD errors (float64), priorities, the critic's delta and
+// the step's decisions, every piece train.inc's.
 __global__ void __launch_bounds__(kTrainMaxBatch) k_td_q(Train c, Exp e, Dev d, int n_layers) {
   const int r = threadIdx.x, B = c.batch;
-  const int64_t size = e.ctl->size;
-  const int64_t need = c.batch > c.min_size ? c.batch : c.min_size;
-  const bool small = size < need || (e.prio && size < 2);
-  TrainCtl *ctl = c.ctl;
+  const bool small = train_small(c, e);
   double td = 0.0;
   bool bad = false;
-  if (r < B && !small) {
-    double tg = c.r[r];
-    if (!c.done[r]) tg = tg + c.discount * c.q2[r];
-    td = tg - c.q[r];
-    bad = !(fabs(td) < __builtin_inf());
-    c.td[r] = td;
-  }
+  if (r < B && !small) td = td_scalar(c, r, bad);
   const bool any_bad = __syncthreads_or(bad ? 1 : 0) != 0;
-  const bool skip = small || any_bad;
-  if (r < B) {
-    c.prio[r] = skip ? 0.0 : fabs(td) + 1e-4;
-    float g = 0.0f;
-    if (!skip) g = (float)(((2.0 * c.w[r]) * (-td)) / (double)(1 * B));
-    float *row = c.delta + ((size_t)(n_layers - 1) * c.bpad + r) * kNetMaxUnits;
-    for (int j = 0; j < 16; j++) row[j] = j == 0 ? g : -0.0f;
-  }
-  if (r == 0) {
-    const int64_t tn = ctl->t + 1;
-    ctl->skip = skip ? 1 : 0;
-    ctl->due = (!skip && c.target_steps > 0 && tn % c.target_steps == 0) ? 1 : 0;
-    ctl->lr_t = c.lr * sqrt(1.0 - aigar_math::pow_glibc(c.beta2, (double)tn)) /
-                (1.0 - aigar_math::pow_glibc(c.beta1, (double)tn));
-    if (!small) e.ctl->calls += 1;
-    if (any_bad) atomicOr(&d.ctl[0].warn, (uint32_t)WARN_TRAIN_NONFINITE);
-  }
+  if (r < B) delta_scalar(c, n_layers, r, td_prio_grad(c, r, small || any_bad, td, 1));
+  if (r == 0) td_decide(c, e, d, small, any_bad);
 }
 
 // The combined model's output delta (mse of Q([s, mu]) against Q'([s, mu-]) + q_increase, every
@@ -108,17 +84,14 @@ __global__ void __launch_bounds__(kTrainMaxBatch) k_dpg_delta(DPGTrain t, Dev d,
     const double tgt = t.qt[r] + t.q_increase;
     g = (float)((2.0 * (t.qm[r] - tgt)) / (double)(1 * B));
     bad = !(fabsf(g) < __builtin_inff());
-    float *row = t.ca.delta + ((size_t)(n_layers - 1) * t.ca.bpad + r) * kNetMaxUnits;
-    for (int j = 0; j < 16; j++) row[j] = j == 0 ? g : -0.0f;
+    delta_scalar(t.ca, n_layers, r, g);
   }
   const bool any_bad = __syncthreads_or(bad ? 1 : 0) != 0;
   if (r == 0) {
     const int skip = (live && !any_bad) ? 0 : 1;
     t.ca.ctl->skip = skip;
     a.ctl->skip = skip;  // (k_net_bwd_in may still raise it)
-    const int64_t tn = a.ctl->t + 1;
-    a.ctl->lr_t = a.lr * sqrt(1.0 - aigar_math::pow_glibc(a.beta2, (double)tn)) /
-                  (1.0 - aigar_math::pow_glibc(a.beta1, (double)tn));
+    a.ctl->lr_t = adam_lr_t(a, a.ctl->t + 1);
     if (any_bad) atomicOr(&d.ctl[0].warn, (uint32_t)WARN_TRAIN_NONFINITE);
   }
 }

@@ -54,16 +54,65 @@ struct Train {  // aigar_train_config (batch 0: off)
 
 constexpr int kTrainMaxBatch = 256;  // k_td is one workgroup, a row a thread
 
-// Targets, TD errors (float64, qLearning.py:116-129), priorities, the output delta and the
-// step's decisions.  The step is skipped when the memory holds fewer than max(batch,
-// min_size) transitions, and, with the warn bit, when a TD error is not finite or a stored
-// action index is outside the head.
-__global__ void __launch_bounds__(kTrainMaxBatch) k_td(Train t, Exp e, Dev d, int n_layers, int n_out) {
-  const int r = threadIdx.x, B = t.batch;
+// ---- what the three learners' TD kernels share (k_td here, k_td_v in actrain.inc, k_td_q in
+// dpg.inc), so that a replay priority and a skipped step mean the same under each of them
+
+// a view's lr * sqrt(1 - beta2^tn) / (1 - beta1^tn) for its step number tn
+__device__ __forceinline__ double adam_lr_t(const Train &v, int64_t tn) {
+  return v.lr * sqrt(1.0 - aigar_math::pow_glibc(v.beta2, (double)tn)) / (1.0 - aigar_math::pow_glibc(v.beta1, (double)tn));
+}
+
+// The memory holds fewer than max(batch, min_size) transitions (a prioritized one fewer than 2):
+// no step.
+__device__ __forceinline__ bool train_small(const Train &t, const Exp &e) {
   const int64_t size = e.ctl->size;
   const int64_t need = t.batch > t.min_size ? t.batch : t.min_size;
-  const bool small = size < need || (e.prio && size < 2);
+  return size < need || (e.prio && size < 2);
+}
+
+// Row r's priority and the value of its output delta's one entry, d(w mse)/dq over the
+// n_out * batch entries of the output.
+__device__ __forceinline__ float td_prio_grad(const Train &t, int r, bool skip, double td, int n_out) {
+  t.prio[r] = skip ? 0.0 : fabs(td) + 1e-4;  // (k_exp_update passes over an entry that is not > 0)
+  return skip ? 0.0f : (float)(((2.0 * t.w[r]) * (-td)) / (double)(n_out * t.batch));
+}
+
+// Thread 0's decisions of a step: the flags that every later kernel of the step reads first, the
+// view's lr_t, the memory's draw count and the warn bit.
+__device__ __forceinline__ void td_decide(const Train &t, const Exp &e, const Dev &d, bool small, bool any_bad) {
   TrainCtl *ctl = t.ctl;
+  const bool skip = small || any_bad;
+  const int64_t tn = ctl->t + 1;
+  ctl->skip = skip ? 1 : 0;
+  ctl->due = (!skip && t.target_steps > 0 && tn % t.target_steps == 0) ? 1 : 0;
+  ctl->lr_t = adam_lr_t(t, tn);
+  if (!small) e.ctl->calls += 1;  // (the memory's own draws of this step are used)
+  if (any_bad) atomicOr(&d.ctl[0].warn, (uint32_t)WARN_TRAIN_NONFINITE);
+}
+
+// A scalar critic's row r (V(s), Q(s, a): q and q2 are [batch]): its TD error (float64), kept
+// in c.td; bad: it is not finite.
+__device__ __forceinline__ double td_scalar(const Train &c, int r, bool &bad) {
+  double tg = c.r[r];
+  if (!c.done[r]) tg = tg + c.discount * c.q2[r];
+  const double td = tg - c.q[r];
+  bad = !(fabs(td) < __builtin_inf());
+  c.td[r] = td;
+  return td;
+}
+
+// ... and the output delta row of a one-unit head: g, then the padded units
+__device__ __forceinline__ void delta_scalar(const Train &v, int n_layers, int r, float g) {
+  float *row = v.delta + ((size_t)(n_layers - 1) * v.bpad + r) * kNetMaxUnits;
+  for (int j = 0; j < 16; j++) row[j] = j == 0 ? g : -0.0f;
+}
+
+// Targets, TD errors (float64, qLearning.py:116-129), priorities, the output delta and the
+// step's decisions.  The step is skipped when the memory is too small, and, with the warn bit,
+// when a TD error is not finite or a stored action index is outside the head.
+__global__ void __launch_bounds__(kTrainMaxBatch) k_td(Train t, Exp e, Dev d, int n_layers, int n_out) {
+  const int r = threadIdx.x, B = t.batch;
+  const bool small = train_small(t, e);
   int a = 0;
   double td = 0.0;
   bool bad = false;
@@ -90,24 +139,13 @@ __global__ void __launch_bounds__(kTrainMaxBatch) k_td(Train t, Exp e, Dev d, in
     t.td[r] = td;
   }
   const bool any_bad = __syncthreads_or(bad ? 1 : 0) != 0;
-  const bool skip = small || any_bad;
   if (r < B) {
-    t.prio[r] = skip ? 0.0 : fabs(td) + 1e-4;  // (k_exp_update passes over an entry that is not > 0)
-    float g = 0.0f;
-    if (!skip) g = (float)(((2.0 * t.w[r]) * (-td)) / (double)(n_out * B));
+    const float g = td_prio_grad(t, r, small || any_bad, td, n_out);
     float *row = t.delta + ((size_t)(n_layers - 1) * t.bpad + r) * kNetMaxUnits;
     const int op = net_out_pad(n_out);
     for (int j = 0; j < op; j++) row[j] = j == a ? g : (j < n_out ? 0.0f : -0.0f);
   }
-  if (r == 0) {
-    const int64_t tn = ctl->t + 1;
-    ctl->skip = skip ? 1 : 0;
-    ctl->due = (!skip && t.target_steps > 0 && tn % t.target_steps == 0) ? 1 : 0;
-    ctl->lr_t = t.lr * sqrt(1.0 - aigar_math::pow_glibc(t.beta2, (double)tn)) /
-                (1.0 - aigar_math::pow_glibc(t.beta1, (double)tn));
-    if (!small) e.ctl->calls += 1;  // (the memory's own draws of this step are used)
-    if (any_bad) atomicOr(&d.ctl[0].warn, (uint32_t)WARN_TRAIN_NONFINITE);
-  }
+  if (r == 0) td_decide(t, e, d, small, any_bad);
 }
 
 // delta_l -> delta_{l - 1} for l = n_layers - 1 ... 1, 16 batch rows a workgroup, four waves.

@@ -330,6 +330,7 @@ class AgarVecEnv:
             self.net_output = None
 
         self.training = None
+        self._trainer = None  # the Stepper's trainer family that train= configured: "train", "actrain" or "dpg"
         self.cacla = False  # (the trainer is the CACLA learner's: DESIGN.md §4m)
         self.dpg = False  # (... the DPG learner's: §4n)
         self.critic = None
@@ -347,22 +348,14 @@ class AgarVecEnv:
                                  "memory)")
             if self.pixels is not None or hasattr(self.network, "convs"):
                 raise ValueError("train=: CNN / pixel states are not trained on the device")
-            tp = _net.dpg_params(parameters)
-            tp["batch"] = int(self.memory["batch"])
-            if isinstance(train, dict):
-                over = {k: v for k, v in train.items() if k != "algorithm"}
-                unknown = set(over) - set(tp)
-                if unknown:
-                    raise ValueError("train: unknown keys %s" % sorted(unknown))
-                tp.update(over)
+            tp = self._train_settings(_net.dpg_params(parameters), train)
             n_in, n_act = int(self.stepper.obs_len), int(self.network.units[-1])
             cs = _net.qcritic_spec(parameters, n_in=n_in, n_act=n_act) if critic is None else _net.NetSpec(*critic)
             if cs.n_in is None:
                 cs = cs._replace(n_in=n_in + n_act)
             self.critic = cs
             self.stepper.qcritic_config(cs, self.obs.dtype)
-            self.training = tp
-            self.dpg = True
+            self.training, self._trainer, self.dpg = tp, "dpg", True
             self.stepper.dpg_config(**tp)
         elif train and self.continuous is not None:  # (explicit only, as memory=)
             if self.network is None or self.memory is None:
@@ -370,37 +363,35 @@ class AgarVecEnv:
                                  "memory)")
             if self.pixels is not None or hasattr(self.network, "convs"):
                 raise ValueError("train=: CNN / pixel states are not trained on the device")
-            tp = _net.actrain_params(parameters)
-            tp["batch"] = int(self.memory["batch"])
-            if isinstance(train, dict):
-                unknown = set(train) - set(tp)
-                if unknown:
-                    raise ValueError("train: unknown keys %s" % sorted(unknown))
-                tp.update(train)
+            tp = self._train_settings(_net.actrain_params(parameters), train)
             n_in = int(self.stepper.obs_len)
             cs = _net.critic_spec(parameters, n_in=n_in) if critic is None else _net.NetSpec(*critic)
             if cs.n_in is None:
                 cs = cs._replace(n_in=n_in)
             self.critic = cs
             self.stepper.critic_config(cs, self.obs.dtype)
-            self.training = tp
-            self.cacla = True
+            self.training, self._trainer, self.cacla = tp, "actrain", True
             self.stepper.actrain_config(**tp)
         elif train:
             if self.discrete is None or self.network is None or self.memory is None:
                 raise ValueError("train= needs discrete=, network= and memory= (Q-learning on the device's replay memory)")
             if self.pixels is not None or hasattr(self.network, "convs"):
                 raise ValueError("train=: CNN / pixel states are not trained on the device")
-            tp = _net.train_params(parameters)
-            if self.memory is not None:
-                tp["batch"] = int(self.memory["batch"])
-            if isinstance(train, dict):
-                unknown = set(train) - set(tp)
-                if unknown:
-                    raise ValueError("train: unknown keys %s" % sorted(unknown))
-                tp.update(train)
-            self.training = tp
+            tp = self._train_settings(_net.train_params(parameters), train)
+            self.training, self._trainer = tp, "train"
             self.stepper.train_config(**tp)
+
+    def _train_settings(self, tp, train):
+        """The trainer's settings: tp (the parameters' own) with the memory's batch, then the
+        overrides of a train= dict, whose "algorithm" key is no setting."""
+        tp["batch"] = int(self.memory["batch"])
+        if isinstance(train, dict):
+            over = {k: v for k, v in train.items() if k != "algorithm"}
+            unknown = set(over) - set(tp)
+            if unknown:
+                raise ValueError("train: unknown keys %s" % sorted(unknown))
+            tp.update(over)
+        return tp
 
     def _need_network(self):
         if self.network is None:
@@ -425,12 +416,7 @@ class AgarVecEnv:
             u = torch.as_tensor(u, dtype=torch.float64, device=self.dev).reshape(n, self.training["batch"]).contiguous()
         if self._mem_sync:
             torch.cuda.synchronize(self.dev)
-        if self.cacla:
-            self.stepper.actrain_step(n, u)
-        elif self.dpg:
-            self.stepper.dpg_step(n, u)
-        else:
-            self.stepper.train_step(n, u)
+        getattr(self.stepper, self._trainer + "_step")(n, u)
         if self._mem_sync:
             self.stepper.sync()  # (u is freed when this returns)
 
@@ -439,9 +425,7 @@ class AgarVecEnv:
         also has actor_epochs, selected, epochs, cut and epochs_skipped (aigar_actrain_info), the
         DPG trainer's actor_steps and actor_skipped (aigar_dpg_info)."""
         self._need_training()
-        if self.dpg:
-            return self.stepper.dpg_info()
-        return self.stepper.actrain_info() if self.cacla else self.stepper.train_info()
+        return getattr(self.stepper, self._trainer + "_info")()
 
     def train_td(self):
         """(td [batch] float64, idx [batch] int64) of the last drawn training step, device tensors."""
@@ -452,12 +436,7 @@ class AgarVecEnv:
         idx = torch.empty(b, dtype=torch.int64, device=self.dev)
         if self._mem_sync:
             torch.cuda.synchronize(self.dev)
-        if self.cacla:
-            self.stepper.actrain_td(td, idx)
-        elif self.dpg:
-            self.stepper.dpg_td(td, idx)
-        else:
-            self.stepper.train_td(td, idx)
+        getattr(self.stepper, self._trainer + "_td")(td, idx)
         if self._mem_sync:
             self.stepper.sync()
         return td, idx
