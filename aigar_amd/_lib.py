@@ -207,6 +207,32 @@ def _ptr(x):
     raise TypeError("expected numpy array or torch tensor, got %r" % type(x))
 
 
+_DTYPE_NAMES = {}  # dtype -> its bare name (every checked tensor of every call asks: the strings are made once)
+
+
+def _dtype_name(dtype, what=None):
+    """A numpy / torch dtype (or its name) -> the bare name, "float64" for torch.float64 and
+    for numpy.float64.  what: the caller and its argument ("net_config: x_dtype"), for a value
+    that must be float64 or float32 -- anything else is refused under that name."""
+    try:
+        d = _DTYPE_NAMES[dtype]
+    except KeyError:
+        d = _DTYPE_NAMES[dtype] = str(dtype).replace("torch.", "").replace("<class 'numpy.", "").replace("'>", "")
+    if what is not None and d not in ("float64", "float32"):
+        raise ValueError("%s must be float64 or float32, got %s" % (what, dtype))
+    return d
+
+
+def _dtype_code(d):
+    """The library's code of a floating dtype name: 0 float64, 1 float32."""
+    return 0 if d == "float64" else 1
+
+
+def _reward_params(params):
+    """A parameters object (or None: the defaults) -> _abi.RewardParams; one is passed through."""
+    return params if isinstance(params, _abi.RewardParams) else _abi.RewardParams.from_parameters(params)
+
+
 class Stepper:
     """One handle of the device stepper: n_arenas fields x bots_per_arena players."""
 
@@ -258,11 +284,16 @@ class Stepper:
     def policy_random(self, p_split=0.0, p_eject=0.0, seed=0):
         self._chk(self.L.aigar_policy_random(self.h, float(p_split), float(p_eject), int(seed)))
 
-    def policy_greedy(self, greedy_split=False, mask=None):
-        """Greedy bots' moves (bot.py:579-633) for the players where mask != 0 (all if None)."""
+    def _mask_ptr(self, mask):
+        """A per-player mask (None: everybody) -> (void pointer, on_device): a numpy array
+        becomes the [NP] uint8 the library reads, a device tensor goes as it is."""
         if isinstance(mask, np.ndarray):
             mask = np.ascontiguousarray(mask, np.uint8).reshape(self.NP)
-        p, dev = _ptr(mask)
+        return _ptr(mask)
+
+    def policy_greedy(self, greedy_split=False, mask=None):
+        """Greedy bots' moves (bot.py:579-633) for the players where mask != 0 (all if None)."""
+        p, dev = self._mask_ptr(mask)
         self._chk(self.L.aigar_policy_greedy(self.h, int(bool(greedy_split)), p, dev))
 
     def apply_actions(self, act, enable_split=True, skipping=False, record=True):
@@ -276,7 +307,7 @@ class Stepper:
 
     def rewards(self, params=None, update_last=True, out=None):
         """Bot.getReward for every player (NaN where the reference has None)."""
-        prm = params if isinstance(params, _abi.RewardParams) else _abi.RewardParams.from_parameters(params)
+        prm = _reward_params(params)
         if out is None:
             out = np.zeros(self.NP, np.float64)
         p, dev = _ptr(out)
@@ -302,7 +333,7 @@ class Stepper:
         if out is not None:
             if not getattr(out, "is_cuda", False):
                 raise ValueError("aigar_run writes observations to a device tensor")
-            dt = 0 if str(out.dtype) == "torch.float64" else 1
+            dt = _dtype_code(_dtype_name(out.dtype))
             if tuple(out.shape) != (self.NP, self.obs_len):
                 raise ValueError("observation tensor must be [%d, %d]" % (self.NP, self.obs_len))
             p = C.c_void_p(out.data_ptr())
@@ -322,19 +353,29 @@ class Stepper:
         if self.pixel_state_shape is not None:
             if tuple(reward.shape) != (self.NP,):
                 raise ValueError("reward must be [%d]" % self.NP)
-            self._check_out(obs, self.pixel_state_shape, ("float64", "float32"), "env_step")
         elif tuple(obs.shape) != (self.NP, self.obs_len) or tuple(reward.shape) != (self.NP,):
             raise ValueError("reward must be [%d], obs [%d, %d]" % (self.NP, self.NP, self.obs_len))
-        prm = params if isinstance(params, _abi.RewardParams) else _abi.RewardParams.from_parameters(params)
-        dt = 0 if str(obs.dtype) == "torch.float64" else 1
+        prm, rp, op, dt = self._decision_tail("env_step", reward, obs, params)
         self._chk(self.L.aigar_env_step(self.h, C.c_void_p(act.data_ptr()), int(act.shape[1]), int(bool(enable_split)),
-                                        int(skip), C.byref(prm), C.c_void_p(reward.data_ptr()),
-                                        C.c_void_p(obs.data_ptr()), dt))
+                                        int(skip), prm, rp, op, dt))
+
+    def _decision_tail(self, what, reward, obs, params, pixels=True):
+        """What every decision call ends with: reward [NP] float64 and obs, the handle's states
+        (the pixel state while one is configured and pixels holds, else the grid row) in float64
+        or float32, both contiguous device tensors; params as rewards() takes them.  Returns the
+        call's RewardParams pointer, the two tensors' pointers and obs' dtype code."""
+        for t in (reward, obs):
+            if not getattr(t, "is_cuda", False) or not t.is_contiguous():
+                raise ValueError("%s takes contiguous device tensors" % what)
+        rp = self._dev_ptr(reward, (self.NP,), ("float64",), what)
+        shape = self.pixel_state_shape if pixels and self.pixel_state_shape is not None else (self.NP, self.obs_len)
+        d = self._check_out(obs, shape, ("float64", "float32"), what)
+        return C.byref(_reward_params(params)), rp, C.c_void_p(obs.data_ptr()), _dtype_code(d)
 
     def _check_out(self, out, shape, dtypes, what):
         """The library writes prod(shape) elements of the dtype into out: refuse a
         buffer of another shape / dtype, a strided view or a tensor on another device."""
-        d = str(getattr(out, "dtype", "")).replace("torch.", "")
+        d = _dtype_name(getattr(out, "dtype", ""))
         if tuple(out.shape) != tuple(shape):
             raise ValueError("%s: out must have shape %s, got %s" % (what, tuple(shape), tuple(out.shape)))
         if d not in dtypes:
@@ -353,14 +394,12 @@ class Stepper:
         if out is None:
             out = np.zeros((self.NP, self.obs_len), dtype)
         d = self._check_out(out, (self.NP, self.obs_len), ("float64", "float32"), "observe")
-        dt = 0 if d == "float64" else 1
+        dt = _dtype_code(d)
         p, dev = _ptr(out)
         if mask is None:
             self._chk(self.L.aigar_observe(self.h, p, dt, dev))
         else:
-            if isinstance(mask, np.ndarray):
-                mask = np.ascontiguousarray(mask, np.uint8).reshape(self.NP)
-            mp, mdev = _ptr(mask)
+            mp, mdev = self._mask_ptr(mask)
             self._chk(self.L.aigar_observe_masked(self.h, p, dt, dev, mp, mdev))
         return out
 
@@ -397,12 +436,12 @@ class Stepper:
         uint8 [NP, side, side, 3] when rgb, else float64/float32 grayscale [NP, side, side]."""
         if out is None:
             out = np.zeros((self.NP, side, side, 3), np.uint8) if rgb else np.zeros((self.NP, side, side), np.float64)
-        d = str(getattr(out, "dtype", "")).replace("torch.", "")
+        d = _dtype_name(getattr(out, "dtype", ""))
         if d == "uint8":
             self._check_out(out, (self.NP, side, side, 3), ("uint8",), "observe_pixels")
         else:
             self._check_out(out, (self.NP, side, side), ("float64", "float32"), "observe_pixels")
-        dt = 2 if d == "uint8" else 0 if d == "float64" else 1
+        dt = 2 if d == "uint8" else _dtype_code(d)
         p, dev = _ptr(out)
         self._chk(self.L.aigar_observe_pixels(self.h, p, int(side), int(color_seed), dt, dev))
         return out
@@ -432,10 +471,8 @@ class Stepper:
             out = np.zeros(self.pixel_state_shape, dtype)
         d = self._check_out(out, self.pixel_state_shape, ("float64", "float32"), "observe_pixel_state")
         p, dev = _ptr(out)
-        if isinstance(mask, np.ndarray):
-            mask = np.ascontiguousarray(mask, np.uint8).reshape(self.NP)
-        mp, mdev = _ptr(mask)
-        self._chk(self.L.aigar_observe_pixel_state(self.h, p, 0 if d == "float64" else 1, dev, mp, mdev))
+        mp, mdev = self._mask_ptr(mask)
+        self._chk(self.L.aigar_observe_pixel_state(self.h, p, _dtype_code(d), dev, mp, mdev))
         return out
 
     # ---- replay memory (include/aigar.h: aigar_exp_*)
@@ -451,11 +488,9 @@ class Stepper:
             self._chk(self.L.aigar_exp_config(self.h, None))
             self.exp = None
             return
-        d = str(dtype).replace("torch.", "").replace("<class 'numpy.", "").replace("'>", "")
-        if d not in ("float64", "float32"):
-            raise ValueError("exp_config: dtype must be float64 or float32, got %s" % (dtype,))
+        d = _dtype_name(dtype, "exp_config: dtype")
         flags = (_abi.EXP_PRIORITIZED if prioritized else 0) | (_abi.EXP_EXTRA if extra else 0)
-        prm = _abi.ExpParams(int(capacity), 0 if d == "float64" else 1, flags, float(alpha), float(beta),
+        prm = _abi.ExpParams(int(capacity), _dtype_code(d), flags, float(alpha), float(beta),
                              int(seed) & 0xFFFFFFFFFFFFFFFF)
         self._chk(self.L.aigar_exp_config(self.h, C.byref(prm)))
         row = tuple(self.pixel_state_shape[1:]) if self.pixel_state_shape is not None else (self.obs_len,)
@@ -466,10 +501,16 @@ class Stepper:
             raise RuntimeError("aigar: %s: no replay memory is configured (exp_config)" % what)
         return self.exp
 
-    def _check_dev(self, t, shape, dtypes, what):
+    def _dev_ptr(self, t, shape, dtypes, what, optional=False):
+        """The pointer of a device tensor the library reads or writes as prod(shape) elements of
+        one of dtypes (optional: None for None): anything _check_out refuses, and what is no
+        tensor on a device, is refused under the caller's name."""
+        if t is None and optional:
+            return None
         if not getattr(t, "is_cuda", False):
             raise ValueError("%s takes device tensors" % what)
-        return self._check_out(t, shape, dtypes, what)
+        self._check_out(t, shape, dtypes, what)
+        return C.c_void_p(t.data_ptr())
 
     def exp_info(self):
         """{capacity, size, next_idx, added} of the memory (a host round trip)."""
@@ -502,15 +543,9 @@ class Stepper:
 
     def _exp_rows(self, batch, s, a, r, s2, done, what):
         row, d, _ = self._need_exp(what)
-        out = []
-        for x, shape, dts in ((s, (batch,) + row, (d,)), (a, (batch, 4), ("float64",)), (r, (batch,), ("float64",)),
-                              (s2, (batch,) + row, (d,)), (done, (batch,), ("uint8", "bool"))):
-            if x is None:
-                out.append(None)
-            else:
-                self._check_dev(x, shape, dts, what)
-                out.append(C.c_void_p(x.data_ptr()))
-        return out
+        args = ((s, (batch,) + row, (d,)), (a, (batch, 4), ("float64",)), (r, (batch,), ("float64",)),
+                (s2, (batch,) + row, (d,)), (done, (batch,), ("uint8", "bool")))
+        return [self._dev_ptr(x, shape, dts, what, optional=True) for x, shape, dts in args]
 
     def exp_sample(self, w, idx, u=None, s=None, a=None, r=None, s2=None, done=None):
         """One mini-batch of len(idx) draws on device tensors (aigar_exp_sample): idx [batch]
@@ -519,22 +554,18 @@ class Stepper:
         memory's own Philox stream).  Stream-ordered, no host round trip."""
         batch = int(idx.shape[0])
         rows = self._exp_rows(batch, s, a, r, s2, done, "exp_sample")
-        self._check_dev(w, (batch,), ("float64",), "exp_sample")
-        self._check_dev(idx, (batch,), ("int64",), "exp_sample")
-        up = None
-        if u is not None:
-            self._check_dev(u, (batch,), ("float64",), "exp_sample")
-            up = C.c_void_p(u.data_ptr())
-        self._chk(self.L.aigar_exp_sample(self.h, batch, up, rows[0], rows[1], rows[2], rows[3], rows[4],
-                                          C.c_void_p(w.data_ptr()), C.c_void_p(idx.data_ptr())))
+        wp = self._dev_ptr(w, (batch,), ("float64",), "exp_sample")
+        ip = self._dev_ptr(idx, (batch,), ("int64",), "exp_sample")
+        up = self._dev_ptr(u, (batch,), ("float64",), "exp_sample", optional=True)
+        self._chk(self.L.aigar_exp_sample(self.h, batch, up, rows[0], rows[1], rows[2], rows[3], rows[4], wp, ip))
 
     def exp_gather(self, idx, s=None, a=None, r=None, s2=None, done=None):
         """Row k of the given device tensors gets transition idx[k] (idx: int64 device tensor);
         rows whose index is outside [0, size) are left as they are."""
         batch = int(idx.shape[0])
         rows = self._exp_rows(batch, s, a, r, s2, done, "exp_gather")
-        self._check_dev(idx, (batch,), ("int64",), "exp_gather")
-        self._chk(self.L.aigar_exp_gather(self.h, C.c_void_p(idx.data_ptr()), batch, *rows))
+        ip = self._dev_ptr(idx, (batch,), ("int64",), "exp_gather")
+        self._chk(self.L.aigar_exp_gather(self.h, ip, batch, *rows))
 
     def exp_update_priorities(self, idx, prio):
         """PrioritizedReplayBuffer.update_priorities on device tensors idx [n] int64, prio [n]
@@ -542,9 +573,9 @@ class Stepper:
         are skipped); nothing in uniform mode."""
         self._need_exp("exp_update_priorities")
         n = int(idx.shape[0])
-        self._check_dev(idx, (n,), ("int64",), "exp_update_priorities")
-        self._check_dev(prio, (n,), ("float64",), "exp_update_priorities")
-        self._chk(self.L.aigar_exp_update_priorities(self.h, C.c_void_p(idx.data_ptr()), C.c_void_p(prio.data_ptr()), n))
+        ip = self._dev_ptr(idx, (n,), ("int64",), "exp_update_priorities")
+        pp = self._dev_ptr(prio, (n,), ("float64",), "exp_update_priorities")
+        self._chk(self.L.aigar_exp_update_priorities(self.h, ip, pp, n))
 
     def exp_extra_get(self, idx, out=None, valid=None):
         """The fifth field of the slots idx [batch] (int64 device tensor) into the device tensors
@@ -552,15 +583,10 @@ class Stepper:
         [0, size) are left as they are.  The memory needs extra=True."""
         self._need_exp("exp_extra_get")
         batch = int(idx.shape[0])
-        self._check_dev(idx, (batch,), ("int64",), "exp_extra_get")
-        op = vp = None
-        if out is not None:
-            self._check_dev(out, (batch, 4), ("float64",), "exp_extra_get")
-            op = C.c_void_p(out.data_ptr())
-        if valid is not None:
-            self._check_dev(valid, (batch,), ("uint8", "bool"), "exp_extra_get")
-            vp = C.c_void_p(valid.data_ptr())
-        self._chk(self.L.aigar_exp_extra_get(self.h, C.c_void_p(idx.data_ptr()), batch, op, vp))
+        ip = self._dev_ptr(idx, (batch,), ("int64",), "exp_extra_get")
+        op = self._dev_ptr(out, (batch, 4), ("float64",), "exp_extra_get", optional=True)
+        vp = self._dev_ptr(valid, (batch,), ("uint8", "bool"), "exp_extra_get", optional=True)
+        self._chk(self.L.aigar_exp_extra_get(self.h, ip, batch, op, vp))
 
     def exp_extra_set(self, idx, rows):
         """ReplayBuffer.update_dones on device tensors idx [n] int64, rows [n, 4] float64: slot
@@ -568,9 +594,9 @@ class Stepper:
         outside [0, size) are skipped).  The memory needs extra=True."""
         self._need_exp("exp_extra_set")
         n = int(idx.shape[0])
-        self._check_dev(idx, (n,), ("int64",), "exp_extra_set")
-        self._check_dev(rows, (n, 4), ("float64",), "exp_extra_set")
-        self._chk(self.L.aigar_exp_extra_set(self.h, C.c_void_p(idx.data_ptr()), C.c_void_p(rows.data_ptr()), n))
+        ip = self._dev_ptr(idx, (n,), ("int64",), "exp_extra_set")
+        rp = self._dev_ptr(rows, (n, 4), ("float64",), "exp_extra_set")
+        self._chk(self.L.aigar_exp_extra_set(self.h, ip, rp, n))
 
     # ---- exploration noise of the actor-critic learners (include/aigar.h: aigar_noise*)
     def noise_config(self, n_act, kind="Gaussian", mu_dtype="float32", theta=0.15, ou_mu=0.0, dt=0.01, seed=0,
@@ -584,11 +610,9 @@ class Stepper:
             self._chk(self.L.aigar_noise_config(self.h, None))
             self.noi = None
             return
-        d = str(mu_dtype).replace("torch.", "").replace("<class 'numpy.", "").replace("'>", "")
-        if d not in ("float64", "float32"):
-            raise ValueError("noise_config: mu_dtype must be float64 or float32, got %s" % (mu_dtype,))
+        d = _dtype_name(mu_dtype, "noise_config: mu_dtype")
         k = _abi.NOISE_TYPES[kind] if isinstance(kind, str) else int(kind)
-        prm = _abi.NoiseParams(int(n_act), k, 0 if d == "float64" else 1, int(bool(store_raw)), float(theta),
+        prm = _abi.NoiseParams(int(n_act), k, _dtype_code(d), int(bool(store_raw)), float(theta),
                                float(ou_mu), float(dt), int(seed) & 0xFFFFFFFFFFFFFFFF)
         self._chk(self.L.aigar_noise_config(self.h, C.byref(prm)))
         self.noi = (int(n_act), d, k == _abi.NOISE_ORN_UHL)
@@ -597,16 +621,19 @@ class Stepper:
         if self.noi is None:
             raise RuntimeError("aigar: %s: no exploration noise is configured (noise_config)" % what)
         n, d, _ = self.noi
-        self._check_dev(mu, (rows, n), (d,), what)
-        self._check_dev(std, (1,), ("float64",), what)
-        up, T = None, 0
-        if u is not None:
-            if u.dim() != 4 or not 1 <= int(u.shape[2]) <= _abi.NOISE_MAX_T:
-                raise ValueError("%s: u must be [rows, 2, T, 2] with T in 1..%d" % (what, _abi.NOISE_MAX_T))
-            T = int(u.shape[2])
-            self._check_dev(u, (rows, 2, T, 2), ("float64",), what)
-            up = C.c_void_p(u.data_ptr())
-        return C.c_void_p(mu.data_ptr()), C.c_void_p(std.data_ptr()), up, T
+        mp = self._dev_ptr(mu, (rows, n), (d,), what)
+        sp = self._dev_ptr(std, (1,), ("float64",), what)
+        return (mp, sp) + self._draws_arg(u, rows, "rows", what)
+
+    def _draws_arg(self, u, rows, rows_name, what):
+        """The noise's draws u [rows, 2, T, 2] float64 -> (pointer, T); (None, 0) for None, the
+        own Philox stream.  rows_name: how the caller's message calls the first dimension."""
+        if u is None:
+            return None, 0
+        if u.dim() != 4 or not 1 <= int(u.shape[2]) <= _abi.NOISE_MAX_T:
+            raise ValueError("%s: u must be [%s, 2, T, 2] with T in 1..%d" % (what, rows_name, _abi.NOISE_MAX_T))
+        T = int(u.shape[2])
+        return self._dev_ptr(u, (rows, 2, T, 2), ("float64",), what), T
 
     def noise(self, mu, std, out, u=None, prev=None, n_exhausted=None):
         """The perturbation alone on device tensors (aigar_noise): mu [rows, n_act], std [1]
@@ -617,42 +644,91 @@ class Stepper:
         rows = int(mu.shape[0])
         mp, sp, up, T = self._noise_args(mu, rows, std, u, "noise")
         n = self.noi[0]
-        self._check_dev(out, (rows, n), ("float64",), "noise")
-        pp = ep = None
-        if prev is not None:
-            self._check_dev(prev, (rows, n), ("float64",), "noise")
-            pp = C.c_void_p(prev.data_ptr())
-        if n_exhausted is not None:
-            self._check_dev(n_exhausted, (1,), ("int64",), "noise")
-            ep = C.c_void_p(n_exhausted.data_ptr())
-        self._chk(self.L.aigar_noise(self.h, mp, rows, sp, up, T, pp, C.c_void_p(out.data_ptr()), ep))
+        op = self._dev_ptr(out, (rows, n), ("float64",), "noise")
+        pp = self._dev_ptr(prev, (rows, n), ("float64",), "noise", optional=True)
+        ep = self._dev_ptr(n_exhausted, (1,), ("int64",), "noise", optional=True)
+        self._chk(self.L.aigar_noise(self.h, mp, rows, sp, up, T, pp, op, ep))
 
     def env_step_ac(self, mu, std, reward, obs, u=None, noisy=None, enable_split=True, skip=0, params=None):
         """One actor-critic decision on device tensors (aigar_env_step_ac): the noise, then
         env_step with the noisy rows; one graph replay.  noisy [NP, n_act] float64 gets the
         noisy actions (NaN rows where nobody decided)."""
         mp, sp, up, T = self._noise_args(mu, self.NP, std, u, "env_step_ac")
-        for t in (reward, obs):
-            if not getattr(t, "is_cuda", False) or not t.is_contiguous():
-                raise ValueError("env_step_ac takes contiguous device tensors")
-        self._check_dev(reward, (self.NP,), ("float64",), "env_step_ac")
-        if self.pixel_state_shape is not None:
-            self._check_out(obs, self.pixel_state_shape, ("float64", "float32"), "env_step_ac")
-        else:
-            self._check_out(obs, (self.NP, self.obs_len), ("float64", "float32"), "env_step_ac")
-        np_ = None
-        if noisy is not None:
-            self._check_dev(noisy, (self.NP, self.noi[0]), ("float64",), "env_step_ac")
-            np_ = C.c_void_p(noisy.data_ptr())
-        prm = params if isinstance(params, _abi.RewardParams) else _abi.RewardParams.from_parameters(params)
-        dt = 0 if str(obs.dtype) == "torch.float64" else 1
-        self._chk(self.L.aigar_env_step_ac(self.h, mp, sp, up, T, int(bool(enable_split)), int(skip), C.byref(prm),
-                                           C.c_void_p(reward.data_ptr()), C.c_void_p(obs.data_ptr()), dt, np_))
+        prm, rp, op, dt = self._decision_tail("env_step_ac", reward, obs, params)
+        np_ = self._dev_ptr(noisy, (self.NP, self.noi[0]), ("float64",), "env_step_ac", optional=True)
+        self._chk(self.L.aigar_env_step_ac(self.h, mp, sp, up, T, int(bool(enable_split)), int(skip), prm, rp, op, dt,
+                                           np_))
 
     @staticmethod
     def selftest_log(x):
         """Device log (glibc's, restated in aigar_math.h) for a host array."""
         return selftest_log(x)
+
+    # ---- what the acting network and the critic share: each is a stack of dense layers of the handle
+    _NET_CODES = {"online": _abi.NET_ONLINE, "target": _abi.NET_TARGET, "m": _abi.NET_ADAM_M, "v": _abi.NET_ADAM_V}
+    _CRITIC_CODES = {"online": _abi.NET_CRITIC, "target": _abi.NET_CRITIC_TARGET, "m": _abi.NET_CRITIC_M,
+                     "v": _abi.NET_CRITIC_V}
+
+    def _dense_params(self, what, n_in, units, hidden, out, x_dtype, min_layers):
+        """The NetParams of a dense stack -> (params, units, state dtype name): the activations by
+        name or code, x_dtype a numpy or torch dtype or its name; another dtype and a layer count
+        outside min_layers..NET_MAX_LAYERS are refused under the caller's name."""
+        units = [int(v) for v in units]
+        d = _dtype_name(x_dtype, what + ": x_dtype")
+        if not min_layers <= len(units) <= 8:
+            raise ValueError("%s: %d layers, %s%d" % (what, len(units), "1.." if min_layers else "at most ",
+                                                      _abi.NET_MAX_LAYERS))
+        code = lambda a: _abi.ACTIVATIONS[a] if isinstance(a, str) else int(a)
+        prm = _abi.NetParams(len(units), int(n_in), _dtype_code(d), code(hidden), code(out), 0)
+        for i, v in enumerate(units):
+            prm.units[i] = v
+        return prm, tuple(units), d
+
+    def _push_pair(self, what, push, l, W, b, shape):
+        """Layer l's weights through push (an aigar_*_set_*weights entry): W of shape and b
+        [shape[-1]], float32, both numpy arrays (anything else is made one) or both device tensors."""
+        if isinstance(W, np.ndarray) or not hasattr(W, "data_ptr"):
+            W, b = np.ascontiguousarray(W, np.float32), np.ascontiguousarray(b, np.float32)
+        self._check_out(W, shape, ("float32",), what)
+        self._check_out(b, (shape[-1],), ("float32",), what)
+        (wp, on), (bp, on_b) = _ptr(W), _ptr(b)
+        if on != on_b:
+            raise ValueError("%s: W and b both numpy arrays or both device tensors" % what)
+        self._chk(push(self.h, l, wp, bp, on))
+
+    def _push_dense(self, what, push, n_in, units, weights):
+        for l, (W, b) in enumerate(weights):
+            self._push_pair(what, push, l, W, b, (units[l - 1] if l else n_in, units[l]))
+
+    def _read_dense(self, what, codes, which, n_in, units, device=False):
+        """[(W [in, out], b [out])] float32 of the stack's copy codes[which] (aigar_net_get_weights)."""
+        if which not in codes:
+            raise ValueError("%s: which must be one of %s" % (what, sorted(codes)))
+        out = []
+        for l, n in enumerate(units):
+            k = units[l - 1] if l else n_in
+            if device:
+                import torch
+                dev = "cuda:%d" % self.cfg.device
+                W = torch.empty((k, n), dtype=torch.float32, device=dev)
+                b = torch.empty((n,), dtype=torch.float32, device=dev)
+            else:
+                W, b = np.empty((k, n), np.float32), np.empty((n,), np.float32)
+            self._chk(self.L.aigar_net_get_weights(self.h, codes[which], l, _ptr(W)[0], _ptr(b)[0], int(device)))
+            out.append((W, b))
+        return out
+
+    def _pad_check(self, codes, which):
+        v = C.c_int64()
+        self._chk(self.L.aigar_net_pad_check(self.h, codes[which], C.byref(v)))
+        return int(v.value)
+
+    def _forward(self, what, forward, x, xshape, out, oshape):
+        """x of xshape, float64 / float32, through forward (an aigar_*_forward entry) into out of
+        oshape, float64; rows is the first dimension of both."""
+        xp = self._dev_ptr(x, xshape, ("float64", "float32"), what)
+        op = self._dev_ptr(out, oshape, ("float64",), what)
+        self._chk(forward(self.h, xp, _dtype_code(_dtype_name(x.dtype)), xshape[0], op))
 
     # ---- the learners' acting network (include/aigar.h: aigar_net*)
     def net_config(self, spec, x_dtype="float64"):
@@ -681,23 +757,14 @@ class Stepper:
             n_in = n_flat
         else:
             n_in, units, hidden, out = spec
-        units = [int(v) for v in units]
-        d = str(x_dtype).replace("torch.", "").replace("<class 'numpy.", "").replace("'>", "")
-        if d not in ("float64", "float32"):
-            raise ValueError("net_config: x_dtype must be float64 or float32, got %s" % (x_dtype,))
-        if len(units) > 8:
-            raise ValueError("net_config: %d layers, at most %d" % (len(units), _abi.NET_MAX_LAYERS))
-        code = lambda a: _abi.ACTIVATIONS[a] if isinstance(a, str) else int(a)
-        prm = _abi.NetParams(len(units), int(n_in), 0 if d == "float64" else 1, code(hidden), code(out), 0)
-        for i, v in enumerate(units):
-            prm.units[i] = v
+        prm, units, d = self._dense_params("net_config", n_in, units, hidden, out, x_dtype, 0)
         if cprm is not None:
             self._chk(self.L.aigar_net_config_cnn(self.h, C.byref(cprm), C.byref(prm)))
             self.conv = (int(side), int(channels), convs)
         else:
             self._chk(self.L.aigar_net_config(self.h, C.byref(prm)))
             self.conv = None
-        self.net = (int(n_in), tuple(units), d)
+        self.net = (int(n_in), units, d)
 
     def _need_net(self, what):
         if getattr(self, "net", None) is None:
@@ -716,56 +783,21 @@ class Stepper:
         cin = self.conv[1] if self.conv is not None else 0
         for l, (W, b) in enumerate(weights[:len(convs)]):
             k, _, f = convs[l]
-            shape = (k, k, cin, f)
+            self._push_pair("net_set_weights", self.L.aigar_net_set_conv_weights, l, W, b, (k, k, cin, f))
             cin = f
-            if isinstance(W, np.ndarray) or not hasattr(W, "data_ptr"):
-                W, b = np.ascontiguousarray(W, np.float32), np.ascontiguousarray(b, np.float32)
-            self._check_out(W, shape, ("float32",), "net_set_weights")
-            self._check_out(b, (f,), ("float32",), "net_set_weights")
-            (wp, on), (bp, on_b) = _ptr(W), _ptr(b)
-            if on != on_b:
-                raise ValueError("net_set_weights: W and b both numpy arrays or both device tensors")
-            self._chk(self.L.aigar_net_set_conv_weights(self.h, l, wp, bp, on))
-        for l, (W, b) in enumerate(weights[len(convs):]):
-            shape = (units[l - 1] if l else n_in, units[l])
-            if isinstance(W, np.ndarray) or not hasattr(W, "data_ptr"):
-                W, b = np.ascontiguousarray(W, np.float32), np.ascontiguousarray(b, np.float32)
-            self._check_out(W, shape, ("float32",), "net_set_weights")
-            self._check_out(b, (shape[1],), ("float32",), "net_set_weights")
-            (wp, on), (bp, on_b) = _ptr(W), _ptr(b)
-            if on != on_b:
-                raise ValueError("net_set_weights: W and b both numpy arrays or both device tensors")
-            self._chk(self.L.aigar_net_set_weights(self.h, l, wp, bp, on))
+        self._push_dense("net_set_weights", self.L.aigar_net_set_weights, n_in, units, weights[len(convs):])
 
     def net_get_weights(self, which="online", device=False):
         """The read-back of net_set_weights (aigar_net_get_weights): a list of (W [in, out],
         b [out]) float32 per dense layer, numpy arrays or (device=True) device tensors.  which:
         "online", or with a train configuration "target", "m", "v" (Adam's state)."""
         n_in, units, _ = self._need_net("net_get_weights")
-        code = {"online": _abi.NET_ONLINE, "target": _abi.NET_TARGET, "m": _abi.NET_ADAM_M, "v": _abi.NET_ADAM_V}
-        if which not in code:
-            raise ValueError("net_get_weights: which must be one of %s" % sorted(code))
-        out = []
-        for l, n in enumerate(units):
-            k = units[l - 1] if l else n_in
-            if device:
-                import torch
-                dev = "cuda:%d" % self.cfg.device
-                W = torch.empty((k, n), dtype=torch.float32, device=dev)
-                b = torch.empty((n,), dtype=torch.float32, device=dev)
-            else:
-                W, b = np.empty((k, n), np.float32), np.empty((n,), np.float32)
-            self._chk(self.L.aigar_net_get_weights(self.h, code[which], l, _ptr(W)[0], _ptr(b)[0], int(device)))
-            out.append((W, b))
-        return out
+        return self._read_dense("net_get_weights", self._NET_CODES, which, n_in, units, device)
 
     def net_pad_check(self, which="online"):
         """A debug read (aigar_net_pad_check): how many padded entries of the packed copies are
         not +0.0f (0 in every correct state; a host round trip)."""
-        code = {"online": _abi.NET_ONLINE, "target": _abi.NET_TARGET, "m": _abi.NET_ADAM_M, "v": _abi.NET_ADAM_V}
-        v = C.c_int64()
-        self._chk(self.L.aigar_net_pad_check(self.h, code[which], C.byref(v)))
-        return int(v.value)
+        return self._pad_check(self._NET_CODES, which)
 
     # ---- the three trainers' shared plumbing: kind is the entry points' prefix
     _TRAINERS = {"train": ("trn", "no training is configured (train_config)"),
@@ -785,19 +817,15 @@ class Stepper:
         self._chk(getattr(self.L, "aigar_%s_%s" % (kind, name))(self.h, *args))
 
     def _trainer_step(self, kind, n, u):
-        batch, up = self._need_trainer(kind, kind + "_step"), None
-        if u is not None:
-            self._check_dev(u, (int(n), batch), ("float64",), kind + "_step")
-            up = C.c_void_p(u.data_ptr())
+        batch = self._need_trainer(kind, kind + "_step")
+        up = self._dev_ptr(u, (int(n), batch), ("float64",), kind + "_step", optional=True)
         self._trainer_call(kind, "step", int(n), up)
 
     def _trainer_td(self, kind, *outs):
         """outs: (tensor or None, dtype) of every optional [batch] output, in the call's order."""
         batch = self._need_trainer(kind, kind + "_td")
-        for t, dt in outs:
-            if t is not None:
-                self._check_dev(t, (batch,), (dt,), kind + "_td")
-        self._trainer_call(kind, "td", *(None if t is None else C.c_void_p(t.data_ptr()) for t, _ in outs))
+        self._trainer_call(kind, "td", *[self._dev_ptr(t, (batch,), (dt,), kind + "_td", optional=True)
+                                         for t, dt in outs])
 
     # ---- the Q-learning trainer (include/aigar.h: aigar_train*)
     def train_config(self, batch=32, min_size=0, target_steps=0, lr=1e-4, beta1=0.9, beta2=0.999, epsilon=1e-7,
@@ -850,16 +878,9 @@ class Stepper:
             self.crit = None
             return
         n_in, units, hidden, out = spec
-        units = [int(v) for v in units]
-        if not 1 <= len(units) <= 8:
-            raise ValueError("critic_config: %d layers, 1..%d" % (len(units), _abi.NET_MAX_LAYERS))
-        code = lambda a: _abi.ACTIVATIONS[a] if isinstance(a, str) else int(a)
-        d = str(x_dtype).replace("torch.", "")
-        prm = _abi.NetParams(len(units), int(n_in), 0 if d == "float64" else 1, code(hidden), code(out), 0)
-        for i, v in enumerate(units):
-            prm.units[i] = v
+        prm, units, _ = self._dense_params("critic_config", n_in, units, hidden, out, x_dtype, 1)
         self._chk(config(self.h, C.byref(prm)))
-        self.crit = (int(n_in), tuple(units))
+        self.crit = (int(n_in), units)
 
     def qcritic_config(self, spec, x_dtype="float64"):
         """The handle's critic Q(s, a) (aigar_qcritic_config): as critic_config, but n_in is the
@@ -879,48 +900,23 @@ class Stepper:
         n_in, units = self._need_crit("critic_set_weights")
         if len(weights) != len(units):
             raise ValueError("critic_set_weights: %d layers given, the critic has %d" % (len(weights), len(units)))
-        for l, (W, b) in enumerate(weights):
-            shape = (units[l - 1] if l else n_in, units[l])
-            if isinstance(W, np.ndarray) or not hasattr(W, "data_ptr"):
-                W, b = np.ascontiguousarray(W, np.float32), np.ascontiguousarray(b, np.float32)
-            self._check_out(W, shape, ("float32",), "critic_set_weights")
-            self._check_out(b, (shape[1],), ("float32",), "critic_set_weights")
-            (wp, on), (bp, on_b) = _ptr(W), _ptr(b)
-            if on != on_b:
-                raise ValueError("critic_set_weights: W and b both numpy arrays or both device tensors")
-            self._chk(self.L.aigar_critic_set_weights(self.h, l, wp, bp, on))
+        self._push_dense("critic_set_weights", self.L.aigar_critic_set_weights, n_in, units, weights)
 
     def critic_get_weights(self, which="online"):
         """[(W [in, out], b [out])] float32 numpy arrays of the critic ("online"), or with a CACLA
         train configuration of its "target", "m" or "v"."""
         n_in, units = self._need_crit("critic_get_weights")
-        code = {"online": _abi.NET_CRITIC, "target": _abi.NET_CRITIC_TARGET, "m": _abi.NET_CRITIC_M,
-                "v": _abi.NET_CRITIC_V}
-        if which not in code:
-            raise ValueError("critic_get_weights: which must be one of %s" % sorted(code))
-        out = []
-        for l, n in enumerate(units):
-            W, b = np.empty((units[l - 1] if l else n_in, n), np.float32), np.empty((n,), np.float32)
-            self._chk(self.L.aigar_net_get_weights(self.h, code[which], l, _ptr(W)[0], _ptr(b)[0], 0))
-            out.append((W, b))
-        return out
+        return self._read_dense("critic_get_weights", self._CRITIC_CODES, which, n_in, units)
 
     def critic_pad_check(self, which="online"):
-        code = {"online": _abi.NET_CRITIC, "target": _abi.NET_CRITIC_TARGET, "m": _abi.NET_CRITIC_M,
-                "v": _abi.NET_CRITIC_V}
-        v = C.c_int64()
-        self._chk(self.L.aigar_net_pad_check(self.h, code[which], C.byref(v)))
-        return int(v.value)
+        return self._pad_check(self._CRITIC_CODES, which)
 
     def critic_forward(self, x, out):
         """V(s) on device tensors (aigar_critic_forward): x [rows, n_in] float64 / float32 -> out
         [rows] float64."""
         n_in, _ = self._need_crit("critic_forward")
         rows = int(x.shape[0])
-        self._check_dev(x, (rows, n_in), ("float64", "float32"), "critic_forward")
-        self._check_dev(out, (rows,), ("float64",), "critic_forward")
-        self._chk(self.L.aigar_critic_forward(self.h, C.c_void_p(x.data_ptr()), 0 if str(x.dtype) == "torch.float64" else 1,
-                                              rows, C.c_void_p(out.data_ptr())))
+        self._forward("critic_forward", self.L.aigar_critic_forward, x, (rows, n_in), out, (rows,))
 
     def actrain_config(self, batch=32, min_size=0, target_steps=0, var_epochs=0, critic_lr=7.5e-5, actor_lr=5e-4,
                        beta1=0.9, beta2=0.999, epsilon=1e-7, discount=0.9, var_start=1.0, var_beta=0.001):
@@ -1009,17 +1005,13 @@ class Stepper:
         n_in, units, _ = self._need_net("net_forward")
         rows = int(x.shape[0])
         xshape = (rows, n_in) if self.conv is None else (rows, self.conv[0], self.conv[0], self.conv[1])
-        self._check_dev(x, xshape, ("float64", "float32"), "net_forward")
-        self._check_dev(out, (rows, units[-1]), ("float64",), "net_forward")
-        self._chk(self.L.aigar_net_forward(self.h, C.c_void_p(x.data_ptr()), 0 if str(x.dtype) == "torch.float64" else 1,
-                                           rows, C.c_void_p(out.data_ptr())))
+        self._forward("net_forward", self.L.aigar_net_forward, x, xshape, out, (rows, units[-1]))
 
     def net_output(self, out):
         """A copy of the handle's output buffer (the last decision's Q values / mu) into the
         device tensor out [NP, n_out] float64."""
         _, units, _ = self._need_net("net_output")
-        self._check_dev(out, (self.NP, units[-1]), ("float64",), "net_output")
-        self._chk(self.L.aigar_net_output(self.h, C.c_void_p(out.data_ptr())))
+        self._chk(self.L.aigar_net_output(self.h, self._dev_ptr(out, (self.NP, units[-1]), ("float64",), "net_output")))
 
     def env_step_net(self, head, explore, reward, obs, idx=None, val=None, u=None, noisy=None, enable_split=True,
                      skip=0, params=None, n_decisions=1):
@@ -1029,39 +1021,20 @@ class Stepper:
         must hold the current states: the network reads it, the decision rewrites it."""
         self._need_net("env_step_net")
         hd = _abi.NET_HEADS[head] if isinstance(head, str) else int(head)
-        for t in (reward, obs):
-            if not getattr(t, "is_cuda", False) or not t.is_contiguous():
-                raise ValueError("env_step_net takes contiguous device tensors")
-        self._check_dev(reward, (self.NP,), ("float64",), "env_step_net")
-        if self.conv is not None and self.pixel_state_shape is not None:
-            self._check_out(obs, self.pixel_state_shape, ("float64", "float32"), "env_step_net")
-        else:
-            self._check_out(obs, (self.NP, self.obs_len), ("float64", "float32"), "env_step_net")
-        up, T, ip, vp, np_ = None, 0, None, None, None
+        # (a dense network reads the grid row also while a pixel state is configured)
+        prm, rp, op, dt = self._decision_tail("env_step_net", reward, obs, params, pixels=self.conv is not None)
+        T, ip, vp, np_ = 0, None, None, None
         if hd == _abi.NET_HEAD_Q:
-            self._check_dev(explore, (2,), ("float64",), "env_step_net")
-            self._check_dev(idx, (self.NP,), ("int32",), "env_step_net")
-            self._check_dev(val, (self.NP,), ("float64",), "env_step_net")
-            ip, vp = C.c_void_p(idx.data_ptr()), C.c_void_p(val.data_ptr())
-            if u is not None:
-                self._check_dev(u, (self.NP, 3), ("float64",), "env_step_net")
-                up = C.c_void_p(u.data_ptr())
+            ep = self._dev_ptr(explore, (2,), ("float64",), "env_step_net")
+            ip = self._dev_ptr(idx, (self.NP,), ("int32",), "env_step_net")
+            vp = self._dev_ptr(val, (self.NP,), ("float64",), "env_step_net")
+            up = self._dev_ptr(u, (self.NP, 3), ("float64",), "env_step_net", optional=True)
         else:
-            self._check_dev(explore, (1,), ("float64",), "env_step_net")
-            if u is not None:
-                if u.dim() != 4 or not 1 <= int(u.shape[2]) <= _abi.NOISE_MAX_T:
-                    raise ValueError("env_step_net: u must be [NP, 2, T, 2] with T in 1..%d" % _abi.NOISE_MAX_T)
-                T = int(u.shape[2])
-                self._check_dev(u, (self.NP, 2, T, 2), ("float64",), "env_step_net")
-                up = C.c_void_p(u.data_ptr())
-            if noisy is not None:
-                self._check_dev(noisy, (self.NP, self.net[1][-1]), ("float64",), "env_step_net")
-                np_ = C.c_void_p(noisy.data_ptr())
-        prm = params if isinstance(params, _abi.RewardParams) else _abi.RewardParams.from_parameters(params)
-        dt = 0 if str(obs.dtype) == "torch.float64" else 1
-        self._chk(self.L.aigar_env_step_net(self.h, hd, C.c_void_p(explore.data_ptr()), up, T, int(bool(enable_split)),
-                                            int(skip), C.byref(prm), C.c_void_p(reward.data_ptr()),
-                                            C.c_void_p(obs.data_ptr()), dt, ip, vp, np_, int(n_decisions)))
+            ep = self._dev_ptr(explore, (1,), ("float64",), "env_step_net")
+            up, T = self._draws_arg(u, self.NP, "NP", "env_step_net")
+            np_ = self._dev_ptr(noisy, (self.NP, self.net[1][-1]), ("float64",), "env_step_net", optional=True)
+        self._chk(self.L.aigar_env_step_net(self.h, hd, ep, up, T, int(bool(enable_split)), int(skip), prm, rp, op, dt,
+                                            ip, vp, np_, int(n_decisions)))
 
     # ---- action selection of the Q-learning bots (include/aigar.h: aigar_decide*)
     def decide_config(self, actions, strategy="e-Greedy", q_dtype="float32", seed=0):
@@ -1076,11 +1049,9 @@ class Stepper:
         t = np.ascontiguousarray(actions, np.float64)
         if t.ndim != 2 or t.shape[1] != 4:
             raise ValueError("decide_config: the action table must be [n_out, 4], got %s" % (t.shape,))
-        d = str(q_dtype).replace("torch.", "").replace("<class 'numpy.", "").replace("'>", "")
-        if d not in ("float64", "float32"):
-            raise ValueError("decide_config: q_dtype must be float64 or float32, got %s" % (q_dtype,))
+        d = _dtype_name(q_dtype, "decide_config: q_dtype")
         st = _abi.STRATEGIES[strategy] if isinstance(strategy, str) else int(strategy)
-        prm = _abi.DecideParams(int(t.shape[0]), st, 0 if d == "float64" else 1, 0, int(seed) & 0xFFFFFFFFFFFFFFFF)
+        prm = _abi.DecideParams(int(t.shape[0]), st, _dtype_code(d), 0, int(seed) & 0xFFFFFFFFFFFFFFFF)
         self._chk(self.L.aigar_decide_config(self.h, C.byref(prm), t.ctypes.data_as(C.c_void_p)))
         self.dec = (int(t.shape[0]), d)
 
@@ -1088,45 +1059,28 @@ class Stepper:
         if self.dec is None:
             raise RuntimeError("aigar: %s: no action selection is configured (decide_config)" % what)
         n, d = self.dec
-        self._check_dev(q, (self.NP, n), (d,), what)
-        self._check_dev(explore, (2,), ("float64",), what)
-        self._check_dev(idx, (self.NP,), ("int32",), what)
-        self._check_dev(val, (self.NP,), ("float64",), what)
-        up = None
-        if u is not None:
-            self._check_dev(u, (self.NP, 3), ("float64",), what)
-            up = C.c_void_p(u.data_ptr())
-        return C.c_void_p(q.data_ptr()), C.c_void_p(explore.data_ptr()), up
+        qp = self._dev_ptr(q, (self.NP, n), (d,), what)
+        ep = self._dev_ptr(explore, (2,), ("float64",), what)
+        ip = self._dev_ptr(idx, (self.NP,), ("int32",), what)
+        vp = self._dev_ptr(val, (self.NP,), ("float64",), what)
+        return qp, ep, self._dev_ptr(u, (self.NP, 3), ("float64",), what, optional=True), ip, vp
 
     def decide(self, q, explore, idx, val, u=None, act=None):
         """The selection alone on device tensors (aigar_decide): q [NP, n_out], explore
         [epsilon, temperature] float64, u [NP, 3] float64 draws in [0, 1) (None: the own
         Philox stream); writes idx [NP] int32, val [NP] float64 and the chosen table rows
         into act [NP, 4] (dead and non-NN players: -1, NaN, row untouched)."""
-        qp, ep, up = self._decide_args(q, explore, u, idx, val, "decide")
-        ap = None
-        if act is not None:
-            self._check_dev(act, (self.NP, 4), ("float64",), "decide")
-            ap = C.c_void_p(act.data_ptr())
-        self._chk(self.L.aigar_decide(self.h, qp, ep, up, C.c_void_p(idx.data_ptr()), C.c_void_p(val.data_ptr()), ap))
+        qp, ep, up, ip, vp = self._decide_args(q, explore, u, idx, val, "decide")
+        ap = self._dev_ptr(act, (self.NP, 4), ("float64",), "decide", optional=True)
+        self._chk(self.L.aigar_decide(self.h, qp, ep, up, ip, vp, ap))
 
     def env_step_q(self, q, explore, reward, obs, idx, val, u=None, enable_split=True, skip=0, params=None):
         """One Q-learning decision on device tensors (aigar_env_step_q): decide, then
         env_step with the chosen table rows; one graph replay."""
-        qp, ep, up = self._decide_args(q, explore, u, idx, val, "env_step_q")
-        for t in (reward, obs):
-            if not getattr(t, "is_cuda", False) or not t.is_contiguous():
-                raise ValueError("env_step_q takes contiguous device tensors")
-        self._check_dev(reward, (self.NP,), ("float64",), "env_step_q")
-        if self.pixel_state_shape is not None:
-            self._check_out(obs, self.pixel_state_shape, ("float64", "float32"), "env_step_q")
-        else:
-            self._check_out(obs, (self.NP, self.obs_len), ("float64", "float32"), "env_step_q")
-        prm = params if isinstance(params, _abi.RewardParams) else _abi.RewardParams.from_parameters(params)
-        dt = 0 if str(obs.dtype) == "torch.float64" else 1
-        self._chk(self.L.aigar_env_step_q(self.h, qp, ep, up, int(bool(enable_split)), int(skip), C.byref(prm),
-                                          C.c_void_p(reward.data_ptr()), C.c_void_p(obs.data_ptr()), dt,
-                                          C.c_void_p(idx.data_ptr()), C.c_void_p(val.data_ptr())))
+        qp, ep, up, ip, vp = self._decide_args(q, explore, u, idx, val, "env_step_q")
+        prm, rp, op, dt = self._decision_tail("env_step_q", reward, obs, params)
+        self._chk(self.L.aigar_env_step_q(self.h, qp, ep, up, int(bool(enable_split)), int(skip), prm, rp, op, dt,
+                                          ip, vp))
 
     def warnings(self, arena=0):
         """The arena's sticky quirk bits since its last reset (aigar_warnings; _abi.WARN_*)."""
@@ -1142,9 +1096,7 @@ class Stepper:
     def reset_bots(self, mask=None):
         """Bot.reset's device half (bot.py:125-164) for the players where mask != 0
         (all if None): history grids zeroed, lastFovSize 0."""
-        if isinstance(mask, np.ndarray):
-            mask = np.ascontiguousarray(mask, np.uint8).reshape(self.NP)
-        p, dev = _ptr(mask)
+        p, dev = self._mask_ptr(mask)
         self._chk(self.L.aigar_reset_bots(self.h, p, dev))
 
     def player_stats(self):
@@ -1164,9 +1116,7 @@ class Stepper:
 
     def score_reset(self, mask=None):
         """Bot.resetMassList for the players where mask != 0 (all if None); stream-ordered."""
-        if isinstance(mask, np.ndarray):
-            mask = np.ascontiguousarray(mask, np.uint8).reshape(self.NP)
-        p, dev = _ptr(mask)
+        p, dev = self._mask_ptr(mask)
         self._chk(self.L.aigar_score_reset(self.h, p, dev))
 
     def score_trace(self, buf):
@@ -1284,7 +1234,7 @@ class Stepper:
         if out is not None:
             if not getattr(out, "is_cuda", False) or tuple(out.shape) != (self.NP, self.obs_len):
                 raise ValueError("tile_run writes observations to a device tensor [%d, %d]" % (self.NP, self.obs_len))
-            dt = 0 if str(out.dtype) == "torch.float64" else 1
+            dt = _dtype_code(_dtype_name(out.dtype))
             p = C.c_void_p(out.data_ptr())
         self._chk(self.L.aigar_tile_run(self.h, int(n), C.byref(prm), int(extra_passes), p, dt))
 
@@ -1301,7 +1251,7 @@ class Stepper:
         if out is not None:
             if not getattr(out, "is_cuda", False) or tuple(out.shape) != (self.NP, self.obs_len):
                 raise ValueError("tile_end writes observations to a device tensor [%d, %d]" % (self.NP, self.obs_len))
-            dt = 0 if str(out.dtype) == "torch.float64" else 1
+            dt = _dtype_code(_dtype_name(out.dtype))
             p = C.c_void_p(out.data_ptr())
         self._chk(self.L.aigar_tile_end(self.h, p, dt))
 

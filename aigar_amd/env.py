@@ -142,6 +142,37 @@ from .model import obs_masks, pixel_params
 Batch = collections.namedtuple("Batch", "s a r s2 done w idx")
 
 
+def _settings(name, defaults, given):
+    """The settings of an option that is True or a dict: the defaults (read from `parameters`),
+    overridden by the dict's entries; a key that is no setting is refused under the option's name."""
+    if isinstance(given, dict):
+        unknown = set(given) - set(defaults)
+        if unknown:
+            raise ValueError("%s: unknown keys %s" % (name, sorted(unknown)))
+        defaults.update(given)
+    return defaults
+
+
+# What train= configures, by the Stepper's prefix of the trainer's entry points: the option whose head
+# the trainer needs and the refusal's text when it, network= or memory= is missing, the trainer's
+# settings (aigar_amd.net), and for a trainer with a critic its spec from `parameters`, the critic's
+# input length (what a critic= spec without n_in gets) and the Stepper's configuration method.
+_Trainer = collections.namedtuple("_Trainer", "needs refusal settings critic_spec critic_n_in critic_config")
+_TRAINERS = {
+    "train": _Trainer("discrete",
+                      "train= needs discrete=, network= and memory= (Q-learning on the device's replay memory)",
+                      _net.train_params, None, None, None),
+    "actrain": _Trainer("continuous",
+                        "train= with continuous= needs network= and memory= (CACLA on the device's replay memory)",
+                        _net.actrain_params, lambda p, n_in, n_act: _net.critic_spec(p, n_in=n_in),
+                        lambda n_in, n_act: n_in, "critic_config"),
+    "dpg": _Trainer("continuous",
+                    "train='dpg' needs continuous=, network= and memory= (DPG on the device's replay memory)",
+                    _net.dpg_params, lambda p, n_in, n_act: _net.qcritic_spec(p, n_in=n_in, n_act=n_act),
+                    lambda n_in, n_act: n_in + n_act, "qcritic_config"),
+}
+
+
 class AgarVecEnv:
     def __init__(self, n_players, parameters=None, n_arenas=1, virus=None, field_size=0, max_pellets=-1.0,
                  max_viruses=-1.0, device=0, torch_stream=True, roles=None, reset_limit=None, desync=True, seed=0,
@@ -153,6 +184,7 @@ class AgarVecEnv:
         self.torch = torch
         self.parameters = parameters
         g = (lambda n, dflt: getattr(parameters, n, dflt)) if parameters is not None else (lambda n, dflt: dflt)
+        self._g = g  # (a setting of `parameters`, or the given default)
         ch, ex, gsq = obs_masks(parameters)
         virus = bool(g("VIRUS_SPAWN", False)) if virus is None else bool(virus)
         if not virus:
@@ -191,6 +223,11 @@ class AgarVecEnv:
         self.nn = torch.as_tensor(self.roles == _abi.ROLE_NN, device=self.dev)
         self._nn_u8 = self.nn.to(torch.uint8)
         self._mixed = bool((self.roles != _abi.ROLE_NN).any())
+        # the other bots' policies (step_calls and the warm-up move them call by call)
+        self._greedy = torch.as_tensor(self.roles == _abi.ROLE_GREEDY, device=self.dev).to(torch.uint8)
+        self._has_greedy = bool((self.roles == _abi.ROLE_GREEDY).any())
+        self._has_random = bool((self.roles == _abi.ROLE_RANDOM).any())
+        self._greedy_split = bool(g("ENABLE_GREEDY_SPLIT", False))
         self.reset_limit = int(g("RESET_LIMIT", 20000) if reset_limit is None else reset_limit)
         self.desync = bool(desync) and self.reset_limit > 0 and n_arenas > 1
         self.age = np.zeros(n_arenas, np.int64)
@@ -205,40 +242,40 @@ class AgarVecEnv:
         self._mask = torch.zeros(self.NP, dtype=torch.uint8, device=self.dev)  # (persistent: read on the stepper's stream)
         self._r = torch.empty(self.NP, dtype=torch.float64, device=self.dev)
         self._act = {}  # n_act -> persistent action buffer (the decision graph is keyed by its address)
+        self._own_stream = not torch_stream  # (the stepper's work is then not ordered with torch's)
         self._scored = bool(score)
         if self._scored:
-            self._own_stream = not torch_stream  # (the stepper's work is then not ordered with torch's)
             self._score = torch.empty((self.NP, 4), dtype=torch.float64, device=self.dev)
             self._ret = torch.zeros(self.NP, dtype=torch.float64, device=self.dev)
             nan = float("nan")
             # the last finished episode of every arena: NaN until its first episode has ended
             self.last_score = torch.full((self.NP, 4), nan, dtype=torch.float64, device=self.dev)
             self.last_return = torch.full((self.NP,), nan, dtype=torch.float64, device=self.dev)
+        self._setup_memory(memory, continuous)
+        self._setup_selection(discrete)
+        self._setup_noise(continuous)
+        self._setup_network(network)
+        self._setup_trainer(train, critic)
+
+    def _setup_memory(self, memory, continuous):
+        g = self._g
         self.memory = None
-        self._mem_sync = not torch_stream  # (the stepper's work is then not ordered with torch's)
         if memory:  # (explicit only: existing callers pass full parameter sets)
-            m = {"capacity": int(g("MEMORY_CAPACITY", 40000)),
-                 "prioritized": bool(g("PRIORITIZED_EXP_REPLAY_ENABLED", False)),
-                 "alpha": float(g("MEMORY_ALPHA", 0.6)), "beta": float(g("MEMORY_BETA", 0.4)),
-                 "batch": int(g("MEMORY_BATCH_LEN", 32)), "seed": self.seed}
-            if isinstance(memory, dict):
-                unknown = set(memory) - set(m)
-                if unknown:
-                    raise ValueError("memory: unknown keys %s" % sorted(unknown))
-                m.update(memory)
+            m = _settings("memory", {"capacity": int(g("MEMORY_CAPACITY", 40000)),
+                                     "prioritized": bool(g("PRIORITIZED_EXP_REPLAY_ENABLED", False)),
+                                     "alpha": float(g("MEMORY_ALPHA", 0.6)), "beta": float(g("MEMORY_BETA", 0.4)),
+                                     "batch": int(g("MEMORY_BATCH_LEN", 32)), "seed": self.seed}, memory)
             self.memory = m
             self.stepper.exp_config(m["capacity"], prioritized=m["prioritized"], alpha=m["alpha"], beta=m["beta"],
                                     dtype=self.obs.dtype, seed=m["seed"], extra=bool(continuous))
 
+    def _setup_selection(self, discrete):
+        torch, g = self.torch, self._g
         self.discrete = None
         if discrete:  # (explicit only, as memory=)
-            dd = {"num_actions": int(g("NUM_ACTIONS", 25)), "square": bool(g("SQUARE_ACTIONS", True)),
-                  "strategy": g("EXPLORATION_STRATEGY", "e-Greedy"), "seed": self.seed}
-            if isinstance(discrete, dict):
-                unknown = set(discrete) - set(dd)
-                if unknown:
-                    raise ValueError("discrete: unknown keys %s" % sorted(unknown))
-                dd.update(discrete)
+            dd = _settings("discrete", {"num_actions": int(g("NUM_ACTIONS", 25)),
+                                        "square": bool(g("SQUARE_ACTIONS", True)),
+                                        "strategy": g("EXPLORATION_STRATEGY", "e-Greedy"), "seed": self.seed}, discrete)
             if dd["strategy"] not in _abi.STRATEGIES:
                 raise ValueError("discrete: strategy must be one of %s" % sorted(_abi.STRATEGIES))
             self._table = _actions.discrete_actions(dd["num_actions"], dd["square"], self.enable_split,
@@ -257,17 +294,16 @@ class AgarVecEnv:
             self._q_dtype = None
             self._decide_dtype(torch.float32)
 
+    def _setup_noise(self, continuous):
+        torch, g = self.torch, self._g
         self.continuous = None
         if continuous:  # (explicit only, as memory=)
-            cc = {"noise": g("NOISE_TYPE", "Gaussian"), "theta": float(g("ORN_UHL_THETA", 0.15)),
-                  "mu": float(g("ORN_UHL_MU", 0)), "dt": float(g("ORN_UHL_DT", 0.01)),
-                  "std": float(g("GAUSSIAN_NOISE", 1.0)), "store_raw": g("ALGORITHM", "CACLA") == "CACLA",
-                  "seed": self.seed}
-            if isinstance(continuous, dict):
-                unknown = set(continuous) - set(cc)
-                if unknown:
-                    raise ValueError("continuous: unknown keys %s" % sorted(unknown))
-                cc.update(continuous)
+            cc = _settings("continuous", {"noise": g("NOISE_TYPE", "Gaussian"),
+                                          "theta": float(g("ORN_UHL_THETA", 0.15)),
+                                          "mu": float(g("ORN_UHL_MU", 0)), "dt": float(g("ORN_UHL_DT", 0.01)),
+                                          "std": float(g("GAUSSIAN_NOISE", 1.0)),
+                                          "store_raw": g("ALGORITHM", "CACLA") == "CACLA", "seed": self.seed},
+                            continuous)
             if cc["noise"] not in _abi.NOISE_TYPES:
                 raise ValueError("continuous: noise must be one of %s" % sorted(_abi.NOISE_TYPES))
             cc["n_act"] = 2 + int(self.enable_split) + int(bool(g("ENABLE_EJECT", False)))
@@ -287,6 +323,8 @@ class AgarVecEnv:
             self.stepper.noise_config(cc["n_act"], cc["noise"], torch.float64, theta=cc["theta"], ou_mu=cc["mu"],
                                       dt=cc["dt"], seed=cc["seed"], store_raw=cc["store_raw"])
 
+    def _setup_network(self, network):
+        torch, parameters = self.torch, self.parameters
         self.network = None
         self._obs_ready = False  # (`obs` holds the current states: what step_net's network reads)
         if network:  # (explicit only, as memory=)
@@ -329,10 +367,10 @@ class AgarVecEnv:
             self._net_out = torch.empty((self.NP, n_out), dtype=torch.float64, device=self.dev)
             self.net_output = None
 
+    def _setup_trainer(self, train, critic):
+        parameters = self.parameters
         self.training = None
         self._trainer = None  # the Stepper's trainer family that train= configured: "train", "actrain" or "dpg"
-        self.cacla = False  # (the trainer is the CACLA learner's: DESIGN.md §4m)
-        self.dpg = False  # (... the DPG learner's: §4n)
         self.critic = None
         if critic is not None and not (train and self.continuous is not None):
             raise ValueError("critic= needs continuous= and train= (the CACLA or DPG trainer's critic)")
@@ -342,56 +380,42 @@ class AgarVecEnv:
         if isinstance(train, dict) and "algorithm" in train and not dpg:
             raise ValueError("train: algorithm = %r: 'dpg' (the other trainers follow from discrete= / continuous=)"
                              % (train["algorithm"],))
-        if dpg:
-            if self.continuous is None or self.network is None or self.memory is None:
-                raise ValueError("train='dpg' needs continuous=, network= and memory= (DPG on the device's replay "
-                                 "memory)")
+        kind = "dpg" if dpg else "actrain" if self.continuous is not None else "train"
+        if train:  # (explicit only, as memory=)
+            row = _TRAINERS[kind]
+            if getattr(self, row.needs) is None or self.network is None or self.memory is None:
+                raise ValueError(row.refusal)
             if self.pixels is not None or hasattr(self.network, "convs"):
                 raise ValueError("train=: CNN / pixel states are not trained on the device")
-            tp = self._train_settings(_net.dpg_params(parameters), train)
-            n_in, n_act = int(self.stepper.obs_len), int(self.network.units[-1])
-            cs = _net.qcritic_spec(parameters, n_in=n_in, n_act=n_act) if critic is None else _net.NetSpec(*critic)
-            if cs.n_in is None:
-                cs = cs._replace(n_in=n_in + n_act)
-            self.critic = cs
-            self.stepper.qcritic_config(cs, self.obs.dtype)
-            self.training, self._trainer, self.dpg = tp, "dpg", True
-            self.stepper.dpg_config(**tp)
-        elif train and self.continuous is not None:  # (explicit only, as memory=)
-            if self.network is None or self.memory is None:
-                raise ValueError("train= with continuous= needs network= and memory= (CACLA on the device's replay "
-                                 "memory)")
-            if self.pixels is not None or hasattr(self.network, "convs"):
-                raise ValueError("train=: CNN / pixel states are not trained on the device")
-            tp = self._train_settings(_net.actrain_params(parameters), train)
-            n_in = int(self.stepper.obs_len)
-            cs = _net.critic_spec(parameters, n_in=n_in) if critic is None else _net.NetSpec(*critic)
-            if cs.n_in is None:
-                cs = cs._replace(n_in=n_in)
-            self.critic = cs
-            self.stepper.critic_config(cs, self.obs.dtype)
-            self.training, self._trainer, self.cacla = tp, "actrain", True
-            self.stepper.actrain_config(**tp)
-        elif train:
-            if self.discrete is None or self.network is None or self.memory is None:
-                raise ValueError("train= needs discrete=, network= and memory= (Q-learning on the device's replay memory)")
-            if self.pixels is not None or hasattr(self.network, "convs"):
-                raise ValueError("train=: CNN / pixel states are not trained on the device")
-            tp = self._train_settings(_net.train_params(parameters), train)
-            self.training, self._trainer = tp, "train"
-            self.stepper.train_config(**tp)
+            # the trainer's settings: the parameters' own with the memory's batch, then the
+            # overrides of a train= dict, whose "algorithm" key is no setting
+            tp = row.settings(parameters)
+            tp["batch"] = int(self.memory["batch"])
+            if isinstance(train, dict):
+                tp = _settings("train", tp, {k: v for k, v in train.items() if k != "algorithm"})
+            if row.critic_spec is not None:
+                n_in, n_act = int(self.stepper.obs_len), int(self.network.units[-1])
+                cs = row.critic_spec(parameters, n_in, n_act) if critic is None else _net.NetSpec(*critic)
+                if cs.n_in is None:
+                    cs = cs._replace(n_in=row.critic_n_in(n_in, n_act))
+                self.critic = cs
+                getattr(self.stepper, row.critic_config)(cs, self.obs.dtype)
+            self.training, self._trainer = tp, kind
+            getattr(self.stepper, kind + "_config")(**tp)
+        self.cacla = self._trainer == "actrain"  # (the trainer is the CACLA learner's: DESIGN.md §4m)
+        self.dpg = self._trainer == "dpg"  # (... the DPG learner's: §4n)
 
-    def _train_settings(self, tp, train):
-        """The trainer's settings: tp (the parameters' own) with the memory's batch, then the
-        overrides of a train= dict, whose "algorithm" key is no setting."""
-        tp["batch"] = int(self.memory["batch"])
-        if isinstance(train, dict):
-            over = {k: v for k, v in train.items() if k != "algorithm"}
-            unknown = set(over) - set(tp)
-            if unknown:
-                raise ValueError("train: unknown keys %s" % sorted(unknown))
-            tp.update(over)
-        return tp
+    def _ordered(self, call, *args, **kw):
+        """A stepper call outside the decision that reads or writes torch's tensors.  On torch's
+        stream it is ordered like any kernel.  A stepper with its own stream is ordered here:
+        what torch has queued (the arguments) is finished before the call, and the call's work
+        before it returns -- so the results are there for torch, and the arguments may be freed."""
+        if self._own_stream:
+            self.torch.cuda.synchronize(self.dev)
+        out = call(*args, **kw)
+        if self._own_stream:
+            self.stepper.sync()
+        return out
 
     def _need_network(self):
         if self.network is None:
@@ -414,11 +438,7 @@ class AgarVecEnv:
             raise ValueError("train: n must be at least 1")
         if u is not None:
             u = torch.as_tensor(u, dtype=torch.float64, device=self.dev).reshape(n, self.training["batch"]).contiguous()
-        if self._mem_sync:
-            torch.cuda.synchronize(self.dev)
-        getattr(self.stepper, self._trainer + "_step")(n, u)
-        if self._mem_sync:
-            self.stepper.sync()  # (u is freed when this returns)
+        self._ordered(getattr(self.stepper, self._trainer + "_step"), n, u)  # (u is freed when this returns)
 
     def train_info(self):
         """{steps, skipped, since_target} (aigar_train_info: a host round trip); the CACLA trainer's
@@ -434,11 +454,7 @@ class AgarVecEnv:
         b = self.training["batch"]
         td = torch.empty(b, dtype=torch.float64, device=self.dev)
         idx = torch.empty(b, dtype=torch.int64, device=self.dev)
-        if self._mem_sync:
-            torch.cuda.synchronize(self.dev)
-        getattr(self.stepper, self._trainer + "_td")(td, idx)
-        if self._mem_sync:
-            self.stepper.sync()
+        self._ordered(getattr(self.stepper, self._trainer + "_td"), td, idx)
         return td, idx
 
     def get_weights(self, target=False):
@@ -450,9 +466,7 @@ class AgarVecEnv:
             raise RuntimeError("get_weights: a network with a conv part has no read-back")
         if target:
             self._need_training()
-        if self._mem_sync:
-            self.torch.cuda.synchronize(self.dev)
-        return self.stepper.net_get_weights("target" if target else "online")
+        return self._ordered(self.stepper.net_get_weights, "target" if target else "online")
 
     # ---- the CACLA learner's critic and the DPG learner's (§4n)
     def _need_cacla(self):
@@ -467,42 +481,31 @@ class AgarVecEnv:
         """The critic's weights, as set_weights takes the acting network's.  The trainer's target
         keeps what it holds (train= copied the critic as it was then)."""
         self._need_critic()
-        torch = self.torch
-        pairs = isinstance(weights, (list, tuple)) and all(
-            isinstance(p, (list, tuple)) and len(p) == 2 and isinstance(p[0], torch.Tensor) and p[0].is_cuda
-            for p in weights)
-        if pairs:
-            ws = [(W.to(torch.float32).contiguous(), b.to(device=self.dev, dtype=torch.float32).contiguous())
-                  for W, b in weights]
-        else:
-            ws = _net.weights_from_torch(weights)
-        if self._mem_sync:
-            torch.cuda.synchronize(self.dev)
-        self.stepper.critic_set_weights(ws)
-        if self._mem_sync:
-            self.stepper.sync()  # (ws is freed when this returns)
+        self._push_weights(weights, _net.weights_from_torch, self.stepper.critic_set_weights)
 
     def get_critic_weights(self, target=False):
         """The critic's (target=True: its target's) weights as [(W [in, out], b [out])] float32 numpy arrays."""
         self._need_critic()
-        if self._mem_sync:
-            self.torch.cuda.synchronize(self.dev)
-        return self.stepper.critic_get_weights("target" if target else "online")
+        return self._ordered(self.stepper.critic_get_weights, "target" if target else "online")
 
     def critic_value(self, states):
         """V(s) of states [rows, n_in] (a device tensor or an array) -> [rows] float64 device tensor."""
         self._need_cacla()
+        return self._critic_rows(self._float_states(states))
+
+    def _float_states(self, states):
+        """states as a device tensor, float64 unless they are float32."""
         torch = self.torch
         x = torch.as_tensor(states, device=self.dev)
         if x.dtype not in (torch.float64, torch.float32):
             x = x.to(torch.float64)
+        return x
+
+    def _critic_rows(self, x):
+        """The critic on its input rows x [rows, critic n_in] -> [rows] float64 device tensor."""
         x = x.contiguous()
-        out = torch.empty(x.shape[0], dtype=torch.float64, device=self.dev)
-        if self._mem_sync:
-            torch.cuda.synchronize(self.dev)
-        self.stepper.critic_forward(x, out)
-        if self._mem_sync:
-            self.stepper.sync()
+        out = self.torch.empty(x.shape[0], dtype=self.torch.float64, device=self.dev)
+        self._ordered(self.stepper.critic_forward, x, out)
         return out
 
     def q_value(self, states, actions):
@@ -512,22 +515,13 @@ class AgarVecEnv:
         if not self.dpg:
             raise RuntimeError("AgarVecEnv was created without train='dpg' (the DPG trainer)")
         torch = self.torch
-        s = torch.as_tensor(states, device=self.dev)
-        if s.dtype not in (torch.float64, torch.float32):
-            s = s.to(torch.float64)
+        s = self._float_states(states)
         a = torch.as_tensor(actions, device=self.dev).to(s.dtype)
         n_act = self.critic.n_in - int(self.stepper.obs_len)
         if s.ndim != 2 or a.ndim != 2 or a.shape[0] != s.shape[0] or a.shape[1] != n_act:
             raise ValueError("q_value: states [rows, n_in] and actions [rows, %d], got %s and %s"
                              % (n_act, tuple(s.shape), tuple(a.shape)))
-        x = torch.cat([s, a], dim=1).contiguous()
-        out = torch.empty(x.shape[0], dtype=torch.float64, device=self.dev)
-        if self._mem_sync:
-            torch.cuda.synchronize(self.dev)
-        self.stepper.critic_forward(x, out)
-        if self._mem_sync:
-            self.stepper.sync()
-        return out
+        return self._critic_rows(torch.cat([s, a], dim=1))
 
     def cacla_var(self):
         """CACLA-Var's running variance of the TD error (a host round trip)."""
@@ -541,6 +535,15 @@ class AgarVecEnv:
         pairs (W [k, k, Cin, F], b [F]) first, aigar_amd.net.cnn_weights_from_torch).  Takes
         effect at the next decision; the captured graph stays."""
         self._need_network()
+        if hasattr(self.network, "convs"):
+            convert = lambda w: _net.cnn_weights_from_torch(w, self.network)
+        else:
+            convert = _net.weights_from_torch
+        self._push_weights(weights, convert, self.stepper.net_set_weights)
+
+    def _push_weights(self, weights, convert, push):
+        """weights through push (the Stepper's net_set_weights or critic_set_weights): pairs of
+        device tensors go as float32 device tensors, anything else through convert."""
         torch = self.torch
         pairs = isinstance(weights, (list, tuple)) and all(
             isinstance(p, (list, tuple)) and len(p) == 2 and isinstance(p[0], torch.Tensor) and p[0].is_cuda
@@ -548,15 +551,9 @@ class AgarVecEnv:
         if pairs:
             ws = [(W.to(torch.float32).contiguous(), b.to(device=self.dev, dtype=torch.float32).contiguous())
                   for W, b in weights]
-        elif hasattr(self.network, "convs"):
-            ws = _net.cnn_weights_from_torch(weights, self.network)
         else:
-            ws = _net.weights_from_torch(weights)
-        if self._mem_sync:
-            torch.cuda.synchronize(self.dev)
-        self.stepper.net_set_weights(ws)
-        if self._mem_sync:
-            self.stepper.sync()  # (ws is freed when this returns)
+            ws = convert(weights)
+        self._ordered(push, ws)  # (ws is freed when this returns)
 
     def _net_decisions(self, n, u=None):
         """n decisions with the network in front, one graph replay each, no host work between."""
@@ -566,22 +563,12 @@ class AgarVecEnv:
             raise RuntimeError("step_net: `obs` does not hold the current states yet: call reset() or observe() first")
         kw = dict(enable_split=self.enable_split, skip=self.skip, params=self.reward_params, n_decisions=n)
         if self._head == "q":
-            if u is not None:
-                self._u.copy_(torch.as_tensor(u, dtype=torch.float64, device=self.dev))
-                u = self._u
+            u = self._q_draws(u)
             self._decide_dtype(torch.float64)
             self.stepper.env_step_net("q", self.explore, self._r, self.obs, idx=self._idx, val=self._val, u=u, **kw)
             self.action_idx, self.action_value = self._idx.clone(), self._val.clone()
         else:
-            if u is not None:
-                u = torch.as_tensor(u, dtype=torch.float64, device=self.dev)
-                if u.dim() != 4 or tuple(u.shape[:2]) != (self.NP, 2) or int(u.shape[3]) != 2:
-                    raise ValueError("step_net: u must be [%d, 2, T, 2], got %s" % (self.NP, tuple(u.shape)))
-                ub = self._nu.get(int(u.shape[2]))
-                if ub is None:
-                    ub = self._nu[int(u.shape[2])] = torch.empty(tuple(u.shape), dtype=torch.float64, device=self.dev)
-                ub.copy_(u)
-                u = ub
+            u = self._noise_draws(u, "step_net")
             self.stepper.env_step_net("actor", self.noise_std, self._r, self.obs, u=u, noisy=self._noisy, **kw)
             self.noisy_action = self._noisy.clone()
         self.stepper.net_output(self._net_out)
@@ -652,16 +639,22 @@ class AgarVecEnv:
             raise ValueError("%s: mu must be [%d, %d], got %s" % (what, self.NP, n, tuple(mu.shape)))
         buf = self._mu
         buf.copy_(mu)  # (float32 -> float64: exact)
-        if u is not None:
-            u = torch.as_tensor(u, dtype=torch.float64, device=self.dev)
-            if u.dim() != 4 or tuple(u.shape[:2]) != (self.NP, 2) or int(u.shape[3]) != 2:
-                raise ValueError("%s: u must be [%d, 2, T, 2], got %s" % (what, self.NP, tuple(u.shape)))
-            ub = self._nu.get(int(u.shape[2]))
-            if ub is None:
-                ub = self._nu[int(u.shape[2])] = torch.empty(tuple(u.shape), dtype=torch.float64, device=self.dev)
-            ub.copy_(u)
-            u = ub
-        return buf, u
+        return buf, self._noise_draws(u, what)
+
+    def _noise_draws(self, u, what):
+        """The decision's given draws u [NP, 2, T, 2] in the persistent buffer of their T (the
+        decision graph is keyed by its address); None (the device's own) stays None."""
+        if u is None:
+            return None
+        torch = self.torch
+        u = torch.as_tensor(u, dtype=torch.float64, device=self.dev)
+        if u.dim() != 4 or tuple(u.shape[:2]) != (self.NP, 2) or int(u.shape[3]) != 2:
+            raise ValueError("%s: u must be [%d, 2, T, 2], got %s" % (what, self.NP, tuple(u.shape)))
+        ub = self._nu.get(int(u.shape[2]))
+        if ub is None:
+            ub = self._nu[int(u.shape[2])] = torch.empty(tuple(u.shape), dtype=torch.float64, device=self.dev)
+        ub.copy_(u)
+        return ub
 
     def step_ac(self, mu, u=None):
         """mu: [n_players, n_act] float32 / float64 device tensor of the actor's outputs (rows of
@@ -719,11 +712,7 @@ class AgarVecEnv:
         if u is not None:
             u = torch.as_tensor(u, dtype=torch.float64, device=self.dev).contiguous()
         out = torch.empty(tuple(a.shape), dtype=torch.float64, device=self.dev)
-        if self._mem_sync:
-            torch.cuda.synchronize(self.dev)
-        self.stepper.noise(a, std, out, u=u, prev=prev)
-        if self._mem_sync:
-            self.stepper.sync()
+        self._ordered(self.stepper.noise, a, std, out, u=u, prev=prev)
         return out
 
     def sample_extra(self, idx):
@@ -736,11 +725,7 @@ class AgarVecEnv:
         idx = torch.as_tensor(idx, dtype=torch.int64, device=self.dev).contiguous()
         extra = torch.full((int(idx.shape[0]), 4), float("nan"), dtype=torch.float64, device=self.dev)
         valid = torch.zeros(int(idx.shape[0]), dtype=torch.bool, device=self.dev)
-        if self._mem_sync:
-            torch.cuda.synchronize(self.dev)
-        self.stepper.exp_extra_get(idx, extra, valid)
-        if self._mem_sync:
-            self.stepper.sync()
+        self._ordered(self.stepper.exp_extra_get, idx, extra, valid)
         return extra, valid
 
     def update_actions(self, idx, actions):
@@ -754,11 +739,7 @@ class AgarVecEnv:
         a = torch.as_tensor(actions, dtype=torch.float64, device=self.dev)
         rows = torch.zeros((int(idx.shape[0]), 4), dtype=torch.float64, device=self.dev)
         rows[:, :a.shape[1]] = a
-        if self._mem_sync:
-            torch.cuda.synchronize(self.dev)
-        self.stepper.exp_extra_set(idx, rows)
-        if self._mem_sync:
-            self.stepper.sync()  # (rows is freed when this returns)
+        self._ordered(self.stepper.exp_extra_set, idx, rows)  # (rows is freed when this returns)
 
     def _decide_dtype(self, dtype):
         """(Re)configure the selection for Q rows of dtype (the kernel is built per dtype)."""
@@ -792,10 +773,14 @@ class AgarVecEnv:
             buf = self._q[q.dtype] = torch.empty((self.NP, self.discrete["n_out"]), dtype=q.dtype, device=self.dev)
         buf.copy_(q)
         self._decide_dtype(q.dtype)
+        return buf, self._q_draws(u)
+
+    def _q_draws(self, u):
+        """The selection's given draws u [NP, 3] in their persistent buffer; None stays None."""
         if u is not None:
-            self._u.copy_(torch.as_tensor(u, dtype=torch.float64, device=self.dev))
+            self._u.copy_(self.torch.as_tensor(u, dtype=self.torch.float64, device=self.dev))
             u = self._u
-        return buf, u
+        return u
 
     def step_q(self, q, u=None):
         """q: [n_players, n_out] float32 / float64 device tensor of action values (rows of
@@ -838,11 +823,7 @@ class AgarVecEnv:
         idx = torch.empty(n, dtype=torch.int64, device=self.dev)
         if u is not None:
             u = torch.as_tensor(u, dtype=torch.float64, device=self.dev).contiguous()
-        if self._mem_sync:
-            torch.cuda.synchronize(self.dev)
-        self.stepper.exp_sample(w, idx, u=u, s=s, a=a, r=r, s2=s2, done=done)
-        if self._mem_sync:
-            self.stepper.sync()
+        self._ordered(self.stepper.exp_sample, w, idx, u=u, s=s, a=a, r=r, s2=s2, done=done)
         return Batch(s, a, r, s2, done, w, idx)
 
     def update_priorities(self, idx, td_error):
@@ -856,11 +837,7 @@ class AgarVecEnv:
         idx = torch.as_tensor(idx, dtype=torch.int64, device=self.dev).contiguous()
         td = torch.as_tensor(td_error, dtype=torch.float64, device=self.dev).contiguous()
         prio = td.abs() + 1e-4
-        if self._mem_sync:
-            torch.cuda.synchronize(self.dev)
-        self.stepper.exp_update_priorities(idx, prio)
-        if self._mem_sync:
-            self.stepper.sync()  # (prio is freed when this returns)
+        self._ordered(self.stepper.exp_update_priorities, idx, prio)  # (prio is freed when this returns)
 
     def memory_size(self):
         """Transitions the memory holds (aigar_exp_info: a host round trip)."""
@@ -893,9 +870,6 @@ class AgarVecEnv:
         k * int(R / N) of them are left; then Model.resetBots for every arena."""
         per = self.reset_limit // self.A
         total = (self.A - 1) * per
-        has_g, has_r = bool((self.roles == _abi.ROLE_GREEDY).any()), bool((self.roles == _abi.ROLE_RANDOM).any())
-        greedy = self.torch.as_tensor(self.roles == _abi.ROLE_GREEDY, device=self.dev).to(self.torch.uint8)
-        gsplit = bool(getattr(self.parameters, "ENABLE_GREEDY_SPLIT", False)) if self.parameters is not None else False
         for t in range(total + 1):
             fresh = [a for a in range(self.A) if t > 0 and total - a * per == t]
             if fresh:
@@ -905,11 +879,7 @@ class AgarVecEnv:
             # NN players: random points in their view (an untrained network's moves);
             # Greedy / Random bots: their own device policies
             self.stepper.policy_random(0.0, 0.0, seed ^ 0x5DEECE66D)
-            if has_g:
-                self.stepper.policy_greedy(gsplit, greedy)
-            if has_r:
-                self.stepper.policy_random_bots()
-            self.stepper.step(1)
+            self._others_move_and_tick()
         # Model.resetBots: every bot of every arena (the world goes on).  Still the host
         # round trip: load_state also re-lays the pellet rows and restarts the arena's
         # control block and epochs, which no device call does for a running world
@@ -993,9 +963,7 @@ class AgarVecEnv:
         return self.obs.clone(), reward, alive, done
 
     def _read_score(self):
-        self.stepper.score(self._score)
-        if self._own_stream:
-            self.stepper.sync()
+        self._ordered(self.stepper.score, self._score)
 
     def score(self):
         """[NP, 4] device tensor of the running episodes: samples, sum, max, deaths of
@@ -1030,22 +998,23 @@ class AgarVecEnv:
         act = actions if isinstance(actions, torch.Tensor) else torch.as_tensor(np.asarray(actions), device=self.dev)
         act = act.to(device=self.dev, dtype=torch.float64).contiguous()
         reward = torch.zeros(self.NP, dtype=torch.float64, device=self.dev)
-        greedy = torch.as_tensor(self.roles == _abi.ROLE_GREEDY, device=self.dev).to(torch.uint8)
-        has_g, has_r = bool((self.roles == _abi.ROLE_GREEDY).any()), bool((self.roles == _abi.ROLE_RANDOM).any())
-        gsplit = bool(getattr(self.parameters, "ENABLE_GREEDY_SPLIT", False)) if self.parameters is not None else False
         for k in range(self.skip + 1):
             if k > 0:  # updateRewards on the skipped frames (bot.py:166-168)
                 reward += self._reward_term(update_last=False)
             self.stepper.apply_actions(act, self.enable_split, skipping=k > 0, record=k == 0)
-            if has_g:
-                self.stepper.policy_greedy(gsplit, greedy)
-            if has_r:
-                self.stepper.policy_random_bots()
-            self.stepper.step(1)
+            self._others_move_and_tick()
         reward += self._reward_term(update_last=True)
         obs = self.observe()
         alive = ~torch.isnan(obs.view(self.NP, -1)[:, 0]) & self.nn
         return obs, reward, alive
+
+    def _others_move_and_tick(self):
+        """The Greedy and the Random bots' own device policies, then one tick."""
+        if self._has_greedy:
+            self.stepper.policy_greedy(self._greedy_split, self._greedy)
+        if self._has_random:
+            self.stepper.policy_random_bots()
+        self.stepper.step(1)
 
     def _reward_term(self, update_last):
         """What updateRewards adds for every player (bot.py:167): getReward() while the bot

@@ -445,6 +445,10 @@ def test_live_handle_refusals():
         st.critic_config((64, (15, 2), "relu", "linear"))
     with pytest.raises(RuntimeError, match="V\\(s\\) is one linear unit"):
         st.critic_config((64, (15, 1), "relu", "sigmoid"))
+    with pytest.raises(ValueError, match="critic_config: x_dtype must be float64 or float32, got float16"):
+        st.critic_config(crit, x_dtype="float16")
+    st.critic_config(crit, x_dtype=np.float64)  # (numpy and torch dtypes are taken, as net_config takes them)
+    assert st.crit == (64, (15, 1))
     st.critic_config(crit)
     with pytest.raises(RuntimeError, match="the network's head is sigmoid, Q-learning needs a linear head"):
         st.train_config(batch=16)  # (the Q trainer's own message, as before)
