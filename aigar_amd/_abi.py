@@ -130,6 +130,16 @@ class DpgParams(C.Structure):
                 ("epsilon", C.c_double), ("discount", C.c_double), ("tau", C.c_double), ("q_increase", C.c_double)]
 
 
+SPG_MAX_SAMPLES = 8
+
+
+class SpgParams(C.Structure):
+    """aigar_spg_params (include/aigar.h): the SPG trainer (actorCritic.py:860-919, 986-1029)."""
+    _fields_ = DpgParams._fields_ + [("samples", C.c_int32), ("moving", C.c_int32), ("replace", C.c_int32),
+                                     ("prio_evals", C.c_int32), ("fused", C.c_int32), ("pad", C.c_int32),
+                                     ("noise", C.c_double), ("noise_decay", C.c_double), ("seed", C.c_uint64)]
+
+
 CONV_MAX_LAYERS, CONV_MAX_SIDE, CONV_MAX_CHANNELS, CONV_MAX_KERNEL, CONV_MAX_FILTERS = 3, 128, 8, 8, 64
 
 

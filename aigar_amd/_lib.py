@@ -131,6 +131,13 @@ def load(build_if_missing=False):
         "aigar_dpg_td": [vp, vp, vp],
         "aigar_dpg_sync_target": [vp],
         "aigar_dpg_reset": [vp],
+        "aigar_spg_config": [vp, C.POINTER(_abi.SpgParams)],
+        "aigar_spg_step": [vp, i32, vp, vp],
+        "aigar_spg_info": [vp, C.POINTER(C.c_int64)],
+        "aigar_spg_td": [vp, vp, vp],
+        "aigar_spg_noise": [vp, C.POINTER(vp)],
+        "aigar_spg_sync_target": [vp],
+        "aigar_spg_reset": [vp],
         "aigar_net_get_weights": [vp, i32, i32, vp, vp, i32],
         "aigar_net_pad_check": [vp, i32, C.POINTER(C.c_int64)],
         "aigar_exp_extra_get": [vp, vp, i32, vp, vp],
@@ -255,6 +262,7 @@ class Stepper:
         self.crit = None  # (n_in, units) while a critic is configured
         self.act = None  # the batch while a CACLA training is configured
         self.dpg = None  # the batch while a DPG training is configured
+        self.spg = None  # (batch, samples) while an SPG training is configured
 
     def _chk(self, r):
         if r < 0:
@@ -483,7 +491,7 @@ class Stepper:
         is set every env_step appends the NN players' transitions inside its graph.  extra:
         the ring also keeps the tuple's fifth field (exp_extra_get / exp_extra_set).
         exp_config(None) frees it."""
-        self.trn = self.act = self.dpg = None  # (the library drops the train configurations with the memory)
+        self.trn = self.act = self.dpg = self.spg = None  # (the library drops the train configurations with the memory)
         if not capacity:
             self._chk(self.L.aigar_exp_config(self.h, None))
             self.exp = None
@@ -739,7 +747,7 @@ class Stepper:
         conv layers in front (aigar_net_config_cnn): the states are then images [side, side,
         channels] and n_in is n_flat.  The weights are zero until net_set_weights.
         net_config(None) turns it off."""
-        self.trn = self.crit = self.act = self.dpg = None  # (the library drops the train configurations and the critic with the network)
+        self.trn = self.crit = self.act = self.dpg = self.spg = None  # (the library drops the train configurations and the critic with the network)
         if spec is None:
             self._chk(self.L.aigar_net_config(self.h, None))
             self.net = self.conv = None
@@ -802,7 +810,8 @@ class Stepper:
     # ---- the three trainers' shared plumbing: kind is the entry points' prefix
     _TRAINERS = {"train": ("trn", "no training is configured (train_config)"),
                  "actrain": ("act", "no CACLA training is configured (actrain_config)"),
-                 "dpg": ("dpg", "no DPG training is configured (dpg_config)")}
+                 "dpg": ("dpg", "no DPG training is configured (dpg_config)"),
+                 "spg": ("spg", "no SPG training is configured (spg_config)")}
 
     def _need_trainer(self, kind, what):
         """The batch of the configured trainer of this kind; what: the caller, for the message."""
@@ -872,7 +881,7 @@ class Stepper:
         the acting network's n_in (aigar_critic_config).  The weights are zero until
         critic_set_weights.  critic_config(None) turns it off."""
         config = getattr(self.L, _entry)
-        self.act = self.dpg = None  # (the library drops the train configurations with the critic)
+        self.act = self.dpg = self.spg = None  # (the library drops the train configurations with the critic)
         if spec is None:
             self._chk(config(self.h, None))
             self.crit = None
@@ -976,6 +985,7 @@ class Stepper:
                              float(beta1), float(beta2), float(epsilon), float(discount), float(tau), float(q_increase))
         self._chk(self.L.aigar_dpg_config(self.h, C.byref(prm)))
         self.dpg = int(batch)
+        self.spg = None  # (the library drops an SPG configuration for it)
 
     def dpg_step(self, n=1, u=None):
         """n DPG training steps, one graph replay each (aigar_dpg_step); u as train_step's."""
@@ -997,6 +1007,62 @@ class Stepper:
 
     def dpg_reset(self):
         self._trainer_call("dpg", "reset")
+
+    # ---- the SPG trainer (include/aigar.h: aigar_spg*)
+    def spg_config(self, batch=32, min_size=0, target_steps=0, critic_lr=5e-4, actor_lr=1e-4, beta1=0.9, beta2=0.999,
+                   epsilon=1e-7, discount=0.9, tau=0.001, samples=5, moving=True, replace=True, prio_evals=True,
+                   fused=True, noise=0.1, noise_decay=1.0, seed=0):
+        """The SPG trainer of the handle's actor and Q(s, a) critic on its replay memory
+        (aigar_spg_config): DPG's critic half, then a search of `samples` Gaussian candidates a row
+        around the best action so far (moving) or the actor's, and the actor's regression towards
+        the winners.  Needs what dpg_config needs and, with replace, exp_config(extra=True).  It
+        and dpg_config exclude each other.  spg_config(None) turns it off."""
+        if batch is None:
+            self._chk(self.L.aigar_spg_config(self.h, None))
+            self.spg = None
+            return
+        prm = _abi.SpgParams(int(batch), int(min_size), int(target_steps), 0, float(critic_lr), float(actor_lr),
+                             float(beta1), float(beta2), float(epsilon), float(discount), float(tau), 0.0, int(samples),
+                             int(bool(moving)), int(bool(replace)), int(bool(prio_evals)), int(bool(fused)), 0,
+                             float(noise), float(noise_decay), int(seed) & (2 ** 64 - 1))
+        self._chk(self.L.aigar_spg_config(self.h, C.byref(prm)))
+        self.spg = (int(batch), int(samples))
+        self.dpg = None  # (the library drops a DPG configuration for it)
+
+    def spg_step(self, n=1, u=None, zu=None):
+        """n SPG training steps, one graph replay each (aigar_spg_step); u as train_step's; zu:
+        None (the search's own Philox draws) or a device tensor [n, batch, samples, 2, 16, 2]
+        float64 of uniforms in [0, 1)."""
+        batch, k = self._need_trainer("spg", "spg_step")
+        up = self._dev_ptr(u, (int(n), batch), ("float64",), "spg_step", optional=True)
+        zp = None if k == 0 else self._dev_ptr(zu, (int(n), batch, k, 2, 16, 2), ("float64",), "spg_step", optional=True)
+        self._trainer_call("spg", "step", int(n), up, zp)
+
+    def spg_info(self):
+        """The SPG trainer's counters (aigar_spg_info: the one synchronising read)."""
+        v = (C.c_int64 * 8)()
+        self._trainer_call("spg", "info", v)
+        return {"steps": v[0], "skipped": v[1], "since_target": v[2], "actor_steps": v[3], "actor_skipped": v[4],
+                "actor_empty": v[5], "selected": v[6]}
+
+    def spg_td(self, td=None, idx=None):
+        """The last drawn step's TD errors and memory indices into the device tensors td [batch]
+        float64 and idx [batch] int64."""
+        batch, _ = self._need_trainer("spg", "spg_td")
+        self._trainer_call("spg", "td", *[self._dev_ptr(t, (batch,), (dt,), "spg_td", optional=True)
+                                          for t, dt in ((td, "float64"), (idx, "int64"))])
+
+    def spg_noise_ptr(self):
+        """The device address of the search noise's double (aigar_spg_noise)."""
+        p = C.c_void_p()
+        self._trainer_call("spg", "noise", C.byref(p))
+        return int(p.value)
+
+    def spg_sync_target(self):
+        self._trainer_call("spg", "sync_target")
+
+    def spg_reset(self):
+        self._trainer_call("spg", "reset")
 
     def net_forward(self, x, out):
         """The network alone on device tensors (aigar_net_forward): x [rows, n_in] float64 /

@@ -60,6 +60,7 @@ using namespace aigar;
 #include "train.inc"
 #include "actrain.inc"
 #include "dpg.inc"
+#include "spg.inc"
 
 static thread_local std::string g_err;
 static int fail(const char *fmt, ...) {
@@ -158,10 +159,11 @@ struct TileKey {  // aigar_tile_begin, aigar_tile_end: the tick before the first
   int dtype;           // -1: no observation
 };
 struct TrainKey {  // aigar_*_step: one training step (every buffer is the train configuration's own)
-  int kind;   // whose step it is: kTrainQ, kTrainCacla, kTrainDpg
+  int kind;   // whose step it is: kTrainQ, kTrainCacla, kTrainDpg, kTrainSpg
   int has_u;  // the draws come from the handle's u row (the caller's draws are copied there)
+  int has_zu;  // SPG: the search's uniforms come from the trainer's zu rows (the caller's are copied there)
 };
-enum { kTrainQ, kTrainCacla, kTrainDpg };
+enum { kTrainQ, kTrainCacla, kTrainDpg, kTrainSpg };
 struct EnvKey {  // aigar_env_step*: one learner decision
   const double *act;
   int n_act, enable_split, skip, dtype;
@@ -325,6 +327,7 @@ struct aigar_handle {
   Train trn;     // aigar_train_config: Q-learning (train.inc)
   ACTrain act;   // aigar_actrain_config: CACLA (actrain.inc)
   DPGTrain dpg;  // aigar_dpg_config: DPG (dpg.inc)
+  SPGTrain spg;  // aigar_spg_config: SPG on DPG's critic half (spg.inc)
   DevBlock trn_mem;
   KeyedSlot<TrainKey> train;
   GraphSlot *const slots[8] = {&step, &run, &run_u, &env, &tb, &te, &tr, &train};
@@ -1479,6 +1482,7 @@ static void trainer_free(aigar_handle *h) {
   h->trn = Train{};
   h->act = ACTrain{};
   h->dpg = DPGTrain{};
+  h->spg = SPGTrain{};
 }
 static void critic_free(aigar_handle *h) {
   if (!h->trn.batch) trainer_free(h);  // (Q-learning trains without the critic: it stays)
@@ -2329,6 +2333,9 @@ static int need_act(aigar_handle *h, const char *who) {
 static int need_dpg(aigar_handle *h, const char *who) {
   return need(h, h && h->dpg.batch, who, "no DPG training is configured (aigar_dpg_config)");
 }
+static int need_spg(aigar_handle *h, const char *who) {
+  return need(h, h && h->spg.d.batch, who, "no SPG training is configured (aigar_spg_config)");
+}
 
 // A *_config's parameter checks (before the handle: a bad set has its own message), in the order
 // every trainer reports them: the sizes, its own integers, the learning rates, Adam's constants
@@ -2465,23 +2472,28 @@ static void launch_net_update(hipStream_t s, const Net &n, const Train &v) {
 
 // aigar_*_step after its need_*: n_steps replays of the kind's step graph, each after the copy of
 // its draws into the view's u row.
+// SPG: zu, the search's uniforms, zu_n doubles a step into zu_row; its launch gets has_u | has_zu << 1.
 static int trainer_step(aigar_handle *h, const char *who, int kind, int n_steps, const double *u, const Train &v,
-                        void (*launch)(aigar_handle *, hipStream_t, int)) {
+                        void (*launch)(aigar_handle *, hipStream_t, int), const double *zu = nullptr,
+                        double *zu_row = nullptr, size_t zu_n = 0) {
   if (n_steps < 1) return fail("%s: n_steps = %d is below 1", who, n_steps);
   HIPCHK(hipSetDevice(h->cfg.device));
   TrainKey k;
   key_clear(k);
   k.kind = kind;
   k.has_u = u ? 1 : 0;
+  k.has_zu = zu ? 1 : 0;
+  const int has = k.has_u | k.has_zu << 1;
   const bool graph = h->use_graph;
-  if (graph && !h->train.ensure(h, k, [&](hipStream_t cs) { launch(h, cs, k.has_u); }))
+  if (graph && !h->train.ensure(h, k, [&](hipStream_t cs) { launch(h, cs, has); }))
     return fail("%s: graph capture failed", who);
   Mark m(h, who);
   const size_t B = (size_t)v.batch;
   for (int i = 0; i < n_steps; i++) {
     if (u) HIPCHK(hipMemcpyAsync(v.u, u + (size_t)i * B, B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (zu) HIPCHK(hipMemcpyAsync(zu_row, zu + (size_t)i * zu_n, zu_n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     if (graph) HIPCHK(h->train.launch(h));
-    else launch(h, h->stream, k.has_u);
+    else launch(h, h->stream, has);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -2969,9 +2981,227 @@ extern "C" int aigar_dpg_reset(aigar_handle *h) {
   return 0;
 }
 
+// ------------------------------------------------------------ SPG: the sampled search on DPG's critic half
+static_assert(sizeof(SPGTrain) + sizeof(Net) + sizeof(Dev) <= 4096, "k_spg_search's arguments");
+static_assert(sizeof(SPGTrain) + 2 * sizeof(Net) <= 4096, "k_spg_tail's arguments");
+static_assert(AIGAR_SPG_MAX_SAMPLES == kSpgMaxSamples, "the header's limit is spg.inc's");
+static_assert(sizeof(aigar_spg_params) == 128, "aigar_spg_params is part of the ABI");
+
+extern "C" int aigar_spg_config(aigar_handle *h, const aigar_spg_params *p) {
+  const char *who = "spg_config";
+  if (p) {
+    if (check_train_sizes(who, p)) return -1;
+    if (p->reserved != 0) return fail("spg_config: reserved = %d must be 0", p->reserved);
+    if (p->samples < 0 || p->samples > AIGAR_SPG_MAX_SAMPLES)
+      return fail("spg_config: samples = %d is outside 0..%d", p->samples, AIGAR_SPG_MAX_SAMPLES);
+    if (p->moving != 0 && p->moving != 1) return fail("spg_config: moving = %d must be 0 or 1", p->moving);
+    if (p->replace != 0 && p->replace != 1) return fail("spg_config: replace = %d must be 0 or 1", p->replace);
+    if (p->prio_evals != 0 && p->prio_evals != 1) return fail("spg_config: prio_evals = %d must be 0 or 1", p->prio_evals);
+    if (p->fused != 0 && p->fused != 1) return fail("spg_config: fused = %d must be 0 or 1", p->fused);
+    if (p->pad != 0) return fail("spg_config: pad = %d must be 0", p->pad);
+    if (check_positive(who, "critic_lr", p->critic_lr) || check_positive(who, "actor_lr", p->actor_lr) ||
+        check_train_adam(who, p))
+      return -1;
+    if (!(p->tau >= 0 && p->tau <= 1)) return fail("spg_config: tau = %g is outside [0, 1]", p->tau);
+    if (!(fabs(p->q_increase) < __builtin_inf())) return fail("spg_config: q_increase = %g must be finite", p->q_increase);
+    if (!(p->noise >= 0 && p->noise < __builtin_inf())) return fail("spg_config: noise = %g must be finite and not negative", p->noise);
+    if (!(p->noise_decay > 0 && p->noise_decay <= 1)) return fail("spg_config: noise_decay = %g is outside (0, 1]", p->noise_decay);
+  }
+  if (!h) return fail("null handle");
+  if (p) {
+    if (check_train_net(h, who)) return -1;
+    if (need_crit(h, who)) return -1;
+    if (!h->crit_q) return fail("spg_config: the critic is V(s) (aigar_critic_config), SPG trains Q(s, a) (aigar_qcritic_config)");
+    if (need_exp(h, who)) return -1;
+    if (p->replace && !h->exp.x) return fail("spg_config: replace needs a replay memory with the extra field (AIGAR_EXP_EXTRA)");
+    if (check_train_widths(h, who)) return -1;
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (p || h->spg.d.batch) trainer_free(h);  // (a null p turns off this trainer, not another)
+  if (!p) return 0;
+  SPGTrain sp;
+  DPGTrain &t = sp.d;
+  t.batch = p->batch;
+  t.n_s = h->net.in[0];
+  t.n_act = h->net.out[h->net.n_layers - 1];
+  t.soft = p->tau > 0 ? 1 : 0;
+  t.tau = (float)p->tau;
+  t.keep = (float)(1.0 - p->tau);
+  t.q_increase = p->q_increase;
+  sp.K = p->samples;
+  sp.moving = p->moving;
+  sp.replace = p->replace;
+  sp.prio_evals = p->prio_evals;
+  sp.fused = p->fused;
+  sp.noise0 = p->noise;
+  sp.noise_decay = p->noise_decay;
+  sp.seed = p->seed;
+  bool ok = true;
+  const size_t B = (size_t)p->batch, xrow = (size_t)(t.n_s + t.n_act) * h->exp.esz;
+  const Train s = train_shared(h, ok, p);
+  t.c = train_view(h, ok, s, h->crit, p->critic_lr, true);
+  t.a = train_view(h, ok, s, h->net, p->actor_lr, true);
+  t.c.s = (char *)train_get(h, ok, B * xrow);  // (the critic's first layer reads the packed rows)
+  t.c.s2 = (char *)train_get(h, ok, B * xrow);
+  t.xm = (char *)train_get(h, ok, B * xrow);
+  t.xt = (char *)train_get(h, ok, B * xrow);
+  t.qm = (double *)train_get(h, ok, B * sizeof(double));
+  t.qt = (double *)train_get(h, ok, B * sizeof(double));
+  t.ca = t.c;
+  sp.ex = (double *)train_get(h, ok, B * 4 * sizeof(double));
+  sp.exv = (uint8_t *)train_get(h, ok, B);
+  sp.best = (double *)train_get(h, ok, B * 4 * sizeof(double));
+  sp.cand = (double *)train_get(h, ok, B * 4 * sizeof(double));
+  sp.rows = (double *)train_get(h, ok, B * 4 * sizeof(double));
+  sp.beval = (double *)train_get(h, ok, B * sizeof(double));
+  sp.qmu = (double *)train_get(h, ok, B * sizeof(double));
+  sp.zu = (double *)train_get(h, ok, B * (size_t)std::max(sp.K, 1) * 2 * kNoiseMaxT * 2 * sizeof(double));
+  sp.x = (SCtl *)train_get(h, ok, sizeof(SCtl));
+  if (!ok) {
+    h->trn_mem.release();
+    return fail("spg_config: out of device memory");
+  }
+  hipLaunchKernelGGL(k_spg_clear, dim3(1), dim3(1), 0, h->stream, t.c.ctl, t.a.ctl, sp.x, sp.noise0, 1);
+  HIPCHK(hipGetLastError());
+  h->spg = sp;  // (the blocks are zeroed: every counter starts at 0)
+  return 0;
+}
+
+// One SPG training step's launches on stream s (spg.inc), one linear chain.  has: has_u | has_zu << 1.
+static void launch_spg_step(aigar_handle *h, hipStream_t s, int has) {
+  const SPGTrain &sp = h->spg;
+  const DPGTrain &t = sp.d;
+  const Train &c = t.c, &a = t.a;
+  const Exp &e = h->exp;
+  Net cr = h->crit, ac = h->net;
+  cr.x_dtype = ac.x_dtype = e.dtype;
+  const Net ct = target_net(cr, c), at = target_net(ac, a);
+  const int B = t.batch, has_u = has & 1, has_zu = has >> 1 & 1;
+  // sets: 2, or 1: the first row set alone (k_sa_pack's blocks B .. 2 B - 1 are the second's)
+  auto pack = [&](int sets, const char *s0, const double *a0, int st0, char *o0, const char *s1, const double *a1, int st1,
+                  char *o1) {
+    if (e.dtype == 0)
+      hipLaunchKernelGGL(k_sa_pack<double>, dim3(sets * B), dim3(64), 0, s, B, t.n_s, t.n_act, (const double *)s0, a0, st0,
+                         (double *)o0, (const double *)s1, a1, st1, (double *)o1);
+    else
+      hipLaunchKernelGGL(k_sa_pack<float>, dim3(sets * B), dim3(64), 0, s, B, t.n_s, t.n_act, (const float *)s0, a0, st0,
+                         (float *)o0, (const float *)s1, a1, st1, (float *)o1);
+  };
+  const bool extras = sp.replace && sp.K > 0;
+  launch_draw_fetch(h, s, a, has_u);
+  if (extras)
+    hipLaunchKernelGGL(k_exp_extra_get, dim3((unsigned)(((size_t)B * 4 + 255) / 256)), dim3(256), 0, s, e, a.idx, B, sp.ex,
+                       sp.exv);
+  // the critic half (launch_dpg_step's)
+  launch_net(s, at, a.s2, B, a.q2, nullptr, nullptr);
+  pack(2, a.s, a.a, 4, c.s, a.s2, a.q2, t.n_act, c.s2);
+  launch_net_save(s, cr, B, c.s, c.q, c.hsave);
+  launch_net(s, ct, c.s2, B, c.q2, nullptr, nullptr);
+  hipLaunchKernelGGL(k_td_qe, dim3(1), dim3(kTrainMaxBatch), 0, s, c, e, h->d, cr.n_layers, sp.prio_evals);
+  launch_net_update(s, cr, c);
+  if (e.prio) hipLaunchKernelGGL(k_exp_update, dim3(1), dim3(kExpPlanThreads), 0, s, e, c.idx, c.prio, B);
+  // the search
+  launch_net_save(s, ac, B, a.s, a.q, a.hsave);
+  if (sp.fused) {  // the whole search in one launch, 16 rows a block
+    const dim3 grid((unsigned)(c.bpad / kNetRows)), block(64 * kNetWaves);
+    const int nt0 = (net_out_pad(cr.out[0]) / 16 + kNetWaves - 1) / kNetWaves;
+#define AIGAR_SPG_SEARCH(T, NT) hipLaunchKernelGGL((k_spg_search<T, NT>), grid, block, 0, s, cr, sp, h->d, has_zu)
+    if (e.dtype == 0) {
+      if (nt0 == 1) AIGAR_SPG_SEARCH(double, 1);
+      else if (nt0 == 2) AIGAR_SPG_SEARCH(double, 2);
+      else if (nt0 == 3) AIGAR_SPG_SEARCH(double, 3);
+      else AIGAR_SPG_SEARCH(double, 4);
+    } else {
+      if (nt0 == 1) AIGAR_SPG_SEARCH(float, 1);
+      else if (nt0 == 2) AIGAR_SPG_SEARCH(float, 2);
+      else if (nt0 == 3) AIGAR_SPG_SEARCH(float, 3);
+      else AIGAR_SPG_SEARCH(float, 4);
+    }
+#undef AIGAR_SPG_SEARCH
+  } else {
+    pack(extras ? 2 : 1, a.s, a.q, t.n_act, t.xm, a.s, sp.ex, 4, t.xt);
+    launch_net(s, cr, t.xm, B, sp.qmu, nullptr, nullptr);
+    if (extras) launch_net(s, cr, t.xt, B, t.qt, nullptr, nullptr);
+    hipLaunchKernelGGL(k_spg_pick, dim3(1), dim3(kTrainMaxBatch), 0, s, sp, 1);
+    for (int x = 0; x < sp.K; x++) {
+      if (e.dtype == 0) hipLaunchKernelGGL(k_spg_cand<double>, dim3(B), dim3(64), 0, s, sp, h->d, x, has_zu);
+      else hipLaunchKernelGGL(k_spg_cand<float>, dim3(B), dim3(64), 0, s, sp, h->d, x, has_zu);
+      launch_net(s, cr, t.xm, B, t.qm, nullptr, nullptr);
+      hipLaunchKernelGGL(k_spg_pick, dim3(1), dim3(kTrainMaxBatch), 0, s, sp, 0);
+    }
+  }
+  // the actor half
+  hipLaunchKernelGGL(k_spg_delta, dim3(1), dim3(kTrainMaxBatch), 0, s, sp, h->d, ac.n_layers, t.n_act);
+  launch_net_update(s, ac, a);
+  if (sp.replace) hipLaunchKernelGGL(k_spg_writeback, dim3(1), dim3(kExpPlanThreads), 0, s, sp, e);
+  hipLaunchKernelGGL(k_spg_tail, dim3(64), dim3(256), 0, s, cr, ac, sp);
+}
+
+extern "C" int aigar_spg_step(aigar_handle *h, int n_steps, const double *u, const double *zu) {
+  if (need_spg(h, "spg_step")) return -1;
+  const SPGTrain &sp = h->spg;
+  if (sp.K == 0) zu = nullptr;  // (no sample is drawn)
+  return trainer_step(h, "spg_step", kTrainSpg, n_steps, u, sp.d.a, launch_spg_step, zu, sp.zu,
+                      (size_t)sp.d.batch * sp.K * 2 * kNoiseMaxT * 2);
+}
+
+extern "C" int aigar_spg_info(aigar_handle *h, int64_t info[8]) {
+  if (need_spg(h, "spg_info")) return -1;
+  if (!info) return fail("spg_info: null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  TrainCtl c, a;
+  SCtl x;
+  HIPCHK(hipMemcpyAsync(&c, h->spg.d.c.ctl, sizeof c, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(&a, h->spg.d.a.ctl, sizeof a, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(&x, h->spg.x, sizeof x, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  info[0] = c.t;
+  info[1] = c.skipped;
+  info[2] = c.since;
+  info[3] = a.t;
+  info[4] = a.skipped;
+  info[5] = x.aempty;
+  info[6] = x.sel;
+  info[7] = 0;
+  return 0;
+}
+
+extern "C" int aigar_spg_td(aigar_handle *h, double *td, int64_t *idx) {
+  if (need_spg(h, "spg_td")) return -1;
+  return trainer_td(h, h->spg.d.c, td, idx);
+}
+
+extern "C" int aigar_spg_noise(aigar_handle *h, double **dev) {
+  if (need_spg(h, "spg_noise")) return -1;
+  if (!dev) return fail("spg_noise: null argument");
+  *dev = &h->spg.x->noise;
+  return 0;
+}
+
+extern "C" int aigar_spg_sync_target(aigar_handle *h) {
+  if (need_spg(h, "spg_sync_target")) return -1;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (target_copy(h, h->crit, h->spg.d.c) || target_copy(h, h->net, h->spg.d.a)) return -1;
+  hipLaunchKernelGGL(k_train_clear, dim3(1), dim3(1), 0, h->stream, h->spg.d.c.ctl, 1);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int aigar_spg_reset(aigar_handle *h) {
+  if (need_spg(h, "spg_reset")) return -1;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const SPGTrain &sp = h->spg;
+  if (adam_clear(h, h->crit, sp.d.c) || adam_clear(h, h->net, sp.d.a)) return -1;
+  hipLaunchKernelGGL(k_spg_clear, dim3(1), dim3(1), 0, h->stream, sp.d.c.ctl, sp.d.a.ctl, sp.x, sp.noise0, 0);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // The configured trainer's view of the acting network, or (crit) of the critic.
 static const Train &trainer_view(const aigar_handle *h, bool crit) {
   if (h->dpg.batch) return crit ? h->dpg.c : h->dpg.a;
+  if (h->spg.d.batch) return crit ? h->spg.d.c : h->spg.d.a;
   if (h->act.batch) return crit ? h->act.c : h->act.a;
   return h->trn;
 }
@@ -2988,7 +3218,7 @@ static int net_which(aigar_handle *h, const char *who, int which, int layer, con
   if (crit && !h->crit.n_layers) return fail("%s: no critic is configured (aigar_critic_config)", who);
   const Net &c = crit ? h->crit : h->net;
   if (layer < 0 || layer >= c.n_layers) return fail("%s: layer %d is outside 0..%d", who, layer, c.n_layers - 1);
-  const bool dpg = h->dpg.batch != 0;
+  const bool dpg = h->dpg.batch != 0 || h->spg.d.batch != 0;  // (an SPG configuration serves the codes as DPG's does)
   if (which == 1 && h->act.batch) return fail("%s: which = 1: CACLA keeps no actor target", who);
   if (which > 4 && !dpg && need_act(h, who)) return -1;
   if (which >= 1 && which <= 3 && !dpg && !h->act.batch && need_trn(h, who)) return -1;

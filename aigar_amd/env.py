@@ -170,7 +170,12 @@ _TRAINERS = {
                     "train='dpg' needs continuous=, network= and memory= (DPG on the device's replay memory)",
                     _net.dpg_params, lambda p, n_in, n_act: _net.qcritic_spec(p, n_in=n_in, n_act=n_act),
                     lambda n_in, n_act: n_in + n_act, "qcritic_config"),
+    "spg": _Trainer("continuous",
+                    "search= needs train='dpg', continuous=, network= and memory= (SPG on the DPG trainer's critic)",
+                    _net.spg_params, lambda p, n_in, n_act: _net.qcritic_spec(p, n_in=n_in, n_act=n_act),
+                    lambda n_in, n_act: n_in + n_act, "qcritic_config"),
 }
+_SEARCH_KEYS = ("samples", "moving", "replace", "prio_evals", "fused", "noise", "noise_decay", "seed")
 
 
 class AgarVecEnv:
@@ -255,7 +260,11 @@ class AgarVecEnv:
         self._setup_selection(discrete)
         self._setup_noise(continuous)
         self._setup_network(network)
-        self._setup_trainer(train, critic)
+        self._setup_trainer(train, critic, self._search_option())
+
+    def _search_option(self):
+        """The search= option of the trainer (None here: the keyword is AgarSpgEnv's)."""
+        return None
 
     def _setup_memory(self, memory, continuous):
         g = self._g
@@ -302,7 +311,8 @@ class AgarVecEnv:
                                           "theta": float(g("ORN_UHL_THETA", 0.15)),
                                           "mu": float(g("ORN_UHL_MU", 0)), "dt": float(g("ORN_UHL_DT", 0.01)),
                                           "std": float(g("GAUSSIAN_NOISE", 1.0)),
-                                          "store_raw": g("ALGORITHM", "CACLA") == "CACLA", "seed": self.seed},
+                                          "store_raw": g("ALGORITHM", "CACLA") == "CACLA" and not self._search_option(),
+                                          "seed": self.seed},
                             continuous)
             if cc["noise"] not in _abi.NOISE_TYPES:
                 raise ValueError("continuous: noise must be one of %s" % sorted(_abi.NOISE_TYPES))
@@ -367,10 +377,10 @@ class AgarVecEnv:
             self._net_out = torch.empty((self.NP, n_out), dtype=torch.float64, device=self.dev)
             self.net_output = None
 
-    def _setup_trainer(self, train, critic):
+    def _setup_trainer(self, train, critic, search=None):
         parameters = self.parameters
         self.training = None
-        self._trainer = None  # the Stepper's trainer family that train= configured: "train", "actrain" or "dpg"
+        self._trainer = None  # the Stepper's trainer family that train= configured: "train", "actrain", "dpg" or "spg"
         self.critic = None
         if critic is not None and not (train and self.continuous is not None):
             raise ValueError("critic= needs continuous= and train= (the CACLA or DPG trainer's critic)")
@@ -381,6 +391,11 @@ class AgarVecEnv:
             raise ValueError("train: algorithm = %r: 'dpg' (the other trainers follow from discrete= / continuous=)"
                              % (train["algorithm"],))
         kind = "dpg" if dpg else "actrain" if self.continuous is not None else "train"
+        if search:
+            if not dpg:
+                raise ValueError("search= needs train='dpg' or train=dict(algorithm='dpg', ...) (SPG searches on the DPG "
+                                 "trainer's critic)")
+            kind = "spg"
         if train:  # (explicit only, as memory=)
             row = _TRAINERS[kind]
             if getattr(self, row.needs) is None or self.network is None or self.memory is None:
@@ -392,7 +407,20 @@ class AgarVecEnv:
             tp = row.settings(parameters)
             tp["batch"] = int(self.memory["batch"])
             if isinstance(train, dict):
-                tp = _settings("train", tp, {k: v for k, v in train.items() if k != "algorithm"})
+                own = {k: v for k, v in train.items() if k != "algorithm"}
+                if kind == "spg":  # (the search's settings are search='s, not train='s; it has no q_increase)
+                    if "q_increase" in own:
+                        raise ValueError("train: q_increase = %r: the SPG step has no Q-value increase (search=)"
+                                         % (own["q_increase"],))
+                    tp = dict(_settings("train", {k: v for k, v in tp.items() if k not in _SEARCH_KEYS}, own),
+                              **{k: tp[k] for k in _SEARCH_KEYS})
+                else:
+                    tp = _settings("train", tp, own)
+            if kind == "spg":
+                tp["seed"] = self.seed
+                if not isinstance(search, dict):
+                    search = {}
+                tp.update(_settings("search", {k: tp[k] for k in _SEARCH_KEYS}, search))
             if row.critic_spec is not None:
                 n_in, n_act = int(self.stepper.obs_len), int(self.network.units[-1])
                 cs = row.critic_spec(parameters, n_in, n_act) if critic is None else _net.NetSpec(*critic)
@@ -404,6 +432,7 @@ class AgarVecEnv:
             getattr(self.stepper, kind + "_config")(**tp)
         self.cacla = self._trainer == "actrain"  # (the trainer is the CACLA learner's: DESIGN.md §4m)
         self.dpg = self._trainer == "dpg"  # (... the DPG learner's: §4n)
+        self.spg = self._trainer == "spg"  # (... the SPG learner's, on the DPG learner's critic: §4o)
 
     def _ordered(self, call, *args, **kw):
         """A stepper call outside the decision that reads or writes torch's tensors.  On torch's
@@ -474,7 +503,7 @@ class AgarVecEnv:
             raise RuntimeError("AgarVecEnv was created without continuous= and train= (the CACLA trainer)")
 
     def _need_critic(self):
-        if not (self.cacla or self.dpg):
+        if not (self.cacla or self.dpg or self.spg):
             raise RuntimeError("AgarVecEnv was created without continuous= and train= (the CACLA or DPG trainer)")
 
     def set_critic_weights(self, weights):
@@ -512,7 +541,7 @@ class AgarVecEnv:
         """Q(s, a) of states [rows, n_in] and actions [rows, n_act] (device tensors or arrays) with
         the DPG trainer's critic -> [rows] float64 device tensor.  The row [s, a] is built in the
         states' dtype (float64 unless they are float32)."""
-        if not self.dpg:
+        if not (self.dpg or self.spg):
             raise RuntimeError("AgarVecEnv was created without train='dpg' (the DPG trainer)")
         torch = self.torch
         s = self._float_states(states)
@@ -1033,3 +1062,64 @@ class AgarVecEnv:
 
     def close(self):
         self.stepper.close()
+
+
+class AgarSpgEnv(AgarVecEnv):
+    """AgarVecEnv with the SPG learner's trainer: the keyword `search=` (True, or a
+    dict that overrides samples, moving, replace, prio_evals, fused, noise, noise_decay, seed)
+    beside `train="dpg"` or `train=dict(algorithm="dpg", ...)` selects the SPG step on the DPG
+    trainer's critic: DPG's critic half, then every row's search among the stored action, the
+    action a former search left in the memory's fifth field, the actor's action and `samples`
+    Gaussian candidates, then the actor's regression towards the winners.  `train(n, u, zu)` makes n
+    steps, one graph replay each; `search_noise` is the device double of the search's std (write
+    it to follow a schedule of your own; the device multiplies it by noise_decay after every
+    applied step).  `env.spg` is True and `env.dpg` False; the raw action is not stored
+    (store_raw is off); `train_info()`, `train_td()`, `q_value()`, `get_weights(target=)` and the
+    critic's accessors work as under DPG.  `search=True` reads OCACLA_EXPL_SAMPLES,
+    OCACLA_MOVING_GAUSSIAN, OCACLA_REPLACE_TRANSITIONS, OCACLA_NOISE and OCACLA_NOISE_DECAY and
+    DPG's names for the critic half; what the device does not do is refused by name
+    (aigar_amd.net.spg_params).  With `search=None` this is AgarVecEnv.  The keyword lives here
+    because AgarVecEnv's own signature is part of the facade's recorded surface."""
+
+    def __init__(self, n_players, parameters=None, *, search=None, **options):
+        self._search = search  # (read through _search_option while AgarVecEnv sets the noise and the trainer up)
+        AgarVecEnv.__init__(self, n_players, parameters, **options)
+        self._noise = None
+
+    def _search_option(self):
+        return self._search
+
+    def train(self, n=1, u=None, zu=None):
+        """n training steps.  u as AgarVecEnv.train's; zu: None (the search's own Philox draws) or
+        the search's uniforms [n, batch, samples, 2, 16, 2] in [0, 1) (only with search=)."""
+        if not self.spg:
+            if zu is not None:
+                raise ValueError("train: zu is the SPG search's (search=)")
+            return AgarVecEnv.train(self, n, u)
+        torch = self.torch
+        n = int(n)
+        if n < 1:
+            raise ValueError("train: n must be at least 1")
+        b, k = self.training["batch"], self.training["samples"]
+        if u is not None:
+            u = torch.as_tensor(u, dtype=torch.float64, device=self.dev).reshape(n, b).contiguous()
+        if zu is not None and k:
+            zu = torch.as_tensor(zu, dtype=torch.float64, device=self.dev).reshape(n, b, k, 2, 16, 2).contiguous()
+        self._ordered(self.stepper.spg_step, n, u, zu if k else None)  # (u and zu are freed when this returns)
+
+    @property
+    def search_noise(self):
+        """The device double of the search noise's std as a one-element float64 tensor: no copy,
+        so writing it takes effect at the next step."""
+        if not self.spg:
+            raise RuntimeError("AgarSpgEnv was created without search= (the SPG trainer)")
+        if self._noise is None:
+            self._noise = _device_double(self.torch, self.stepper.spg_noise_ptr(), self.dev)
+        return self._noise
+
+
+def _device_double(torch, address, dev):
+    """A one-element float64 tensor over the device double at `address` (owned by the handle)."""
+    class _Ptr:
+        __cuda_array_interface__ = {"shape": (1,), "typestr": "<f8", "data": (int(address), False), "version": 2}
+    return torch.as_tensor(_Ptr(), device=dev)

@@ -391,3 +391,48 @@ def dpg_params(parameters=None):
             "critic_lr": float(g("DPG_CRITIC_ALPHA", 0.0005)), "actor_lr": float(g("DPG_ACTOR_ALPHA", 0.0001)),
             "beta1": 0.9, "beta2": 0.999, "epsilon": 1e-7, "discount": float(g("DISCOUNT", 0.9)),
             "tau": float(g("DPG_TAU", 0.001)) if soft else 0.0, "q_increase": float(g("DPG_Q_VAL_INCREASE", 2))}
+
+
+def spg_params(parameters=None):
+    """The device's SPG trainer's settings from the reference's parameters: what
+    actorCritic.py does for OCACLA_ENABLED (ALGORITHM "SPG"; an absent ALGORITHM counts as "SPG"
+    here): the critic half under DPG's names, the search under OCACLA_EXPL_SAMPLES,
+    OCACLA_MOVING_GAUSSIAN, OCACLA_REPLACE_TRANSITIONS, OCACLA_NOISE and OCACLA_NOISE_DECAY, and
+    the memory's priority from Q(s, a) as the reference hands it over (prio_evals).  What
+    dpg_params refuses is refused here too, except OCACLA_ENABLED; so are OCACLA_ONLINE_SAMPLES,
+    Orn-Uhl search noise and CNN_REPR, each by its name."""
+    g = lambda n, d: _get(parameters, n, d)
+    if g("ALGORITHM", "SPG") != "SPG":
+        raise ValueError("spg: ALGORITHM = %r: this is the device's SPG trainer" % (g("ALGORITHM", "SPG"),))
+    if g("OCACLA_ONLINE_SAMPLES", 0):
+        raise ValueError("spg: OCACLA_ONLINE_SAMPLES = %r: the decision samples no actions on the device"
+                         % (g("OCACLA_ONLINE_SAMPLES", 0),))
+    if g("NOISE_TYPE", "Gaussian") != "Gaussian":
+        raise ValueError("spg: NOISE_TYPE = %r: the search's noise is Gaussian" % (g("NOISE_TYPE", "Gaussian"),))
+    if g("CNN_REPR", False):
+        raise ValueError("spg: CNN_REPR = %r: CNN critics are not trained on the device" % (g("CNN_REPR", False),))
+    samples = int(g("OCACLA_EXPL_SAMPLES", 5))
+    if not 0 <= samples <= _abi.SPG_MAX_SAMPLES:
+        raise ValueError("spg: OCACLA_EXPL_SAMPLES = %d: 0..%d" % (samples, _abi.SPG_MAX_SAMPLES))
+    as_dpg = {k: g(k, None) for k in _DPG_NAMES if g(k, None) is not None}
+    as_dpg["ALGORITHM"] = "DPG"
+    as_dpg["OCACLA_ENABLED"] = False
+    try:
+        p = dpg_params(as_dpg)
+    except ValueError as e:
+        raise ValueError("spg" + str(e)[3:]) from None
+    del p["q_increase"]  # (the search has no Q-value increase)
+    p.update(samples=samples, moving=bool(g("OCACLA_MOVING_GAUSSIAN", True)),
+             replace=bool(g("OCACLA_REPLACE_TRANSITIONS", False)), prio_evals=True, fused=True,
+             noise=float(g("OCACLA_NOISE", 1)), noise_decay=float(g("OCACLA_NOISE_DECAY", 0.0004 ** (1.0 / 500000))), seed=0)
+    return p
+
+
+# every setting dpg_params reads (spg_params hands them on)
+_DPG_NAMES = ("OPTIMIZER", "OPTIMIZER_POLICY", "DPG_ACTOR_OPTIMIZER", "CACLA_UPDATE_ON_NEGATIVE_TD", "CACLA_CRITIC_WEIGHT_DECAY",
+              "CACLA_OFF_POLICY_CORR", "ACTOR_IS", "AC_ACTOR_TDE", "AC_DELAY_ACTOR_TRAINING", "AC_ACTOR_TRAINING_START",
+              "AMSGRAD", "END_DISCOUNT", "DROPOUT", "GRADIENT_CLIP", "GRADIENT_CLIP_NORM", "USE_ACTION_AS_INPUT", "BATCHNORM",
+              "DPG_USE_CACLA", "DPG_CACLA_ALTERNATION", "DPG_CACLA_INV_ALTERNATION", "DPG_CRITIC_WEIGHT_DECAY",
+              "DPG_ACTOR_NESTEROV", "DPG_FEED_ACTION_IN_LAYER", "DPG_USE_TARGET_MODELS", "DPG_USE_DPG_ACTOR_TRAINING",
+              "NEURON_TYPE", "TD", "SOFT_TARGET_UPDATES", "MEMORY_BATCH_LEN", "NUM_EXPS_BEFORE_TRAIN", "TARGET_NETWORK_STEPS",
+              "DPG_CRITIC_ALPHA", "DPG_ACTOR_ALPHA", "DISCOUNT", "DPG_TAU")

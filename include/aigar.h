@@ -890,6 +890,83 @@ int aigar_dpg_info(aigar_handle *h, int64_t info[8]);
 int aigar_dpg_td(aigar_handle *h, double *td, int64_t *idx);
 int aigar_dpg_sync_target(aigar_handle *h);
 int aigar_dpg_reset(aigar_handle *h);
+/* The SPG (Sampled Policy Gradient) learner's trainer on the device (actorCritic.py
+ * ActorCritic.learn for OCACLA_ENABLED 730-733: train_critic_DPG(get_evals=True) 986-1029,
+ * train_actor_OCACLA 860-919; tests/spg_model.py is the specification in plain
+ * Python).  It trains the Q(s, a) critic of aigar_qcritic_config as aigar_dpg_step does and the
+ * actor by regression towards the best action a per-row search finds.
+ *
+ * One training step on B drawn transitions (s, a[4], rew, s2, done, w, idx, extra[4], valid):
+ *   critic half: aigar_dpg_step's, entry for entry (mu2, q2, q = Q([s, a]), td, delta_L, backward,
+ *   Adam with critic_lr and t_c).  A prioritized memory gets |q_r| + 1e-4 with prio_evals = 1
+ *   (the reference: get_evals hands Q(s, a) to the memory in the TD error's place) and
+ *   |td_r| + 1e-4 with prio_evals = 0;
+ *   search, every row on its own, with the critic as just updated and the actor as it is; every
+ *   comparison is a float64 `>` (a NaN never wins); an action entering the critic is its float64
+ *   value rounded once to float32:
+ *     mu = forward(s, actor) with the activations kept; qmu = Q([s, mu]);
+ *     best = a_r[:n_act], best_eval = q_r (the value from before the critic's update);
+ *     when samples = K > 0: with replace and a valid extra, qe = Q([s, extra[:n_act]]) and the
+ *     extra is taken if qe > best_eval; mu is taken if qmu > best_eval; then for x = 0 .. K-1:
+ *     cand = clip(base + noise z, 0, 1), base = best when moving, else mu; z from numpy's legacy
+ *     Gaussian as aigar_noise's (pair 0 gives values 0 and 1, pair 1 values 2 and 3, at most 16
+ *     attempts a pair; an exhausted pair is (0, 0) and sets AIGAR_WARN_NOISE_EXHAUSTED on arena
+ *     0; the clip leaves -0.0 alone); cand is taken if Q([s, cand]) > best_eval;
+ *     the row is selected iff best_eval > qmu;
+ *   actor half: count = the selected rows.  count == 0: nothing is trained, t_a stays, the half
+ *   is counted as empty.  Else delta_L[r][j] = float32(((2.0 (mu_rj - best_rj)) / (n_out count))
+ *   (mu_rj (1.0 - mu_rj))) for the selected rows and +0.0f for the others, backward, Adam with
+ *   actor_lr and t_a.  No importance weights;
+ *   write-back (replace): every drawn slot's extra becomes valid and holds best padded with zeros
+ *   for a selected row and a_r otherwise; the last entry of a repeated index wins;
+ *   tail: aigar_dpg_step's counters and target updates (soft with tau > 0, else the due hard copy
+ *   of both targets), then noise <- noise * noise_decay, one float64 multiply on the device
+ *   double that holds the search noise.
+ * Skips are aigar_dpg_step's: a small memory or a non-finite td skips the whole step (nothing
+ * changes, no extra is written, the noise does not decay; the latter with
+ * AIGAR_WARN_TRAIN_NONFINITE); a non-finite actor delta skips the actor half only (counted; the
+ * write-back stays).  A noise outside [0, inf) counts as 0 with AIGAR_WARN_NOISE_NONFINITE.
+ * Differences from the reference: the actor trains from the first step (no
+ * AC_ACTOR_TRAINING_START); both targets are updated (the reference's SPG actor target never
+ * moves and its soft update is DPG-only); the write-back does not depend on the memory being
+ * prioritized; Gaussian search noise only; the search's draws are the caller's or order-free
+ * Philox, not numpy's stream; samples <= AIGAR_SPG_MAX_SAMPLES.
+ *
+ * aigar_spg_config: the parameters are checked before the handle, each refusal with its own
+ * message (aigar_dpg_config's; samples 0..8; moving, replace, prio_evals, fused 0 or 1 -- fused = 1
+ * runs the search in one kernel that evaluates the critic's first-layer chunks below the actions once a row, with
+ * the same results bit for bit; pad 0; noise finite and >= 0;
+ * noise_decay in (0, 1]; q_increase is unused but must be finite).  It needs what
+ * aigar_dpg_config needs and, with replace, a memory with AIGAR_EXP_EXTRA.  It and
+ * aigar_dpg_config exclude each other: configuring one drops the other, and whatever drops a
+ * DPG configuration drops this one.  NULL turns it off.
+ * aigar_spg_step: u as aigar_dpg_step's; zu NULL or the DEVICE buffer [n_steps][batch][samples]
+ * [2][16][2] of the search's uniforms in [0, 1) (sample x of row r: pair, attempt, the two
+ * values).  NULL: Philox4x64-10 under arena 0's key at the counter (row, 12 | pair << 8 |
+ * b << 16 | x << 24, the ordinal of the step -- applied or skipped -- since the configuration
+ * or the last aigar_spg_reset, seed); block b holds attempts 2 b and 2 b + 1.
+ * aigar_spg_info: {critic steps applied, steps skipped, steps since the hard copy, actor steps
+ * applied (t_a), actor halves skipped, actor halves empty, rows selected by the last applied
+ * step, 0}; a synchronising read.  aigar_spg_td: as aigar_dpg_td (td either way).
+ * aigar_spg_noise: the DEVICE address of the noise double (the caller may read and write it in
+ * stream order).  aigar_spg_sync_target, aigar_spg_reset (both networks' m and v, t_c, t_a and
+ * the steps' ordinal to zero; the noise stays): as DPG's.  aigar_net_get_weights /
+ * aigar_net_pad_check and aigar_critic_forward behave as under a DPG configuration. */
+#define AIGAR_SPG_MAX_SAMPLES 8
+typedef struct aigar_spg_params {
+  int32_t batch, min_size, target_steps, reserved;   /* 1..256, >=0, >=0, 0 */
+  double critic_lr, actor_lr, beta1, beta2, epsilon, discount, tau, q_increase;
+  int32_t samples, moving, replace, prio_evals, fused, pad;  /* 0..8, 0/1, 0/1, 0/1, 0/1, 0 */
+  double noise, noise_decay;                          /* OCACLA_NOISE, OCACLA_NOISE_DECAY */
+  uint64_t seed;                                      /* of the search's own draws */
+} aigar_spg_params;                                   /* 128 bytes */
+int aigar_spg_config(aigar_handle *h, const aigar_spg_params *p);
+int aigar_spg_step(aigar_handle *h, int n_steps, const double *u, const double *zu);
+int aigar_spg_info(aigar_handle *h, int64_t info[8]);
+int aigar_spg_td(aigar_handle *h, double *td, int64_t *idx);
+int aigar_spg_noise(aigar_handle *h, double **dev);
+int aigar_spg_sync_target(aigar_handle *h);
+int aigar_spg_reset(aigar_handle *h);
 /* The sticky quirk bits of one arena since its last reset (a host round trip): 1 a virus
  * made this tick ate, 2 a dead virus was met, 4 a tile observed past its held pellets,
  * 8 AIGAR_WARN_Q_NONFINITE, 16 AIGAR_WARN_NOISE_NONFINITE, 32 AIGAR_WARN_NOISE_EXHAUSTED,
