@@ -78,7 +78,7 @@ struct ArenaCtl {
   int pu_nconv;   // the closing update (written by pellet_close_prep: k_pp_active's arena blocks, tiled ticks k_spawn_plan):
                   // this tick's blob conversions (staged records 0 .. pu_nconv - 1)
   int pu_nsp, pu_spec;  // the closing update: this tick's pellet spawns, drawn ahead (spec_*) or staged (pn)
-  uint32_t dirty;     // DIRTY_*: a virus / blob died this tick (k_spawn_plan compacts)
+  uint32_t dirty;     // DIRTY_*: a virus / blob died this tick (lists_plan compacts)
   int food_undone[3];  // cells that failed reservation round r (index r % 3)
   uint32_t pl_epoch;  // k_players look-back epoch / finished-tile ticket
   int pl_ticket;  // pellet rebuild: source counts snapshotted by the scan epilogue
@@ -263,6 +263,8 @@ struct Dev {
   uint8_t *f_done;
   // spawn staging
   int *resp_slot;  // [NP] a dead player's place in this tick's respawn order, -1 = waits
+  int *resp_list;  // [NP] per arena: the player respawning j-th this tick (the first n_spawn_pl entries; written and
+                   // read inside one tick, so no state call carries it)
   // events [A*EVcap][5]: key_hi, key_lo, code, a, b
   int64_t *ev;
   // observation state

@@ -27,14 +27,17 @@
 //                             incl. skip-after-removal, re-activating neighbours on growth)
 //                             opens k_spawn_plan.  Untiled ticks: the player waves also store
 //                             the FOV cache (from the cells before the pass), and one more
-//                             block per arena closes the pellet bookkeeping (spawn counts,
-//                             staged spawns), final since the eat phase
+//                             block per arena settles what is final since the eat phase
+//                             (lists_plan: virus / blob list compaction, the dead list's
+//                             partition, spawnStuff's counts) and closes the pellet
+//                             bookkeeping (staged spawns)
 //   k_spawn_plan/all          spawnStuff               field.py:256-313
 //                             untiled ticks, the tick's last launch: + the closing pellet
 //                             update's row blocks behind the arena blocks (beside the pp
-//                             pass: they share no word with it); the arena block then respawns
-//                             players, spawns viruses and stores the FOV cache entries of the
-//                             players the pp pass changed or that respawned
+//                             pass: they share no word with it); the arena block then executes
+//                             the plan: respawns the listed players, spawns viruses and stores
+//                             the FOV cache entries of the players the pp pass changed or that
+//                             respawned.  Tiled ticks and initialize(): lists_plan runs here
 //   k_pel_update              (tiled ticks only) closing pellet update: the bucket rows whose
 //                             pellets changed are rewritten; extra blocks respawn players (FOV
 //                             cache) and spawn viruses
@@ -4436,45 +4439,16 @@ __device__ void spawn_pos(const Dev &d, int a, double radius, const uint64_t u[4
   oy = (double)yp;
 }
 
-// the arena fields spawn_counts reads, loaded by its thread before the dead
-// list's partition (their load round overlaps it)
+// the arena fields spawn_counts reads, loaded by its thread in lists_plan's
+// head round (n_vir: the caller sets the compacted list's)
 struct SpawnIn {
   int n_pel, n_pel_eaten, n_pnew, n_pel_glob, n_eaten_glob, n_vir;
   int64_t seq_next, tick, stat3, stat5;
   uint64_t ctr_pellet, ctr_virus;
-  int n_spawn_p;  // (spawn_in_rest only: the pellet part's result)
 };
 __device__ __forceinline__ SpawnIn spawn_in(const ArenaCtl &c) {
   return SpawnIn{c.n_pel,    c.n_pel_eaten, c.n_pnew,    c.n_pel_glob, c.n_eaten_glob, c.n_vir,
-                 c.seq_next, c.tick,        c.stat[3],   c.stat[5],    c.ctr_pellet,   c.ctr_virus, 0};
-}
-// The untiled tick closes its pellet bookkeeping early (k_pp_active's arena
-// blocks: spawn_counts_pel, pellet_close_prep; nothing after the eat phase
-// touches a pellet), so the row blocks can run beside the pp pass.  Each half
-// loads only its own fields: the pellet half a launch before the row blocks,
-// the rest in k_spawn_plan, which must not read the words the row blocks of its
-// own launch change (n_pel) -- seq_next stays untouched in between.
-__device__ __forceinline__ SpawnIn spawn_in_pel(const ArenaCtl &c) {
-  SpawnIn in{};
-  in.n_pel = c.n_pel;
-  in.n_pel_eaten = c.n_pel_eaten;
-  in.n_pnew = c.n_pnew;
-  in.n_pel_glob = c.n_pel_glob;
-  in.n_eaten_glob = c.n_eaten_glob;
-  in.seq_next = c.seq_next;
-  in.stat3 = c.stat[3];
-  in.stat5 = c.stat[5];
-  in.ctr_pellet = c.ctr_pellet;
-  return in;
-}
-__device__ __forceinline__ SpawnIn spawn_in_rest(const ArenaCtl &c) {
-  SpawnIn in{};
-  in.n_vir = c.n_vir;
-  in.seq_next = c.seq_next;
-  in.tick = c.tick;
-  in.ctr_virus = c.ctr_virus;
-  in.n_spawn_p = c.n_spawn_p;
-  return in;
+                 c.seq_next, c.tick,        c.stat[3],   c.stat[5],    c.ctr_pellet,   c.ctr_virus};
 }
 __device__ __forceinline__ int spawn_counts_pel(const Dev &d, int a, int init, const SpawnIn &in);
 __device__ __forceinline__ int spawn_counts_rest(const Dev &d, int a, int init, int n_resp, int n_wait, const SpawnIn &in,
@@ -4506,13 +4480,162 @@ __device__ __forceinline__ void pellet_close_prep(const Dev &d, int a) {
   __syncthreads();  // (spawn_pellet_at reads n_pnew)
   if (threadIdx.x == 0) pellet_close_words(c, nconv, nsp);
 }
-// k_pp_active (pp_active_own above), here for the spawn counts it closes.
+// ---------------------------------------------------- the tick's lists and plan
+// What the eat phase leaves final, by one block of the arena (any multiple of 64
+// threads; sh >= 32 ints, gcnt the small grid's counts): the virus and blob lists
+// are compacted, the dead list is partitioned and spawnStuff's counts are taken.
+// The pp pass that follows removes and grows player cells only, and every player
+// it kills waits a tick (p_respawn = 1, appended at c.n_dead): the respawn order,
+// the waiters' places and every count are decided by what is here before it.
+// Untiled ticks run this in k_pp_active's launch, ahead of the pass; tiled ticks
+// and initialize() in k_spawn_plan.
+//
+// order-preserving compaction of one list of n entries (KIND 0: viruses, 1: blobs;
+// list order == creation order); returns the new length
+template <int KIND>
+__device__ __forceinline__ int list_compact(const Dev &d, int a, int n, int *sh) {
+  const int T = blockDim.x, tid = threadIdx.x;
+  const int cap = KIND == 0 ? d.Vcap : d.Ecap;
+  int out = 0;
+  for (int base = 0; base < n; base += T) {
+    int i = base + tid;
+    size_t g = (size_t)a * cap + i;
+    bool alive = i < n && ((KIND == 0 ? d.v_flags[g] : d.b_flags[g]) & F_ALIVE);
+    double f0 = 0, f1 = 0, f2 = 0, f3 = 0, f4 = 0, f5 = 0, f6 = 0, f7 = 0;
+    int svc = 0, col = -1;
+    int64_t s = 0, e = 0;
+    uint32_t fl = 0;
+    if (alive) {
+      if (KIND == 0) {
+        f0 = d.v_x[g]; f1 = d.v_y[g]; f2 = d.v_m[g]; f3 = d.v_r[g]; f4 = d.v_vx[g]; f5 = d.v_vy[g];
+        f6 = d.v_svx[g]; f7 = d.v_svy[g]; svc = d.v_svc[g]; s = d.v_seq[g]; fl = d.v_flags[g];
+      } else {
+        f0 = d.b_x[g]; f1 = d.b_y[g]; f2 = d.b_m[g]; f3 = d.b_r[g]; f4 = d.b_vx[g]; f5 = d.b_vy[g];
+        f6 = d.b_svx[g]; f7 = d.b_svy[g]; svc = d.b_svc[g]; s = d.b_seq[g]; e = d.b_ej[g]; fl = d.b_flags[g];
+        col = d.b_col[g];
+      }
+    }
+    int chunk;
+    const int pos = out + block_rank(alive, sh, &chunk);  // (all loads of this chunk are done)
+    if (alive) {
+      size_t o = (size_t)a * cap + pos;
+      if (KIND == 0) {
+        d.v_x[o] = f0; d.v_y[o] = f1; d.v_m[o] = f2; d.v_r[o] = f3; d.v_vx[o] = f4; d.v_vy[o] = f5;
+        d.v_svx[o] = f6; d.v_svy[o] = f7; d.v_svc[o] = svc; d.v_seq[o] = s; d.v_flags[o] = fl;
+      } else {
+        d.b_x[o] = f0; d.b_y[o] = f1; d.b_m[o] = f2; d.b_r[o] = f3; d.b_vx[o] = f4; d.b_vy[o] = f5;
+        d.b_svx[o] = f6; d.b_svy[o] = f7; d.b_svc[o] = svc; d.b_seq[o] = s; d.b_ej[o] = e; d.b_flags[o] = fl;
+        d.b_col[o] = col;
+      }
+    }
+    out += chunk;
+    __syncthreads();
+  }
+  // clear the tail flags
+  for (int i = out + tid; i < n; i += T) {
+    size_t g = (size_t)a * cap + i;
+    if (KIND == 0) d.v_flags[g] = 0;
+    else d.b_flags[g] = 0;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    if (KIND == 0) d.ctl[a].n_vir = out;
+    else d.ctl[a].n_blob = out;
+  }
+  __syncthreads();
+  return out;
+}
+// blobs die every tick (stopped ones turn into pellets): the list keeps its
+// holes -- every consumer tests F_ALIVE and orders by seq -- until they are
+// half of it or it nears its capacity, so most ticks skip the pass -- but
+// never when the next tick's ejections could overflow the holes' list: every
+// player cell may eject once (field.py:134-146), and a split may double the
+// cells first, so the bound is 2 x this tick's cell-grid total (ncell)
+__device__ __forceinline__ bool blob_compact_due(const Dev &d, int n_blob, int n_blob_live, int ncell) {
+  if (n_blob < 2 * n_blob_live + 256 && n_blob < d.Ecap / 2) return n_blob + min(2 * ncell, kMaxCells * d.B) > d.Ecap;
+  return true;
+}
+// spawnPlayers' dead list (deadPlayers in order; respawnTime == 0 respawns),
+// partitioned by the whole block, a chunk of T players per round (a serial loop
+// was one load chain per dead player: ~8 us per greedy tick).  The waiters move
+// to the front in order -- the caller's counts set c.n_dead to their number, so
+// the deaths a later pp pass appends land behind them -- and the respawners go
+// to resp_list in respawn order (resp_list[j] = the player respawning j-th), the
+// untiled tick's k_spawn_plan reads that; every dead player's respawn slot (its
+// place in that order, -1 = waits) is what k_pel_update's player threads read on
+// tiled ticks.  p_first: dead[tid] (tid < B), loaded by the caller in the round
+// of the count.
+__device__ __forceinline__ void dead_partition(const Dev &d, int a, int nd, int p_first, int *sh, int &n_resp,
+                                               int &n_wait) {
+  const int T = blockDim.x, tid = threadIdx.x;
+  int *dl = d.dead + (size_t)a * d.B, *rs = d.resp_slot + (size_t)a * d.B, *rl = d.resp_list + (size_t)a * d.B;
+  n_resp = n_wait = 0;
+  for (int base = 0; base < nd; base += T) {
+    const int i = base + tid;
+    const bool in = i < nd;
+    const int p = base == 0 ? p_first : in ? dl[i] : 0;
+    const bool rsp = in && d.p_respawn[(size_t)a * d.B + p] == 0;
+    int tr, tw;
+    const int rr = block_rank(rsp, sh, &tr);
+    const int rw = block_rank(in && !rsp, sh, &tw);  // (every read of this chunk is done)
+    if (in) rs[p] = rsp ? n_resp + rr : -1;
+    if (rsp) rl[n_resp + rr] = p;
+    if (in && !rsp) dl[n_wait + rw] = p;  // (n_wait + rw <= i: never ahead of an unread entry)
+    n_resp += tr;
+    n_wait += tw;
+  }
+}
+// The step itself.  Everything it reads that no part of it writes comes in ONE
+// load round at its head -- the arena's counts, spawn_counts' fields (thread 0),
+// the cell grid's total for the blob rule and dead[tid], in bounds whatever the
+// count -- so p_respawn[dead[tid]] is the only dependent round before the ranks.
+// Phase marks: k_pp_active's arena block (PTK 3) marks the compaction and the
+// partition, k_spawn_plan (PTK 5) its marks of old.
+template <int PTK>
+__device__ __forceinline__ void lists_plan(const Dev &d, int a, int init, int *sh, int *gcnt PT_PARAMS) {
+  ArenaCtl &c = d.ctl[a];
+  const int tid = threadIdx.x;
+  const int p_first = !init && tid < d.B ? d.dead[(size_t)a * d.B + tid] : 0;
+  const uint32_t dirty = c.dirty;
+  int n_vir = c.n_vir;
+  const int n_blob = c.n_blob, n_blob_live = c.n_blob_live, nd = c.n_dead;
+  const int cc = cgrid_cols(d);
+  const int ncell = d.cstart[(size_t)a * (d.H + 1) + cc * cc];
+  SpawnIn sin{};
+  if (tid == 0) sin = spawn_in(c);
+  // only the lists that lost an entity this tick
+  if (dirty & DIRTY_VIRUS) n_vir = list_compact<0>(d, a, n_vir, sh);
+  if ((dirty & DIRTY_BLOB) && blob_compact_due(d, n_blob, n_blob_live, ncell)) (void)list_compact<1>(d, a, n_blob, sh);
+  // the virus list is compacted: re-index the virus grid for the observations
+  // (membership stays the F_INHASH flag; the viruses spawned later are not hashed)
+  // (unchanged otherwise: viruses do not move after updateViruses, and the ones
+  // appended by splits or spawns are not hashed this tick)
+  if (PTK == 5) PT_MARK(5, 2);
+  if (d.virus_enabled && (dirty & DIRTY_VIRUS)) grid_small_build<2>(d, a, gcnt, sh);
+  if (PTK == 5) PT_MARK(5, 3);
+  if (PTK == 3) PT_MARK(3, 6);
+  int n_resp = 0, n_wait = 0;
+  if (!init) dead_partition(d, a, nd, p_first, sh, n_resp, n_wait);
+  if (PTK == 3) PT_MARK(3, 7);
+  if (tid == 0) {
+    sin.n_vir = n_vir;  // (the compacted list's)
+    spawn_counts(d, a, init, n_resp, n_wait, sin);
+  }
+  __syncthreads();
+  if (PTK == 5) PT_MARK(5, 4);
+}
+// k_pp_active (pp_active_own above), here for the plan it closes.
 // close (untiled ticks; the tiled ones close in k_spawn_plan and k_pel_update):
 // behind the player blocks the grid holds two more kinds, which share no word
 // with them or with each other.
-//  - One block per arena closes the tick's pellet bookkeeping -- the pellet half
-//    of the spawn counts, then pellet_close_prep -- so the closing update's row
-//    blocks can run in the next launch, beside the pp pass.
+//  - One block per arena runs lists_plan -- the list compactions, the dead
+//    list's partition, all of spawnStuff's counts -- and then pellet_close_prep,
+//    so the next launch holds only what needs the pp pass's world: the closing
+//    update's row blocks run beside the pass, and the arena's block of that
+//    launch finds its respawners and counts ready.  Nothing else in this launch
+//    touches a blob or virus record or their grids (the player blocks read the
+//    cell grid and cells, the FOV threads cells), and nothing later in the tick
+//    sets a dirty bit.
 //  - One thread per player stores the FOV cache entry of a live player from
 //    the cells before the pp pass (player_fov), which changes only the few
 //    players it marks; k_spawn_plan's block stores those again.  rmax_cell is
@@ -4530,9 +4653,9 @@ __global__ void __launch_bounds__(256) k_pp_active(Dev d, int close) {
     return;
   }
   if ((int)blockIdx.x >= nblocks) {
+    __shared__ int l_sh[32], l_gcnt[SG_CAP + 1];
     const int a = blockIdx.x - nblocks;
-    if (threadIdx.x == 0) (void)spawn_counts_pel(d, a, 0, spawn_in_pel(d.ctl[a]));
-    __syncthreads();
+    lists_plan<3>(d, a, 0, l_sh, l_gcnt PT_ARGS);
     pellet_close_prep(d, a);
     PT_MARK(3, 5);
     return;
@@ -4541,17 +4664,20 @@ __global__ void __launch_bounds__(256) k_pp_active(Dev d, int close) {
 }
 // pp (tick only): playerPlayerOverlap's serial pass first, by wave 0 of the
 // arena's block (its pending bitmap in the dynamic LDS)
-// close 1 (tiled ticks): then the closing pellet update's step 1 (pellet_close_prep);
-// k_pel_update follows
-// close 2 (untiled ticks: the tick's last launch; the pellet bookkeeping was
-// closed by k_food_commit's fold block): the grid's blocks after the arenas'
-// are the closing update's row blocks (pel_row_update, one per bucket row and
-// arena, on the first PU_T threads with the launch's dynamic LDS), which share
-// no word with the arena blocks -- they run beside the pp pass; the arena's
-// block then finishes spawnStuff itself: the player respawns, the virus
-// spawns, the FOV cache entries of the respawned players and of those the pp
-// pass marked (fov_mark; k_pp_active stored everybody's before the pass), the
-// observe epoch and the tick count.
+// close 0 / 1 (initialize(), tiled ticks): then lists_plan; close 1: then the
+// closing pellet update's step 1 (pellet_close_prep); k_pel_update follows
+// close 2 (untiled ticks: the tick's last launch; k_pp_active's arena block has
+// compacted the lists, partitioned the dead list, taken every count and closed
+// the pellet bookkeeping): the grid's blocks after the arenas' are the closing
+// update's row blocks (pel_row_update, one per bucket row and arena, on the
+// first PU_T threads with the launch's dynamic LDS), which share no word with
+// the arena blocks -- they run beside the pp pass; the arena's block loads the
+// plan (n_spawn_pl, n_spawn_v, resp_list) beside the pass's head round and
+// after the pass only executes it: the virus spawns, the FOV cache entries of
+// the players the pass marked (fov_mark; k_pp_active stored everybody's before
+// the pass), the respawns with their entries, the observe epoch and the tick
+// count.  Nothing is left to fix in the dead list: the pass appended its deaths
+// behind the waiters.
 constexpr int PU_T = 256;  // threads of a row block (the first PU_T of a wider block: the others leave at once)
 struct PelRowLds;
 __device__ __forceinline__ void pel_row_update(const Dev &d, int a, int r, PelRowLds &L PT_PARAMS);
@@ -4570,10 +4696,23 @@ __global__ void __launch_bounds__(1024) k_spawn_plan(Dev d, int init, int64_t *s
     PT_MARK(8, 3);
     return;
   }
-  __shared__ int sflag[1024];
+  __shared__ int sflag[32];
   __shared__ int gcnt[SG_CAP + 1];
   PT_BEGIN(5);
   int a = blockIdx.x;
+  ArenaCtl &c = d.ctl[a];
+  const int T = blockDim.x, tid = threadIdx.x;
+  // close 2: what the previous launch planned, in one load round beside the pp
+  // pass's head round (the pass touches none of these words): the two counts as
+  // scalars and one respawner per thread.  (The tick count and the observe epoch
+  // are not held across the pass: with them the kernel, at its 128 registers
+  // under the pass already, spilled to scratch; thread 0 loads them behind it.)
+  int n_resp = 0, n_spawn_v = 0, rp_first = 0;
+  if (close == 2) {
+    n_resp = __builtin_amdgcn_readfirstlane(c.n_spawn_pl);
+    n_spawn_v = __builtin_amdgcn_readfirstlane(c.n_spawn_v);
+    if (tid < d.B) rp_first = d.resp_list[(size_t)a * d.B + tid];
+  }
   if (pp) {
     extern __shared__ uint32_t pend[];
     __shared__ uint32_t s_odirty[OCC_DW];
@@ -4590,161 +4729,67 @@ __global__ void __launch_bounds__(1024) k_spawn_plan(Dev d, int init, int64_t *s
     PT_SUB(7);
   }
   PT_MARK(5, 1);
-  ArenaCtl &c = d.ctl[a];
-  const int T = blockDim.x, tid = threadIdx.x;
-  // order-preserving compaction of viruses and blobs (list order == creation order),
-  // only for lists that lost an entity this tick
-  const uint32_t dirty = c.dirty;
-  for (int kind = 0; kind < 2; kind++) {
-    if (!(dirty & (kind == 0 ? DIRTY_VIRUS : DIRTY_BLOB))) continue;
-    // blobs die every tick (stopped ones turn into pellets): the list keeps its
-    // holes -- every consumer tests F_ALIVE and orders by seq -- until they are
-    // half of it or it nears its capacity, so most ticks skip this pass -- but
-    // never when the next tick's ejections could overflow the holes' list: every
-    // player cell may eject once (field.py:134-146), and a split may double the
-    // cells first, so the bound is 2 x this tick's cell-grid total
-    if (kind == 1 && c.n_blob < 2 * c.n_blob_live + 256 && c.n_blob < d.Ecap / 2) {
-      const int cc = cgrid_cols(d);
-      const int ncell = d.cstart[(size_t)a * (d.H + 1) + cc * cc];
-      if (c.n_blob + min(2 * ncell, kMaxCells * d.B) <= d.Ecap) continue;
-    }
-    int n = kind == 0 ? c.n_vir : c.n_blob;
-    int cap = kind == 0 ? d.Vcap : d.Ecap;
-    int out = 0;
-    for (int base = 0; base < n; base += T) {
-      int i = base + tid;
-      size_t g = (size_t)a * cap + i;
-      bool alive = i < n && ((kind == 0 ? d.v_flags[g] : d.b_flags[g]) & F_ALIVE);
-      double f0 = 0, f1 = 0, f2 = 0, f3 = 0, f4 = 0, f5 = 0, f6 = 0, f7 = 0;
-      int svc = 0, col = -1;
-      int64_t s = 0, e = 0;
-      uint32_t fl = 0;
-      if (alive) {
-        if (kind == 0) {
-          f0 = d.v_x[g]; f1 = d.v_y[g]; f2 = d.v_m[g]; f3 = d.v_r[g]; f4 = d.v_vx[g]; f5 = d.v_vy[g];
-          f6 = d.v_svx[g]; f7 = d.v_svy[g]; svc = d.v_svc[g]; s = d.v_seq[g]; fl = d.v_flags[g];
-        } else {
-          f0 = d.b_x[g]; f1 = d.b_y[g]; f2 = d.b_m[g]; f3 = d.b_r[g]; f4 = d.b_vx[g]; f5 = d.b_vy[g];
-          f6 = d.b_svx[g]; f7 = d.b_svy[g]; svc = d.b_svc[g]; s = d.b_seq[g]; e = d.b_ej[g]; fl = d.b_flags[g];
-          col = d.b_col[g];
-        }
-      }
-      int chunk;
-      const int pos = out + block_rank(alive, sflag, &chunk);  // (all loads of this chunk are done)
-      if (alive) {
-        size_t o = (size_t)a * cap + pos;
-        if (kind == 0) {
-          d.v_x[o] = f0; d.v_y[o] = f1; d.v_m[o] = f2; d.v_r[o] = f3; d.v_vx[o] = f4; d.v_vy[o] = f5;
-          d.v_svx[o] = f6; d.v_svy[o] = f7; d.v_svc[o] = svc; d.v_seq[o] = s; d.v_flags[o] = fl;
-        } else {
-          d.b_x[o] = f0; d.b_y[o] = f1; d.b_m[o] = f2; d.b_r[o] = f3; d.b_vx[o] = f4; d.b_vy[o] = f5;
-          d.b_svx[o] = f6; d.b_svy[o] = f7; d.b_svc[o] = svc; d.b_seq[o] = s; d.b_ej[o] = e; d.b_flags[o] = fl;
-          d.b_col[o] = col;
-        }
-      }
-      out += chunk;
-      __syncthreads();
-    }
-    // clear the tail flags
-    for (int i = out + tid; i < n; i += T) {
-      size_t g = (size_t)a * cap + i;
-      if (kind == 0) d.v_flags[g] = 0;
-      else d.b_flags[g] = 0;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      if (kind == 0) c.n_vir = out;
-      else c.n_blob = out;
-    }
-    __syncthreads();
+  if (close != 2) {
+    lists_plan<5>(d, a, init, sflag, gcnt PT_ARGS);
+    if (close == 1) pellet_close_prep(d, a);
+    PT_MARK(5, 5);
+    return;
   }
-  // the virus list is compacted: re-index the virus grid for the observations
-  // (membership stays the F_INHASH flag; the viruses spawned below are not hashed)
-  // (unchanged otherwise: viruses do not move after updateViruses, and the ones
-  // appended by splits or spawns are not hashed this tick)
-  PT_MARK(5, 2);
-  if (d.virus_enabled && (dirty & DIRTY_VIRUS)) grid_small_build<2>(d, a, gcnt, sflag);
-  PT_MARK(5, 3);
-  // (the spawn occupancy is built by k_pp_active and kept by the pp pass above)
-  // spawnPlayers' dead list (deadPlayers in order; respawnTime == 0 respawns):
-  // partitioned by the whole block, a chunk of T players per round (a serial
-  // loop was one load chain per dead player: ~8 us per greedy tick); every dead
-  // player's respawn slot (its place in the respawn order, -1 = waits) is
-  // what k_pel_update's player threads read
-  int n_resp = 0, n_wait = 0;
-  SpawnIn sin{};
-  // (spawn_counts' fields: their round overlaps the partition's; close 2: only the
-  // half that is left, none of the words this launch's row blocks change)
-  if (tid == 0) sin = close == 2 ? spawn_in_rest(c) : spawn_in(c);
-  uint32_t ob_ep = 0;  // (the observe epoch rides the same round: its bump below is then a store)
-  if (tid == 0 && close == 2 && a == 0) ob_ep = *d.ob_epoch;
-  if (!init) {
-    const int nd = c.n_dead;
-    int *dl = d.dead + (size_t)a * d.B, *rl = d.resp_slot + (size_t)a * d.B;
-    for (int base = 0; base < nd; base += T) {
-      const int i = base + tid;
-      int p = -1;
-      bool rsp = false;
-      if (i < nd) {
-        p = dl[i];
-        rsp = d.p_respawn[(size_t)a * d.B + p] == 0;
+  // the rest of spawnStuff on the world the pp pass left (occupancy rebuilt
+  // above): one thread per virus spawn, one per player the pass marked, and
+  // then one per respawn
+  for (int j = tid; j < n_spawn_v; j += T) spawn_virus(d, a * d.Vcap + j);
+  // the mark words, eight bits a thread: a marked player that lives gets its
+  // FOV cache entry again.  A mark covers its aliases (arenas of more than
+  // FOVM_BITS players): every one of them that is alive NOW -- no respawn has
+  // been done yet, so a respawner, dead since before the pass, is passed over
+  // here and never read half-written; its own thread stores its entry below.
+  for (int s = tid; s < FOVM_BITS / 8; s += T) {
+    uint32_t m = (fov_marks()[s >> 2] >> ((s & 3) * 8)) & 0xFFu;
+    while (m) {
+      const int b = __ffs(m) - 1;
+      m &= m - 1;
+      for (int p = s * 8 + b; p < d.B; p += FOVM_BITS) {
+        const int gp = a * d.B + p;
+        if (!d.p_alive[gp]) continue;  // (eaten whole by this tick's pass, or dead before it)
+        const Fov f = player_fov(d, gp);
+        fov_store(d, gp, f);
+        if (f.rmax > 0) atomic_max_pos(&c.rmax_cell, f.rmax);
       }
-      int tr, tw;
-      const int rr = block_rank(i < nd && rsp, sflag, &tr);
-      const int rw = block_rank(i < nd && !rsp, sflag, &tw);  // (every read of this chunk is done)
-      if (i < nd) rl[p] = rsp ? n_resp + rr : -1;
-      if (i < nd && !rsp) dl[n_wait + rw] = p;  // (n_wait + rw <= i: never ahead of an unread entry)
-      if (close == 2 && i < nd && rsp) fov_mark(p);  // (respawns below: its FOV cache entry with it)
-      n_resp += tr;
-      n_wait += tw;
     }
   }
-  __shared__ int s_kv;
-  if (tid == 0) {
-    if (close == 2) {
-      s_kv = spawn_counts_rest(d, a, init, n_resp, n_wait, sin, sin.n_spawn_p);
-      c.tick = sin.tick + 1;  // (the tick's last launch; nothing in it reads the word from here on)
-      if (a == 0) *d.ob_epoch = 0x80000000u | ((ob_ep + 1) & 0x7FFFFFFFu);  // (as fov_cache_thread's)
-    } else {
-      spawn_counts(d, a, init, n_resp, n_wait, sin);
-    }
-  }
-  __syncthreads();
+  __syncthreads();  // (the marks' liveness reads are done: respawns may start)
   PT_MARK(5, 4);
-  if (close == 1) {
-    __syncthreads();
-    pellet_close_prep(d, a);
+  int64_t tick = 0;
+  uint32_t ob_ep = 0;  // (the observe epoch rides the tick count's round: its bump is then a store)
+  // (thread 0's one round behind the pass.  Issued earlier, or with the stores
+  // moved behind the respawns, either value lives across a loop and the
+  // kernel spills to scratch: 1448 bytes a lane, measured in the build.)
+  if (tid == 0) {
+    tick = c.tick;
+    if (a == 0) ob_ep = *d.ob_epoch;
   }
-  if (close == 2) {
-    // the rest of spawnStuff on the world the pp pass left (occupancy rebuilt
-    // above): one thread per virus spawn, one per marked player -- a dead one
-    // with a respawn slot respawns (spawn_player), then its thread stores the
-    // FOV cache entry of the end-of-tick state (as respawn_fov_thread: the
-    // respawn and its entry are one thread's work)
-    for (int j = tid; j < s_kv; j += T) spawn_virus(d, a * d.Vcap + j);
-    for (int p = tid; p < d.B; p += T) {
-      if (!fov_marked(p)) continue;
-      const int gp = a * d.B + p;
-      const bool alive = d.p_alive[gp];
-      const int j = d.resp_slot[gp];  // (one round with the liveness; only a dead player's is read)
-      Fov f;
-      if (alive) {
-        f = player_fov(d, gp);
-      } else {
-        if (j < 0) continue;  // (eaten whole by this tick's pp pass, or waiting)
-        double x, y;
-        spawn_player(d, gp, j, 0, &x, &y);
-        // (the one cell it has now, from the registers: no load behind its stores)
-        f = player_fov_of(d, 1, [&](int, double &cx, double &cy, double &cm, double &cr) {
-          cx = x;
-          cy = y;
-          cm = kStartMass;
-          cr = radius_of(kStartMass);
-        });
-      }
-      fov_store(d, gp, f);
-      if (f.rmax > 0) atomic_max_pos(&c.rmax_cell, f.rmax);
-    }
+  if (tid == 0) {
+    c.tick = tick + 1;  // (the tick's last launch; nothing in it reads the word from here on)
+    if (a == 0) *d.ob_epoch = 0x80000000u | ((ob_ep + 1) & 0x7FFFFFFFu);  // (as fov_cache_thread's)
+  }
+  // thread j respawns the j-th of resp_list (spawn_player), then stores the FOV
+  // cache entry of the end-of-tick state (as respawn_fov_thread: the respawn and
+  // its entry are one thread's work)
+  for (int j = tid; j < n_resp; j += T) {
+    const int p = j == tid ? rp_first : d.resp_list[(size_t)a * d.B + j];
+    const int gp = a * d.B + p;
+    double x, y;
+    spawn_player(d, gp, j, 0, &x, &y);
+    // (the one cell it has now, from the registers: no load behind its stores)
+    const Fov f = player_fov_of(d, 1, [&](int, double &cx, double &cy, double &cm, double &cr) {
+      cx = x;
+      cy = y;
+      cm = kStartMass;
+      cr = radius_of(kStartMass);
+    });
+    fov_store(d, gp, f);
+    if (f.rmax > 0) atomic_max_pos(&c.rmax_cell, f.rmax);
   }
   PT_MARK(5, 5);
 }

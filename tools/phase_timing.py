@@ -17,9 +17,13 @@ SO = os.environ.get("AIGAR_PT_SO") or os.path.join(ROOT, "aigar_amd", "libaigar_
 KERNELS = {0: ("k_food_prep", ["", "player", "cell", "pellet walk", "blob walk", "select", "reserve"]),
            1: ("k_players", ["", "player loads", "tail loads", "tail done", "update_player", "look-back", "seq + blobs"]),
            2: ("k_players/x", ["", "head+policy+queue", "cell updates", "arena block", "blob block", "last-block grid"]),
-           3: ("k_pp_active", ["", "player", "cell", "grid test", "fov cache (own blocks)", "pellet close (arena blocks)"]),
+           3: ("k_pp_active", ["", "player", "cell", "grid test", "fov cache (own blocks)",
+                               "counts + pellet close (arena blocks: end)", "lists compacted (arena blocks)",
+                               "dead list partitioned (arena blocks)"]),
            4: ("k_food_commit", ["", "round 1", "r2 | cell list", "r3 | keys+recs", "r4 | eat loop", "rmax atomic", "serial (fold)", "round 7+"]),
-           5: ("k_spawn_plan", ["", "pp serial", "compaction", "virus grid", "spawn counts", "pellet close", "pp closures", "pp turns"]),
+           # (untiled ticks: marks 2 and 3 are not written, 4 is the marked players' FOV entries, 5 the block's end)
+           5: ("k_spawn_plan", ["", "pp pass", "compaction", "virus grid", "spawn counts | marks' fov", "end of block",
+                                "pp closures", "pp turns"]),
            8: ("pellet rows", ["", "first loads", "kill / join lists", "pellets + buckets", "fov cache", "virus spawns", "suffix loaded", "scans done"])}
 
 
