@@ -2339,7 +2339,8 @@ static int need_spg(aigar_handle *h, const char *who) {
 
 // A *_config's parameter checks (before the handle: a bad set has its own message), in the order
 // every trainer reports them: the sizes, its own integers, the learning rates, Adam's constants
-// and the discount, its own doubles.  P: aigar_train_params, aigar_actrain_params, aigar_dpg_params.
+// and the discount, its own doubles.  P: aigar_train_params, aigar_actrain_params, aigar_dpg_params,
+// aigar_spg_params.
 static int check_positive(const char *who, const char *name, double v) {
   return v > 0 && v < __builtin_inf() ? 0 : fail("%s: %s = %g must be positive and finite", who, name, v);
 }
@@ -2373,6 +2374,30 @@ static int check_train_net(aigar_handle *h, const char *who) {
 static int check_train_widths(aigar_handle *h, const char *who) {
   if (h->net.in[0] == h->exp.L) return 0;
   return fail("%s: the network has %d inputs, the memory's states %d values", who, h->net.in[0], h->exp.L);
+}
+
+// What the two Q(s, a) trainers share of both (P: aigar_dpg_params, aigar_spg_params; name: "DPG",
+// "SPG"): the sizes before a trainer's own integers, the rates before its own doubles, and the
+// handle checks up to need_exp, after which come its own and check_train_widths.
+template <class P>
+static int check_qsa_sizes(const char *who, const P *p) {
+  if (check_train_sizes(who, p)) return -1;
+  return p->reserved != 0 ? fail("%s: reserved = %d must be 0", who, p->reserved) : 0;
+}
+template <class P>
+static int check_qsa_rates(const char *who, const P *p) {
+  if (check_positive(who, "critic_lr", p->critic_lr) || check_positive(who, "actor_lr", p->actor_lr) ||
+      check_train_adam(who, p))
+    return -1;
+  if (!(p->tau >= 0 && p->tau <= 1)) return fail("%s: tau = %g is outside [0, 1]", who, p->tau);
+  if (!(fabs(p->q_increase) < __builtin_inf())) return fail("%s: q_increase = %g must be finite", who, p->q_increase);
+  return 0;
+}
+static int check_qsa_handle(aigar_handle *h, const char *who, const char *name) {
+  if (check_train_net(h, who) || need_crit(h, who)) return -1;
+  if (!h->crit_q)
+    return fail("%s: the critic is V(s) (aigar_critic_config), %s trains Q(s, a) (aigar_qcritic_config)", who, name);
+  return need_exp(h, who);
 }
 
 // One zeroed buffer of the trainer's block; null, and ok false from then on, when one is refused
@@ -2440,6 +2465,35 @@ static Train train_view(aigar_handle *h, bool &ok, const Train &s, const Net &c,
   return v;
 }
 
+// A Q(s, a) trainer's settings, views and packed-row buffers (dpg.inc; P as check_qsa_sizes').
+// actor_pass: DPG's actor half runs through the critic, so it also gets mut and, for ca, a
+// TrainCtl of its own; SPG's ca is c.
+template <class P>
+static DPGTrain qsa_setup(aigar_handle *h, bool &ok, const P *p, bool actor_pass) {
+  DPGTrain t;
+  t.batch = p->batch;
+  t.n_s = h->net.in[0];
+  t.n_act = h->net.out[h->net.n_layers - 1];
+  t.soft = p->tau > 0 ? 1 : 0;
+  t.tau = (float)p->tau;
+  t.keep = (float)(1.0 - p->tau);
+  t.q_increase = p->q_increase;
+  const size_t B = (size_t)p->batch, xrow = (size_t)(t.n_s + t.n_act) * h->exp.esz;
+  const Train s = train_shared(h, ok, p);
+  t.c = train_view(h, ok, s, h->crit, p->critic_lr, true);
+  t.a = train_view(h, ok, s, h->net, p->actor_lr, true);
+  t.c.s = (char *)train_get(h, ok, B * xrow);  // (the critic's first layer reads the packed rows)
+  t.c.s2 = (char *)train_get(h, ok, B * xrow);
+  t.xm = (char *)train_get(h, ok, B * xrow);
+  t.xt = (char *)train_get(h, ok, B * xrow);
+  if (actor_pass) t.mut = (double *)train_get(h, ok, B * t.n_act * sizeof(double));
+  t.qm = (double *)train_get(h, ok, B * sizeof(double));
+  t.qt = (double *)train_get(h, ok, B * sizeof(double));
+  t.ca = t.c;
+  if (actor_pass) t.ca.ctl = (TrainCtl *)train_get(h, ok, sizeof(TrainCtl));
+  return t;
+}
+
 // The launches that every trainer's step is made of, on stream s.  The mini-batch into a view's
 // staging rows (replay.inc):
 static void launch_draw_fetch(aigar_handle *h, hipStream_t s, const Train &v, int has_u) {
@@ -2462,12 +2516,39 @@ static void launch_net_save(hipStream_t s, const Net &n, int B, const char *x, d
   if (n.x_dtype == 0) hipLaunchKernelGGL(k_net_save<double>, rows16, net_block, 0, s, n, (const double *)x, B, y, hsave);
   else hipLaunchKernelGGL(k_net_save<float>, rows16, net_block, 0, s, n, (const float *)x, B, y, hsave);
 }
+// [state, action] rows of the memory's dtype (dpg.inc k_sa_pack): `sets` row sets in one launch,
+// 2, or 1: the first alone (the blocks B .. 2 B - 1 are the second's)
+static void launch_sa_pack(hipStream_t s, const DPGTrain &t, int dtype, int sets, const char *s0, const double *a0, int st0,
+                           char *o0, const char *s1, const double *a1, int st1, char *o1) {
+  const int B = t.batch;
+  if (dtype == 0)
+    hipLaunchKernelGGL(k_sa_pack<double>, dim3(sets * B), dim3(64), 0, s, B, t.n_s, t.n_act, (const double *)s0, a0, st0,
+                       (double *)o0, (const double *)s1, a1, st1, (double *)o1);
+  else
+    hipLaunchKernelGGL(k_sa_pack<float>, dim3(sets * B), dim3(64), 0, s, B, t.n_s, t.n_act, (const float *)s0, a0, st0,
+                       (float *)o0, (const float *)s1, a1, st1, (float *)o1);
+}
 // view v's output delta back through n's layers, then every layer's gradient and Adam in place (train.inc)
 static void launch_net_update(hipStream_t s, const Net &n, const Train &v) {
   if (n.n_layers > 1)
     hipLaunchKernelGGL(k_net_bwd, dim3((unsigned)(v.bpad / kNetRows)), dim3(64 * kNetWaves), 0, s, n, v);
   if (n.x_dtype == 0) hipLaunchKernelGGL(k_net_grad_adam<double>, dim3(v.tile0[n.n_layers]), dim3(64), 0, s, n, v);
   else hipLaunchKernelGGL(k_net_grad_adam<float>, dim3(v.tile0[n.n_layers]), dim3(64), 0, s, n, v);
+}
+// The critic half of a Q(s, a) trainer's step, DPG's and SPG's, on the batch in t.a's staging rows
+// (dpg.inc).  cr: the critic, ct / at: the critic's and the actor's targets, of the memory's dtype.
+static void launch_qsa_critic(aigar_handle *h, hipStream_t s, const DPGTrain &t, const Net &cr, const Net &ct, const Net &at,
+                              int prio_evals) {
+  const Train &c = t.c, &a = t.a;
+  const Exp &e = h->exp;
+  const int B = t.batch;
+  launch_net(s, at, a.s2, B, a.q2, nullptr, nullptr);
+  launch_sa_pack(s, t, e.dtype, 2, a.s, a.a, 4, c.s, a.s2, a.q2, t.n_act, c.s2);
+  launch_net_save(s, cr, B, c.s, c.q, c.hsave);
+  launch_net(s, ct, c.s2, B, c.q2, nullptr, nullptr);
+  hipLaunchKernelGGL(k_td_q, dim3(1), dim3(kTrainMaxBatch), 0, s, c, e, h->d, cr.n_layers, prio_evals);
+  launch_net_update(s, cr, c);
+  if (e.prio) hipLaunchKernelGGL(k_exp_update, dim3(1), dim3(kExpPlanThreads), 0, s, e, c.idx, c.prio, B);
 }
 
 // aigar_*_step after its need_*: n_steps replays of the kind's step graph, each after the copy of
@@ -2535,6 +2616,33 @@ __global__ void k_train_clear(TrainCtl *ctl, int target) {  // target: the copy 
   else ctl->t = 0;
 }
 
+// aigar_*_info: a trainer's control blocks to the host, one synchronisation for all of them
+struct CtlRead {
+  void *host;
+  const void *dev;
+  size_t bytes;
+};
+static int read_ctls(aigar_handle *h, std::initializer_list<CtlRead> blocks) {
+  HIPCHK(hipSetDevice(h->cfg.device));
+  for (const CtlRead &b : blocks) HIPCHK(hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// aigar_dpg_* and aigar_spg_* on the trainer's DPGTrain: both targets as copies of their networks ...
+static int qsa_sync_target(aigar_handle *h, const DPGTrain &t) {
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (target_copy(h, h->crit, t.c) || target_copy(h, h->net, t.a)) return -1;
+  hipLaunchKernelGGL(k_train_clear, dim3(1), dim3(1), 0, h->stream, t.c.ctl, 1);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// ... and a reset's first part: both Adam states to zero (the counters are the trainer's own kernel's)
+static int qsa_adam_clear(aigar_handle *h, const DPGTrain &t) {
+  HIPCHK(hipSetDevice(h->cfg.device));
+  return adam_clear(h, h->crit, t.c) || adam_clear(h, h->net, t.a) ? -1 : 0;
+}
+
 // ------------------------------------------------------------ Q-learning trainer
 extern "C" int aigar_train_config(aigar_handle *h, const aigar_train_params *p) {
   const char *who = "train_config";
@@ -2591,10 +2699,8 @@ extern "C" int aigar_train_step(aigar_handle *h, int n_steps, const double *u) {
 extern "C" int aigar_train_info(aigar_handle *h, int64_t info[4]) {
   if (need_trn(h, "train_info")) return -1;
   if (!info) return fail("train_info: null argument");
-  HIPCHK(hipSetDevice(h->cfg.device));
   TrainCtl c;
-  HIPCHK(hipMemcpyAsync(&c, h->trn.ctl, sizeof c, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  if (read_ctls(h, {{&c, h->trn.ctl, sizeof c}})) return -1;
   info[0] = c.t;
   info[1] = c.skipped;
   info[2] = c.since;
@@ -2782,13 +2888,9 @@ extern "C" int aigar_actrain_step(aigar_handle *h, int n_steps, const double *u)
 extern "C" int aigar_actrain_info(aigar_handle *h, int64_t info[8]) {
   if (need_act(h, "actrain_info")) return -1;
   if (!info) return fail("actrain_info: null argument");
-  HIPCHK(hipSetDevice(h->cfg.device));
   TrainCtl c, a;
   ACtl x;
-  HIPCHK(hipMemcpyAsync(&c, h->act.c.ctl, sizeof c, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(&a, h->act.a.ctl, sizeof a, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(&x, h->act.x, sizeof x, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  if (read_ctls(h, {{&c, h->act.c.ctl, sizeof c}, {&a, h->act.a.ctl, sizeof a}, {&x, h->act.x, sizeof x}})) return -1;
   info[0] = c.t;
   info[1] = c.skipped;
   info[2] = c.since;
@@ -2811,10 +2913,8 @@ extern "C" int aigar_actrain_td(aigar_handle *h, double *td, int64_t *idx, int32
 extern "C" int aigar_actrain_var(aigar_handle *h, double *var) {
   if (need_act(h, "actrain_var")) return -1;
   if (!var) return fail("actrain_var: null argument");
-  HIPCHK(hipSetDevice(h->cfg.device));
   ACtl x;
-  HIPCHK(hipMemcpyAsync(&x, h->act.x, sizeof x, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  if (read_ctls(h, {{&x, h->act.x, sizeof x}})) return -1;
   *var = x.var;
   return 0;
 }
@@ -2843,49 +2943,15 @@ static_assert(sizeof(DPGTrain) + 2 * sizeof(Net) + sizeof(Dev) <= 4096, "k_dpg_t
 
 extern "C" int aigar_dpg_config(aigar_handle *h, const aigar_dpg_params *p) {
   const char *who = "dpg_config";
-  if (p) {
-    if (check_train_sizes(who, p)) return -1;
-    if (p->reserved != 0) return fail("dpg_config: reserved = %d must be 0", p->reserved);
-    if (check_positive(who, "critic_lr", p->critic_lr) || check_positive(who, "actor_lr", p->actor_lr) ||
-        check_train_adam(who, p))
-      return -1;
-    if (!(p->tau >= 0 && p->tau <= 1)) return fail("dpg_config: tau = %g is outside [0, 1]", p->tau);
-    if (!(fabs(p->q_increase) < __builtin_inf())) return fail("dpg_config: q_increase = %g must be finite", p->q_increase);
-  }
+  if (p && (check_qsa_sizes(who, p) || check_qsa_rates(who, p))) return -1;
   if (!h) return fail("null handle");
-  if (p) {
-    if (check_train_net(h, who)) return -1;
-    if (need_crit(h, who)) return -1;
-    if (!h->crit_q) return fail("dpg_config: the critic is V(s) (aigar_critic_config), DPG trains Q(s, a) (aigar_qcritic_config)");
-    if (need_exp(h, who)) return -1;
-    if (check_train_widths(h, who)) return -1;
-  }
+  if (p && (check_qsa_handle(h, who, "DPG") || check_train_widths(h, who))) return -1;
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipStreamSynchronize(h->stream));
   if (p || h->dpg.batch) trainer_free(h);  // (a null p turns off this trainer, not another)
   if (!p) return 0;
-  DPGTrain t;
-  t.batch = p->batch;
-  t.n_s = h->net.in[0];
-  t.n_act = h->net.out[h->net.n_layers - 1];
-  t.soft = p->tau > 0 ? 1 : 0;
-  t.tau = (float)p->tau;
-  t.keep = (float)(1.0 - p->tau);
-  t.q_increase = p->q_increase;
   bool ok = true;
-  const size_t B = (size_t)p->batch, xrow = (size_t)(t.n_s + t.n_act) * h->exp.esz;
-  const Train s = train_shared(h, ok, p);
-  t.c = train_view(h, ok, s, h->crit, p->critic_lr, true);
-  t.a = train_view(h, ok, s, h->net, p->actor_lr, true);
-  t.c.s = (char *)train_get(h, ok, B * xrow);  // (the critic's first layer reads the packed rows)
-  t.c.s2 = (char *)train_get(h, ok, B * xrow);
-  t.xm = (char *)train_get(h, ok, B * xrow);
-  t.xt = (char *)train_get(h, ok, B * xrow);
-  t.mut = (double *)train_get(h, ok, B * t.n_act * sizeof(double));
-  t.qm = (double *)train_get(h, ok, B * sizeof(double));
-  t.qt = (double *)train_get(h, ok, B * sizeof(double));
-  t.ca = t.c;
-  t.ca.ctl = (TrainCtl *)train_get(h, ok, sizeof(TrainCtl));
+  const DPGTrain t = qsa_setup(h, ok, p, true);
   if (!ok) {
     h->trn_mem.release();
     return fail("dpg_config: out of device memory");
@@ -2899,32 +2965,16 @@ extern "C" int aigar_dpg_config(aigar_handle *h, const aigar_dpg_params *p) {
 static void launch_dpg_step(aigar_handle *h, hipStream_t s, int has_u) {
   const DPGTrain &t = h->dpg;
   const Train &c = t.c, &a = t.a, &ca = t.ca;
-  const Exp &e = h->exp;
   Net cr = h->crit, ac = h->net;
-  cr.x_dtype = ac.x_dtype = e.dtype;
+  cr.x_dtype = ac.x_dtype = h->exp.dtype;
   const Net ct = target_net(cr, c), at = target_net(ac, a);
   const int B = t.batch;
-  auto pack = [&](const char *s0, const double *a0, int st0, char *o0, const char *s1, const double *a1, int st1, char *o1) {
-    if (e.dtype == 0)
-      hipLaunchKernelGGL(k_sa_pack<double>, dim3(2 * B), dim3(64), 0, s, B, t.n_s, t.n_act, (const double *)s0, a0, st0,
-                         (double *)o0, (const double *)s1, a1, st1, (double *)o1);
-    else
-      hipLaunchKernelGGL(k_sa_pack<float>, dim3(2 * B), dim3(64), 0, s, B, t.n_s, t.n_act, (const float *)s0, a0, st0,
-                         (float *)o0, (const float *)s1, a1, st1, (float *)o1);
-  };
   launch_draw_fetch(h, s, a, has_u);
-  // the critic half
-  launch_net(s, at, a.s2, B, a.q2, nullptr, nullptr);
-  pack(a.s, a.a, 4, c.s, a.s2, a.q2, t.n_act, c.s2);
-  launch_net_save(s, cr, B, c.s, c.q, c.hsave);
-  launch_net(s, ct, c.s2, B, c.q2, nullptr, nullptr);
-  hipLaunchKernelGGL(k_td_q, dim3(1), dim3(kTrainMaxBatch), 0, s, c, e, h->d, cr.n_layers);
-  launch_net_update(s, cr, c);
-  if (e.prio) hipLaunchKernelGGL(k_exp_update, dim3(1), dim3(kExpPlanThreads), 0, s, e, c.idx, c.prio, B);
+  launch_qsa_critic(h, s, t, cr, ct, at, 0);
   // the actor half
   launch_net_save(s, ac, B, a.s, a.q, a.hsave);
   launch_net(s, at, a.s, B, t.mut, nullptr, nullptr);
-  pack(a.s, a.q, t.n_act, t.xm, a.s, t.mut, t.n_act, t.xt);
+  launch_sa_pack(s, t, h->exp.dtype, 2, a.s, a.q, t.n_act, t.xm, a.s, t.mut, t.n_act, t.xt);
   launch_net_save(s, cr, B, t.xm, t.qm, ca.hsave);  // (the critic's update is done: its buffers serve the actor pass)
   launch_net(s, ct, t.xt, B, t.qt, nullptr, nullptr);
   hipLaunchKernelGGL(k_dpg_delta, dim3(1), dim3(kTrainMaxBatch), 0, s, t, h->d, cr.n_layers);
@@ -2943,11 +2993,8 @@ extern "C" int aigar_dpg_step(aigar_handle *h, int n_steps, const double *u) {
 extern "C" int aigar_dpg_info(aigar_handle *h, int64_t info[8]) {
   if (need_dpg(h, "dpg_info")) return -1;
   if (!info) return fail("dpg_info: null argument");
-  HIPCHK(hipSetDevice(h->cfg.device));
   TrainCtl c, a;
-  HIPCHK(hipMemcpyAsync(&c, h->dpg.c.ctl, sizeof c, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(&a, h->dpg.a.ctl, sizeof a, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  if (read_ctls(h, {{&c, h->dpg.c.ctl, sizeof c}, {&a, h->dpg.a.ctl, sizeof a}})) return -1;
   info[0] = c.t;
   info[1] = c.skipped;
   info[2] = c.since;
@@ -2964,18 +3011,13 @@ extern "C" int aigar_dpg_td(aigar_handle *h, double *td, int64_t *idx) {
 
 extern "C" int aigar_dpg_sync_target(aigar_handle *h) {
   if (need_dpg(h, "dpg_sync_target")) return -1;
-  HIPCHK(hipSetDevice(h->cfg.device));
-  if (target_copy(h, h->crit, h->dpg.c) || target_copy(h, h->net, h->dpg.a)) return -1;
-  hipLaunchKernelGGL(k_train_clear, dim3(1), dim3(1), 0, h->stream, h->dpg.c.ctl, 1);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return qsa_sync_target(h, h->dpg);
 }
 
 extern "C" int aigar_dpg_reset(aigar_handle *h) {
   if (need_dpg(h, "dpg_reset")) return -1;
-  HIPCHK(hipSetDevice(h->cfg.device));
   const DPGTrain &t = h->dpg;
-  if (adam_clear(h, h->crit, t.c) || adam_clear(h, h->net, t.a)) return -1;
+  if (qsa_adam_clear(h, t)) return -1;
   hipLaunchKernelGGL(k_dpg_clear, dim3(1), dim3(1), 0, h->stream, t.c.ctl, t.a.ctl);
   HIPCHK(hipGetLastError());
   return 0;
@@ -2990,8 +3032,7 @@ static_assert(sizeof(aigar_spg_params) == 128, "aigar_spg_params is part of the 
 extern "C" int aigar_spg_config(aigar_handle *h, const aigar_spg_params *p) {
   const char *who = "spg_config";
   if (p) {
-    if (check_train_sizes(who, p)) return -1;
-    if (p->reserved != 0) return fail("spg_config: reserved = %d must be 0", p->reserved);
+    if (check_qsa_sizes(who, p)) return -1;
     if (p->samples < 0 || p->samples > AIGAR_SPG_MAX_SAMPLES)
       return fail("spg_config: samples = %d is outside 0..%d", p->samples, AIGAR_SPG_MAX_SAMPLES);
     if (p->moving != 0 && p->moving != 1) return fail("spg_config: moving = %d must be 0 or 1", p->moving);
@@ -2999,20 +3040,13 @@ extern "C" int aigar_spg_config(aigar_handle *h, const aigar_spg_params *p) {
     if (p->prio_evals != 0 && p->prio_evals != 1) return fail("spg_config: prio_evals = %d must be 0 or 1", p->prio_evals);
     if (p->fused != 0 && p->fused != 1) return fail("spg_config: fused = %d must be 0 or 1", p->fused);
     if (p->pad != 0) return fail("spg_config: pad = %d must be 0", p->pad);
-    if (check_positive(who, "critic_lr", p->critic_lr) || check_positive(who, "actor_lr", p->actor_lr) ||
-        check_train_adam(who, p))
-      return -1;
-    if (!(p->tau >= 0 && p->tau <= 1)) return fail("spg_config: tau = %g is outside [0, 1]", p->tau);
-    if (!(fabs(p->q_increase) < __builtin_inf())) return fail("spg_config: q_increase = %g must be finite", p->q_increase);
+    if (check_qsa_rates(who, p)) return -1;
     if (!(p->noise >= 0 && p->noise < __builtin_inf())) return fail("spg_config: noise = %g must be finite and not negative", p->noise);
     if (!(p->noise_decay > 0 && p->noise_decay <= 1)) return fail("spg_config: noise_decay = %g is outside (0, 1]", p->noise_decay);
   }
   if (!h) return fail("null handle");
   if (p) {
-    if (check_train_net(h, who)) return -1;
-    if (need_crit(h, who)) return -1;
-    if (!h->crit_q) return fail("spg_config: the critic is V(s) (aigar_critic_config), SPG trains Q(s, a) (aigar_qcritic_config)");
-    if (need_exp(h, who)) return -1;
+    if (check_qsa_handle(h, who, "SPG")) return -1;
     if (p->replace && !h->exp.x) return fail("spg_config: replace needs a replay memory with the extra field (AIGAR_EXP_EXTRA)");
     if (check_train_widths(h, who)) return -1;
   }
@@ -3020,15 +3054,9 @@ extern "C" int aigar_spg_config(aigar_handle *h, const aigar_spg_params *p) {
   HIPCHK(hipStreamSynchronize(h->stream));
   if (p || h->spg.d.batch) trainer_free(h);  // (a null p turns off this trainer, not another)
   if (!p) return 0;
+  bool ok = true;
   SPGTrain sp;
-  DPGTrain &t = sp.d;
-  t.batch = p->batch;
-  t.n_s = h->net.in[0];
-  t.n_act = h->net.out[h->net.n_layers - 1];
-  t.soft = p->tau > 0 ? 1 : 0;
-  t.tau = (float)p->tau;
-  t.keep = (float)(1.0 - p->tau);
-  t.q_increase = p->q_increase;
+  sp.d = qsa_setup(h, ok, p, false);
   sp.K = p->samples;
   sp.moving = p->moving;
   sp.replace = p->replace;
@@ -3037,18 +3065,7 @@ extern "C" int aigar_spg_config(aigar_handle *h, const aigar_spg_params *p) {
   sp.noise0 = p->noise;
   sp.noise_decay = p->noise_decay;
   sp.seed = p->seed;
-  bool ok = true;
-  const size_t B = (size_t)p->batch, xrow = (size_t)(t.n_s + t.n_act) * h->exp.esz;
-  const Train s = train_shared(h, ok, p);
-  t.c = train_view(h, ok, s, h->crit, p->critic_lr, true);
-  t.a = train_view(h, ok, s, h->net, p->actor_lr, true);
-  t.c.s = (char *)train_get(h, ok, B * xrow);  // (the critic's first layer reads the packed rows)
-  t.c.s2 = (char *)train_get(h, ok, B * xrow);
-  t.xm = (char *)train_get(h, ok, B * xrow);
-  t.xt = (char *)train_get(h, ok, B * xrow);
-  t.qm = (double *)train_get(h, ok, B * sizeof(double));
-  t.qt = (double *)train_get(h, ok, B * sizeof(double));
-  t.ca = t.c;
+  const size_t B = (size_t)p->batch;
   sp.ex = (double *)train_get(h, ok, B * 4 * sizeof(double));
   sp.exv = (uint8_t *)train_get(h, ok, B);
   sp.best = (double *)train_get(h, ok, B * 4 * sizeof(double));
@@ -3062,13 +3079,14 @@ extern "C" int aigar_spg_config(aigar_handle *h, const aigar_spg_params *p) {
     h->trn_mem.release();
     return fail("spg_config: out of device memory");
   }
-  hipLaunchKernelGGL(k_spg_clear, dim3(1), dim3(1), 0, h->stream, t.c.ctl, t.a.ctl, sp.x, sp.noise0, 1);
+  hipLaunchKernelGGL(k_spg_clear, dim3(1), dim3(1), 0, h->stream, sp.d.c.ctl, sp.d.a.ctl, sp.x, sp.noise0, 1);
   HIPCHK(hipGetLastError());
   h->spg = sp;  // (the blocks are zeroed: every counter starts at 0)
   return 0;
 }
 
-// One SPG training step's launches on stream s (spg.inc), one linear chain.  has: has_u | has_zu << 1.
+// One SPG training step's launches on stream s (spg.inc), one linear chain: DPG's critic half, then
+// the search and the actor's update towards what it found.  has: has_u | has_zu << 1.
 static void launch_spg_step(aigar_handle *h, hipStream_t s, int has) {
   const SPGTrain &sp = h->spg;
   const DPGTrain &t = sp.d;
@@ -3076,31 +3094,13 @@ static void launch_spg_step(aigar_handle *h, hipStream_t s, int has) {
   const Exp &e = h->exp;
   Net cr = h->crit, ac = h->net;
   cr.x_dtype = ac.x_dtype = e.dtype;
-  const Net ct = target_net(cr, c), at = target_net(ac, a);
   const int B = t.batch, has_u = has & 1, has_zu = has >> 1 & 1;
-  // sets: 2, or 1: the first row set alone (k_sa_pack's blocks B .. 2 B - 1 are the second's)
-  auto pack = [&](int sets, const char *s0, const double *a0, int st0, char *o0, const char *s1, const double *a1, int st1,
-                  char *o1) {
-    if (e.dtype == 0)
-      hipLaunchKernelGGL(k_sa_pack<double>, dim3(sets * B), dim3(64), 0, s, B, t.n_s, t.n_act, (const double *)s0, a0, st0,
-                         (double *)o0, (const double *)s1, a1, st1, (double *)o1);
-    else
-      hipLaunchKernelGGL(k_sa_pack<float>, dim3(sets * B), dim3(64), 0, s, B, t.n_s, t.n_act, (const float *)s0, a0, st0,
-                         (float *)o0, (const float *)s1, a1, st1, (float *)o1);
-  };
   const bool extras = sp.replace && sp.K > 0;
   launch_draw_fetch(h, s, a, has_u);
   if (extras)
     hipLaunchKernelGGL(k_exp_extra_get, dim3((unsigned)(((size_t)B * 4 + 255) / 256)), dim3(256), 0, s, e, a.idx, B, sp.ex,
                        sp.exv);
-  // the critic half (launch_dpg_step's)
-  launch_net(s, at, a.s2, B, a.q2, nullptr, nullptr);
-  pack(2, a.s, a.a, 4, c.s, a.s2, a.q2, t.n_act, c.s2);
-  launch_net_save(s, cr, B, c.s, c.q, c.hsave);
-  launch_net(s, ct, c.s2, B, c.q2, nullptr, nullptr);
-  hipLaunchKernelGGL(k_td_qe, dim3(1), dim3(kTrainMaxBatch), 0, s, c, e, h->d, cr.n_layers, sp.prio_evals);
-  launch_net_update(s, cr, c);
-  if (e.prio) hipLaunchKernelGGL(k_exp_update, dim3(1), dim3(kExpPlanThreads), 0, s, e, c.idx, c.prio, B);
+  launch_qsa_critic(h, s, t, cr, target_net(cr, c), target_net(ac, a), sp.prio_evals);
   // the search
   launch_net_save(s, ac, B, a.s, a.q, a.hsave);
   if (sp.fused) {  // the whole search in one launch, 16 rows a block
@@ -3120,7 +3120,7 @@ static void launch_spg_step(aigar_handle *h, hipStream_t s, int has) {
     }
 #undef AIGAR_SPG_SEARCH
   } else {
-    pack(extras ? 2 : 1, a.s, a.q, t.n_act, t.xm, a.s, sp.ex, 4, t.xt);
+    launch_sa_pack(s, t, e.dtype, extras ? 2 : 1, a.s, a.q, t.n_act, t.xm, a.s, sp.ex, 4, t.xt);
     launch_net(s, cr, t.xm, B, sp.qmu, nullptr, nullptr);
     if (extras) launch_net(s, cr, t.xt, B, t.qt, nullptr, nullptr);
     hipLaunchKernelGGL(k_spg_pick, dim3(1), dim3(kTrainMaxBatch), 0, s, sp, 1);
@@ -3149,13 +3149,9 @@ extern "C" int aigar_spg_step(aigar_handle *h, int n_steps, const double *u, con
 extern "C" int aigar_spg_info(aigar_handle *h, int64_t info[8]) {
   if (need_spg(h, "spg_info")) return -1;
   if (!info) return fail("spg_info: null argument");
-  HIPCHK(hipSetDevice(h->cfg.device));
   TrainCtl c, a;
   SCtl x;
-  HIPCHK(hipMemcpyAsync(&c, h->spg.d.c.ctl, sizeof c, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(&a, h->spg.d.a.ctl, sizeof a, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(&x, h->spg.x, sizeof x, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  if (read_ctls(h, {{&c, h->spg.d.c.ctl, sizeof c}, {&a, h->spg.d.a.ctl, sizeof a}, {&x, h->spg.x, sizeof x}})) return -1;
   info[0] = c.t;
   info[1] = c.skipped;
   info[2] = c.since;
@@ -3181,27 +3177,25 @@ extern "C" int aigar_spg_noise(aigar_handle *h, double **dev) {
 
 extern "C" int aigar_spg_sync_target(aigar_handle *h) {
   if (need_spg(h, "spg_sync_target")) return -1;
-  HIPCHK(hipSetDevice(h->cfg.device));
-  if (target_copy(h, h->crit, h->spg.d.c) || target_copy(h, h->net, h->spg.d.a)) return -1;
-  hipLaunchKernelGGL(k_train_clear, dim3(1), dim3(1), 0, h->stream, h->spg.d.c.ctl, 1);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return qsa_sync_target(h, h->spg.d);
 }
 
 extern "C" int aigar_spg_reset(aigar_handle *h) {
   if (need_spg(h, "spg_reset")) return -1;
-  HIPCHK(hipSetDevice(h->cfg.device));
   const SPGTrain &sp = h->spg;
-  if (adam_clear(h, h->crit, sp.d.c) || adam_clear(h, h->net, sp.d.a)) return -1;
+  if (qsa_adam_clear(h, sp.d)) return -1;
   hipLaunchKernelGGL(k_spg_clear, dim3(1), dim3(1), 0, h->stream, sp.d.c.ctl, sp.d.a.ctl, sp.x, sp.noise0, 0);
   HIPCHK(hipGetLastError());
   return 0;
 }
 
+// The configured Q(s, a) trainer's DPGTrain, DPG's or SPG's, or null
+static const DPGTrain *qsa_train(const aigar_handle *h) {
+  return h->dpg.batch ? &h->dpg : h->spg.d.batch ? &h->spg.d : nullptr;
+}
 // The configured trainer's view of the acting network, or (crit) of the critic.
 static const Train &trainer_view(const aigar_handle *h, bool crit) {
-  if (h->dpg.batch) return crit ? h->dpg.c : h->dpg.a;
-  if (h->spg.d.batch) return crit ? h->spg.d.c : h->spg.d.a;
+  if (const DPGTrain *t = qsa_train(h)) return crit ? t->c : t->a;
   if (h->act.batch) return crit ? h->act.c : h->act.a;
   return h->trn;
 }
@@ -3218,7 +3212,7 @@ static int net_which(aigar_handle *h, const char *who, int which, int layer, con
   if (crit && !h->crit.n_layers) return fail("%s: no critic is configured (aigar_critic_config)", who);
   const Net &c = crit ? h->crit : h->net;
   if (layer < 0 || layer >= c.n_layers) return fail("%s: layer %d is outside 0..%d", who, layer, c.n_layers - 1);
-  const bool dpg = h->dpg.batch != 0 || h->spg.d.batch != 0;  // (an SPG configuration serves the codes as DPG's does)
+  const bool dpg = qsa_train(h) != nullptr;  // (an SPG configuration serves the codes as DPG's does)
   if (which == 1 && h->act.batch) return fail("%s: which = 1: CACLA keeps no actor target", who);
   if (which > 4 && !dpg && need_act(h, who)) return -1;
   if (which >= 1 && which <= 3 && !dpg && !h->act.batch && need_trn(h, who)) return -1;

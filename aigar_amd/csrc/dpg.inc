@@ -1,19 +1,21 @@
 // dpg.inc -- the DPG learner's training step on the device (include/aigar.h aigar_dpg*,
-// aigar_qcritic_config; DESIGN.md §4n).  Included by api.hip after actrain.inc: the trainer's
-// device state and its five control kernels; the entry points are in api.hip.
+// aigar_qcritic_config; DESIGN.md §4n), and what the SPG learner's (spg.inc) shares with it: the
+// state of a Q(s, a) trainer (DPGTrain), the critic half's kernels and the tail's body.  Included
+// by api.hip after actrain.inc; the entry points are in api.hip.
 //
 // The reference's trainer (actorCritic.py ActorCritic.learn for ALGORITHM == "DPG":
 // train_critic_DPG 986-1029, train_actor_DPG 751-789 on createCombinedActorCritic 581-598,
 // softlyUpdateTargetModel 366-373).  tests/dpg_model.py is the specification in plain Python.
 // The critic Q(s, a) takes rows [s, a] of n_s + n_act values.  One step is one captured graph:
 //   k_exp_draw, k_exp_fetch   (replay.inc) the mini-batch into the staging rows
-// the critic half
+// the critic half (api.hip launch_qsa_critic: DPG's and SPG's)
 //   k_net          mu2 = the actor's target on s2
 //   k_sa_pack      the rows [s, a] and [s2, mu2]
 //   k_net_save     q = Q([s, a]) with the critic, its hidden activations kept
 //   k_net          q2 = Q([s2, mu2]) with the critic's target
-//   k_td_q         one workgroup: targets, TD errors, priorities, the critic's output delta, the
-//                  step's skip decision (k_td_v's without the selection)
+//   k_td_q         one workgroup: targets, TD errors, priorities (SPG's prio_evals: |Q(s, a)| in the
+//                  TD error's place), the critic's output delta, the step's skip decision (k_td_v's
+//                  without the selection)
 //   k_net_bwd, k_net_grad_adam  (train.inc) on the critic's view
 //   k_exp_update   (replay.inc, prioritized memory)
 // the actor half, with the critic as just updated and both targets as before this step
@@ -28,13 +30,14 @@
 //   k_net_bwd_in   dQ/da = delta_0 W_0^T on the action rows of W_0, times mu (1 - mu): the
 //                  actor's output delta
 //   k_net_bwd, k_net_grad_adam  on the actor's view
-// and k_dpg_tail: the counters, the soft update or the due hard copy of both targets.
+// and k_dpg_tail: dpg_tail (the soft update or the due hard copy of both targets, the critic's
+// counters; k_spg_tail calls it too) with the actor half's counter.
 //
 // The forward, backward and gradient kernels are net.inc's and train.inc's, unchanged: each
 // network has a Train of its own; `ca` is the critic's with a TrainCtl whose skip is the actor
-// half's.
+// half's (SPG has no pass through the critic: its ca is c, and mut stays null).
 
-struct DPGTrain {  // aigar_dpg_config (batch 0: off)
+struct DPGTrain {  // aigar_dpg_config, and SPGTrain's d (api.hip qsa_setup; batch 0: off)
   int batch = 0, n_s = 0, n_act = 0, soft = 0;  // soft: tau > 0 (else the hard copy)
   float tau = 0, keep = 0;                      // float32(tau), float32(1.0 - tau)
   double q_increase = 0;
@@ -59,15 +62,20 @@ __global__ void __launch_bounds__(64) k_sa_pack(int B, int n_s, int n_act, const
 }
 
 // k_td_v without the selection: targets, TD errors (float64), priorities, the critic's delta and
-// the step's decisions, every piece train.inc's.
-__global__ void __launch_bounds__(kTrainMaxBatch) k_td_q(Train c, Exp e, Dev d, int n_layers) {
+// the step's decisions, every piece train.inc's.  With prio_evals (SPG) the priority of an applied
+// step's row is |Q(s, a)| + 1e-4: the reference hands get_evals' Q(s, a) to the memory in the TD
+// error's place (aigar.py:1081).  DPG passes 0.
+__global__ void __launch_bounds__(kTrainMaxBatch) k_td_q(Train c, Exp e, Dev d, int n_layers, int prio_evals) {
   const int r = threadIdx.x, B = c.batch;
   const bool small = train_small(c, e);
   double td = 0.0;
   bool bad = false;
   if (r < B && !small) td = td_scalar(c, r, bad);
   const bool any_bad = __syncthreads_or(bad ? 1 : 0) != 0;
-  if (r < B) delta_scalar(c, n_layers, r, td_prio_grad(c, r, small || any_bad, td, 1));
+  if (r < B) {
+    delta_scalar(c, n_layers, r, td_prio_grad(c, r, small || any_bad, td, 1));
+    if (prio_evals && !small && !any_bad) c.prio[r] = fabs(c.q[r]) + 1e-4;
+  }
   if (r == 0) td_decide(c, e, d, small, any_bad);
 }
 
@@ -161,11 +169,13 @@ __device__ __forceinline__ void dpg_target(const Net &n, const Train &v, bool so
   }
 }
 
-// The step's end: the counters of both halves, then both targets' soft update (tau > 0, after
-// every applied step) or their hard copy when due.
-__global__ void __launch_bounds__(256) k_dpg_tail(Net cr, Net ac, DPGTrain t) {
-  TrainCtl *cc = t.c.ctl, *ac_ctl = t.a.ctl;
-  const int skip = cc->skip, due = cc->due, askip = ac_ctl->skip;  // (this kernel leaves them)
+// The end of a Q(s, a) trainer's step, DPG's and SPG's: both targets' soft update (tau > 0, after
+// every applied step) or their hard copy when due, then in one thread the critic's counters and,
+// after an applied step, actor_half(): the trainer's own booking of its actor half's outcome.
+template <class F>
+__device__ __forceinline__ void dpg_tail(const Net &cr, const Net &ac, const DPGTrain &t, F actor_half) {
+  TrainCtl *cc = t.c.ctl;
+  const int skip = cc->skip, due = cc->due;  // (the tail kernels leave them)
   const bool soft = t.soft != 0;
   if (!skip && (soft || due)) {
     dpg_target(cr, t.c, soft, t.tau, t.keep);
@@ -177,10 +187,19 @@ __global__ void __launch_bounds__(256) k_dpg_tail(Net cr, Net ac, DPGTrain t) {
     } else {
       cc->t += 1;
       cc->since = (!soft && due) ? 0 : cc->since + 1;
-      if (askip) ac_ctl->skipped += 1;
-      else ac_ctl->t += 1;
+      actor_half();
     }
   }
+}
+
+// The step's end: dpg_tail, the actor half's counter from its skip decision.
+__global__ void __launch_bounds__(256) k_dpg_tail(Net cr, Net ac, DPGTrain t) {
+  TrainCtl *ac_ctl = t.a.ctl;
+  const int askip = ac_ctl->skip;  // (this kernel leaves it)
+  dpg_tail(cr, ac, t, [&] {
+    if (askip) ac_ctl->skipped += 1;
+    else ac_ctl->t += 1;
+  });
 }
 
 // aigar_dpg_reset: both step counters to zero

@@ -7,7 +7,7 @@
 // the specification in plain Python.  One step is one captured graph, a linear chain:
 //   k_exp_draw, k_exp_fetch, k_exp_extra_get (replay.inc) the mini-batch and, with replace, the
 //                  drawn slots' fifth field
-// the critic half: dpg.inc's launches, with k_td_qe in k_td_q's place (the priority's choice)
+// the critic half: DPG's (dpg.inc; api.hip launch_qsa_critic), k_td_q with this trainer's prio_evals
 // the search, with the critic as just updated and the actor as it is
 //   k_net_save     mu = the actor on s, its hidden activations kept
 //   k_sa_pack      the rows [s, mu] and [s, extra]
@@ -24,7 +24,8 @@
 //                  half's decision, the actor's lr_t, the rows of the write-back
 //   k_net_bwd, k_net_grad_adam  (train.inc) on the actor's view
 //   k_spg_writeback  (replace) k_exp_extra_set's last-wins scheme on the drawn slots
-// and k_spg_tail: the counters, both targets' update, the noise's decay.
+// and k_spg_tail: dpg.inc's dpg_tail (both targets' update, the critic's counters) with this
+// trainer's booking of the actor half, the noise's decay and the ordinal.
 //
 // The Gaussian pair is spg_gauss_pair, a copy of k_noise's arithmetic (see there).  Every loop is bounded by a
 // compile-time constant (AIGAR_SPG_MAX_SAMPLES rounds, 16 attempts a pair); all stores are plain
@@ -52,22 +53,6 @@ struct SPGTrain {  // aigar_spg_config (d.batch 0: off)
   double *zu = nullptr;    // [batch][K][2][16][2] the caller's uniforms of the running step
   SCtl *x = nullptr;
 };
-
-// k_td_q, and with prio_evals the priority of an applied step's row is |Q(s, a)| + 1e-4 (the
-// reference hands get_evals' Q(s, a) to the memory in the TD error's place, aigar.py:1081).
-__global__ void __launch_bounds__(kTrainMaxBatch) k_td_qe(Train c, Exp e, Dev d, int n_layers, int prio_evals) {
-  const int r = threadIdx.x, B = c.batch;
-  const bool small = train_small(c, e);
-  double td = 0.0;
-  bool bad = false;
-  if (r < B && !small) td = td_scalar(c, r, bad);
-  const bool any_bad = __syncthreads_or(bad ? 1 : 0) != 0;
-  if (r < B) {
-    delta_scalar(c, n_layers, r, td_prio_grad(c, r, small || any_bad, td, 1));
-    if (prio_evals && !small && !any_bad) c.prio[r] = fabs(c.q[r]) + 1e-4;
-  }
-  if (r == 0) td_decide(c, e, d, small, any_bad);
-}
 
 // Row r's first comparisons, float64 `>` (a NaN never wins): best starts as the stored action with
 // Q(s, a) from before the critic's update; with K > 0 the valid extra (replace) and then mu are
@@ -411,7 +396,7 @@ __global__ void __launch_bounds__(64 * kNetWaves) k_spg_search(Net cr, SPGTrain 
 __global__ void __launch_bounds__(kTrainMaxBatch) k_spg_delta(SPGTrain t, Dev d, int n_layers, int n_out) {
   const Train &a = t.d.a;
   const int r = threadIdx.x, B = t.d.batch;
-  const bool live = !t.d.c.ctl->skip;  // (uniform: written by k_td_qe)
+  const bool live = !t.d.c.ctl->skip;  // (uniform: written by k_td_q)
   const bool sel = live && r < B && t.beval[r] > t.qmu[r];
   const int count = __syncthreads_count(sel ? 1 : 0);
   bool bad = false;
@@ -468,31 +453,18 @@ __global__ void __launch_bounds__(kExpPlanThreads) k_spg_writeback(SPGTrain s, E
   }
 }
 
-// The step's end: k_dpg_tail's target update and counters with the actor half's three outcomes,
-// then noise <- noise * noise_decay after an applied step, and the steps' ordinal.
+// The step's end: dpg_tail with the actor half's three outcomes and noise <- noise * noise_decay
+// after an applied step, then the steps' ordinal.
 __global__ void __launch_bounds__(256) k_spg_tail(Net cr, Net ac, SPGTrain s) {
-  const DPGTrain &t = s.d;
-  TrainCtl *cc = t.c.ctl, *ac_ctl = t.a.ctl;
-  const int skip = cc->skip, due = cc->due;  // (this kernel leaves them)
-  const bool soft = t.soft != 0;
-  if (!skip && (soft || due)) {
-    dpg_target(cr, t.c, soft, t.tau, t.keep);
-    dpg_target(ac, t.a, soft, t.tau, t.keep);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    SCtl *x = s.x;
-    if (skip) {
-      cc->skipped += 1;
-    } else {
-      cc->t += 1;
-      cc->since = (!soft && due) ? 0 : cc->since + 1;
-      if (x->half == 0) ac_ctl->t += 1;
-      else if (x->half == 1) x->aempty += 1;
-      else ac_ctl->skipped += 1;
-      x->noise = x->noise * s.noise_decay;
-    }
-    x->ord += 1;
-  }
+  TrainCtl *ac_ctl = s.d.a.ctl;
+  SCtl *x = s.x;
+  dpg_tail(cr, ac, s.d, [&] {
+    if (x->half == 0) ac_ctl->t += 1;
+    else if (x->half == 1) x->aempty += 1;
+    else ac_ctl->skipped += 1;
+    x->noise = x->noise * s.noise_decay;
+  });
+  if (blockIdx.x == 0 && threadIdx.x == 0) x->ord += 1;
 }
 
 // aigar_spg_config (all: the noise and the totals start over) and aigar_spg_reset: both step

@@ -81,7 +81,7 @@ class Case:
 
     def __init__(self, n_in, actor, critic, batch, ha="relu", hc="relu", dtype="float64", prio=False, n_mem=40, hi=2,
                  seed=0, target_steps=0, min_size=0, done=None, rewards=None, tau=0.25, q_increase=2.0, lr=1e-2,
-                 critic_weights=None):
+                 critic_weights=None, extra=False):
         self.st = st = handle(n_in)
         self.rng = rng = np.random.default_rng(1000 * n_in + 10 * batch + seed)
         self.n_in, self.batch, self.dtype, self.prio = n_in, batch, dtype, prio
@@ -90,7 +90,7 @@ class Case:
         np_dt = np.float64 if dtype == "float64" else np.float32
         self.a0 = M.make_weights(rng, n_in, self.actor, hi=hi)
         self.c0 = M.make_weights(rng, n_in + n_act, self.critic, hi=hi) if critic_weights is None else critic_weights
-        st.exp_config(CAP, prioritized=prio, dtype=dtype, seed=3)
+        st.exp_config(CAP, prioritized=prio, dtype=dtype, seed=3, extra=extra)
         st.net_config((n_in, self.actor, ha, "sigmoid"), x_dtype=dtype)
         st.qcritic_config((n_in + n_act, self.critic, hc, "linear"), x_dtype=dtype)
         st.net_set_weights(self.a0)
