@@ -292,6 +292,24 @@ struct Dev {
 };
 enum { SC_N = 0, SC_SUM = 1, SC_MAX = 2, SC_DEAD = 3 };
 
+// The arenas a restart covers (Field.reset of whole worlds), passed by value to
+// its kernels: index i of the selection is arena al[i] with seed seeds[i] (device
+// lists), or arena first + i with the one seed.  A listed arena becomes the world
+// a one-arena handle gets from aigar_reset(seeds[i]), so its Philox key's arena
+// word is 0; a ranged one is keyed by its own index.
+//   whole handle (aigar_reset):          {nullptr, nullptr, seed, 0, A}
+//   listed arenas (aigar_reset_arenas):  {d_rlist, d_rseed, 0, 0, n}
+//   one arena (aigar_load_state):        {nullptr, nullptr, 0, arena, 1}
+struct ArenaSel {
+  const int *al;
+  const uint64_t *seeds;
+  uint64_t seed;
+  int first, n;
+  __device__ __forceinline__ int arena(int i) const { return al ? al[i] : first + i; }
+  __device__ __forceinline__ uint64_t seed_of(int i) const { return seeds ? seeds[i] : seed; }
+  __device__ __forceinline__ int key_arena(int i) const { return al ? 0 : first + i; }
+};
+
 constexpr int FCAP = 32;  // stored candidate foods per cell (overflow -> serial)
 
 // the synthetic population's policy when it is evaluated inside the tick

@@ -220,15 +220,6 @@ __device__ __forceinline__ void fov_store(const Dev &d, int gp, const Fov &f) {
   d.p_fs[gp] = f.fs;
   d.p_mass[gp] = f.mass;
 }
-// per-player FOV cache, refreshed once the world state of a tick is final
-__device__ inline void store_player_fov(const Dev &d, int gp) {
-  if (!d.p_alive[gp]) return;
-  Fov f = player_fov(d, gp);
-  d.p_fx[gp] = f.fx;
-  d.p_fy[gp] = f.fy;
-  d.p_fs[gp] = f.fs;
-  d.p_mass[gp] = f.mass;
-}
 // one thread of the end-of-tick FOV cache pass (every thread of the wave calls
 // it): getFovPos / getFovSize / getTotalMass (player.py:129,156-167) for the
 // observation and the policies, the largest cell radius for their grid walks,
@@ -240,10 +231,7 @@ __device__ inline void fov_cache_thread(const Dev &d, int gp) {
   const int a = gp < d.NP ? gp / d.B : 0;
   if (live) {
     const Fov f = player_fov(d, gp);
-    d.p_fx[gp] = f.fx;
-    d.p_fy[gp] = f.fy;
-    d.p_fs[gp] = f.fs;
-    d.p_mass[gp] = f.mass;
+    fov_store(d, gp, f);
     rb = f.rmax;
   }
   wave_atomic_max_pos(&d.ctl[a].rmax_cell, rb);  // (per-lane atomics when a wave spans arenas)

@@ -26,8 +26,8 @@ void launch_tile_policy(const Dev &d, hipStream_t s, int greedy_split, uint8_t *
 void launch_tile_cmd_apply(const Dev &d, hipStream_t s, int box_recs);
 void launch_pel_gather(const Dev &d, hipStream_t s, int a);
 void launch_tile_apply(const Dev &d, hipStream_t s, int box_recs, int first);
-void launch_reset(const Dev &d, hipStream_t s, uint64_t seed);
-void launch_reset_arenas(const Dev &d, hipStream_t s, const int *al, const uint64_t *seeds, int n);
+void launch_restart(const Dev &d, hipStream_t s, const ArenaSel &sel);
+void launch_restart_bots(const Dev &d, hipStream_t s, const ArenaSel &sel);
 void launch_observe(const Dev &d, hipStream_t s, void *out, int dtype, uint32_t epoch,
                     const uint8_t *mask = nullptr, int greedy_next = -1);
 bool observe_fuses_greedy(const Dev &d);
@@ -41,7 +41,7 @@ void launch_player_stats(const Dev &d, hipStream_t s, double *out);
 void launch_score_read(const Dev &d, hipStream_t s, double *out);
 void launch_score_reset(const Dev &d, hipStream_t s, const uint8_t *mask);
 void launch_score_trace(const Dev &d, hipStream_t s, double *buf, int64_t cap);
-void launch_player_fov(const Dev &d, hipStream_t s);
+void launch_player_fov(const Dev &d, hipStream_t s, const ArenaSel &sel);
 void launch_apply_actions(const Dev &d, hipStream_t s, const double *act, int n_act, int enable_split, int skipping,
                           int record);
 void launch_rewards(const Dev &d, hipStream_t s, double *out, const aigar_reward_params &p, int update_last,
@@ -721,9 +721,9 @@ static int check_device_errors(aigar_handle *h) {
 static size_t pix_hist_bytes(const aigar_handle *h) {
   return (h->pix.flags & AIGAR_PIX_LAST) ? sizeof(uint32_t) * h->d.NP * (size_t)h->pix.side * h->pix.side : 0;
 }
-// the pixel history of the listed arenas' bots (row: the B * side * side words of one arena)
-__global__ void __launch_bounds__(256) k_pix_hist_clear_arenas(uint32_t *hist, size_t row, const int *al) {
-  uint32_t *p = hist + (size_t)al[blockIdx.y] * row;
+// the pixel history of the selected arenas' bots (row: the B * side * side words of one arena)
+__global__ void __launch_bounds__(256) k_pix_hist_clear_arenas(uint32_t *hist, size_t row, ArenaSel sel) {
+  uint32_t *p = hist + (size_t)sel.arena(blockIdx.y) * row;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < row; i += (size_t)gridDim.x * blockDim.x) p[i] = 0;
 }
 // ... of the players with mask[i] != 0 (null: all); LL = side * side words a player
@@ -737,36 +737,37 @@ __global__ void k_fill_d(double *p, size_t n, double v) {
   if (i < n) p[i] = v;
 }
 
+// What a restart clears beside the Dev buffers, for the bots of the selected
+// arenas: the pixel history, the replay memory's oldState marks (Bot.reset:
+// oldState = None) and the Orn-Uhl noise state
+static void restart_side_buffers(aigar_handle *h, const ArenaSel &sel) {
+  const Dev &d = h->d;
+  if (h->d_pix_hist) {
+    const size_t row = (size_t)d.B * h->pix.side * h->pix.side;
+    const unsigned nb = (unsigned)std::min<size_t>((row + 255) / 256, 256);
+    hipLaunchKernelGGL(k_pix_hist_clear_arenas, dim3(nb, sel.n), dim3(256), 0, h->stream, h->d_pix_hist, row, sel);
+  }
+  if (h->exp.cap) hipLaunchKernelGGL(k_exp_clear_arenas, dim3(sel.n), dim3(256), 0, h->stream, h->exp.has_old, d.B, sel);
+  if (h->noi.n_act)
+    hipLaunchKernelGGL(k_noise_clear_arenas, dim3(sel.n), dim3(256), 0, h->stream, h->noi.ou, d.B * h->noi.n_act, sel);
+}
+// a tiled handle: every tile's history copy is current, and the hand-off priorities restart
+static int tiles_restart(aigar_handle *h) {
+  const Dev &d = h->d;
+  if (!d.tiled) return 0;
+  HIPCHK(hipMemsetAsync(d.t_holder, 0xFF, sizeof(int) * d.NP, h->stream));
+  HIPCHK(hipMemsetAsync(d.t_obsby, 0xFF, sizeof(int) * d.NP, h->stream));
+  HIPCHK(hipMemsetAsync(d.t_hodefer, 0, d.NP, h->stream));
+  return 0;
+}
+
 extern "C" int aigar_reset(aigar_handle *h, uint64_t seed) {
   if (!h) return fail("null handle");
   HIPCHK(hipSetDevice(h->cfg.device));
-  Dev &d = h->d;
-  const size_t NP = d.NP, GG = (size_t)d.G * d.G, A = d.A, H1 = (size_t)d.H + 1;
-  hipLaunchKernelGGL(k_fill_d, dim3((NP + 255) / 256), dim3(256), 0, h->stream, d.p_cmdx, NP, -1.0);
-  hipLaunchKernelGGL(k_fill_d, dim3((NP + 255) / 256), dim3(256), 0, h->stream, d.p_cmdy, NP, -1.0);
-  hipLaunchKernelGGL(k_fill_d, dim3((NP + 255) / 256), dim3(256), 0, h->stream, d.o_last_mass, NP,
-                     __builtin_nan(""));  // NN bots' lastMass = None (bot.py:125-130)
-  HIPCHK(hipMemsetAsync(d.cstart, 0, sizeof(int) * A * H1, h->stream));
-  HIPCHK(hipMemsetAsync(d.cgcnt, 0, sizeof(int) * A * 2 * 4100, h->stream));
-  HIPCHK(hipMemsetAsync(d.vstart, 0, sizeof(int) * A * H1, h->stream));
-  HIPCHK(hipMemsetAsync(d.bstart, 0, sizeof(int) * A * H1, h->stream));
-  HIPCHK(hipMemsetAsync(d.bmap, 0, sizeof(uint64_t) * A * 64, h->stream));
-  HIPCHK(hipMemsetAsync(d.v_active, 0, sizeof(int) * A * d.Vcap, h->stream));
-  HIPCHK(hipMemsetAsync(d.o_lastfov, 0, sizeof(double) * NP, h->stream));
-  if (d.sc) HIPCHK(hipMemsetAsync(d.sc, 0, sizeof(double) * 4 * NP, h->stream));  // every mass history starts empty
-  // Bot.reset (bot.py:125-164): currentAction None (NN) / [0, 0, 0, 0] (Greedy, Random)
-  HIPCHK(hipMemsetAsync(d.o_act_cur, 0, sizeof(double) * NP * 4, h->stream));
-  for (double *p : {d.o_self_lf, d.o_self_slf, d.o_en_lf, d.o_en_slf})
-    HIPCHK(hipMemsetAsync(p, 0, sizeof(double) * NP * GG, h->stream));
-  if (h->d_pix_hist) HIPCHK(hipMemsetAsync(h->d_pix_hist, 0, pix_hist_bytes(h), h->stream));
-  if (h->exp.cap) HIPCHK(hipMemsetAsync(h->exp.has_old, 0, NP, h->stream));  // Bot.reset: oldState = None
-  if (h->noi.n_act) HIPCHK(hipMemsetAsync(h->noi.ou, 0, sizeof(double) * NP * h->noi.n_act, h->stream));
-  if (d.tiled) {  // every tile's history copy is current (all zero)
-    HIPCHK(hipMemsetAsync(d.t_holder, 0xFF, sizeof(int) * NP, h->stream));
-    HIPCHK(hipMemsetAsync(d.t_obsby, 0xFF, sizeof(int) * NP, h->stream));
-    HIPCHK(hipMemsetAsync(d.t_hodefer, 0, NP, h->stream));  // (hand-off priorities restart)
-  }
-  launch_reset(d, h->stream, seed);
+  const ArenaSel sel{nullptr, nullptr, seed, 0, h->d.A};
+  restart_side_buffers(h, sel);
+  if (tiles_restart(h)) return -1;
+  launch_restart(h->d, h->stream, sel);
   HIPCHK(hipGetLastError());
   return check_device_errors(h);
 }
@@ -799,16 +800,9 @@ extern "C" int aigar_reset_arenas(aigar_handle *h, const int32_t *arenas, const 
   HIPCHK(hipEventRecord(h->ev_reset[slot], h->stream));
   {
     Mark m(h, "reset_arenas");
-    launch_reset_arenas(d, h->stream, h->d_rlist, h->d_rseed, n);
-    if (h->d_pix_hist) {
-      const size_t row = (size_t)d.B * h->pix.side * h->pix.side;
-      const unsigned nb = (unsigned)std::min<size_t>((row + 255) / 256, 256);
-      hipLaunchKernelGGL(k_pix_hist_clear_arenas, dim3(nb, n), dim3(256), 0, h->stream, h->d_pix_hist, row, h->d_rlist);
-    }
-    if (h->exp.cap)
-      hipLaunchKernelGGL(k_exp_clear_arenas, dim3(n), dim3(256), 0, h->stream, h->exp.has_old, d.B, h->d_rlist);
-    if (h->noi.n_act)
-      hipLaunchKernelGGL(k_noise_clear_arenas, dim3(n), dim3(256), 0, h->stream, h->noi.ou, d.B * h->noi.n_act, h->d_rlist);
+    const ArenaSel sel{h->d_rlist, h->d_rseed, 0, 0, n};
+    launch_restart(d, h->stream, sel);
+    restart_side_buffers(h, sel);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -3682,7 +3676,7 @@ extern "C" int aigar_load_state(aigar_handle *h, int arena, const aigar_state *s
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipStreamSynchronize(h->stream));
   const int B = d.B, NP = d.NP;
-  const size_t p0 = (size_t)arena * B, GG = (size_t)d.G * d.G;
+  const size_t p0 = (size_t)arena * B;
   std::vector<int> alive(B), resp(B), ncells(B, 0), split(B), eject(B), dead(st->n_dead);
   std::vector<double> cmdx(B), cmdy(B);
   for (int p = 0; p < B; p++) {
@@ -3841,28 +3835,12 @@ extern "C" int aigar_load_state(aigar_handle *h, int arena, const aigar_state *s
     HIPCHK(hipMemsetAsync(d.scan_state + ((size_t)sl * d.A + arena) * d.scan_tiles, 0, 8 * (size_t)d.scan_tiles,
                           h->stream));
   HIPCHK(hipMemcpyAsync(d.ctl + arena, &c, sizeof c, hipMemcpyHostToDevice, h->stream));
-  // bot-side observation history restarts (NN bot reset, bot.py:151-158)
-  HIPCHK(hipMemsetAsync(d.o_lastfov + p0, 0, 8 * B, h->stream));
-  HIPCHK(hipMemsetAsync(d.o_act_cur + p0 * 4, 0, 8 * 4 * (size_t)B, h->stream));  // currentAction reset
-  if (d.sc)  // a snapshot carries no mass history: this arena's starts empty
-    for (int f = 0; f < 4; f++) HIPCHK(hipMemsetAsync(d.sc + (size_t)f * NP + p0, 0, 8 * (size_t)B, h->stream));
-  hipLaunchKernelGGL(k_fill_d, dim3((B + 255) / 256), dim3(256), 0, h->stream, d.o_last_mass + p0, (size_t)B,
-                     __builtin_nan(""));
-  for (double *p : {d.o_self_lf, d.o_self_slf, d.o_en_lf, d.o_en_slf})
-    HIPCHK(hipMemsetAsync(p + p0 * GG, 0, 8 * B * GG, h->stream));
-  if (h->d_pix_hist) {
-    const size_t LL = (size_t)h->pix.side * h->pix.side;
-    HIPCHK(hipMemsetAsync(h->d_pix_hist + p0 * LL, 0, sizeof(uint32_t) * B * LL, h->stream));
-  }
-  if (h->exp.cap) HIPCHK(hipMemsetAsync(h->exp.has_old + p0, 0, B, h->stream));
-  if (h->noi.n_act)
-    HIPCHK(hipMemsetAsync(h->noi.ou + p0 * h->noi.n_act, 0, sizeof(double) * B * h->noi.n_act, h->stream));
-  if (d.tiled) {
-    HIPCHK(hipMemsetAsync(d.t_holder, 0xFF, sizeof(int) * d.NP, h->stream));
-    HIPCHK(hipMemsetAsync(d.t_obsby, 0xFF, sizeof(int) * d.NP, h->stream));
-    HIPCHK(hipMemsetAsync(d.t_hodefer, 0, d.NP, h->stream));
-  }
-  launch_player_fov(d, h->stream);  // FOV cache of the loaded players
+  // the arena's bots restart (NN bot reset, bot.py:151-158); the commands are the snapshot's
+  const ArenaSel sel{nullptr, nullptr, 0, arena, 1};
+  launch_restart_bots(d, h->stream, sel);
+  restart_side_buffers(h, sel);
+  if (tiles_restart(h)) return -1;
+  launch_player_fov(d, h->stream, sel);  // FOV cache of the loaded players
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }

@@ -150,8 +150,8 @@ static void launch_noise(const Dev &d, hipStream_t s, const Noise &c, const void
 }
 
 // the Orn-Uhl state restarts at zero wherever the bots' history does (actorCritic.py:1121-1123)
-__global__ void k_noise_clear_arenas(double *ou, int per, const int *al) {
-  for (int i = threadIdx.x; i < per; i += blockDim.x) ou[(size_t)al[blockIdx.x] * per + i] = 0.0;
+__global__ void k_noise_clear_arenas(double *ou, int per, ArenaSel sel) {
+  for (int i = threadIdx.x; i < per; i += blockDim.x) ou[(size_t)sel.arena(blockIdx.x) * per + i] = 0.0;
 }
 __global__ void k_noise_clear_bots(double *ou, int n, int n_act, const uint8_t *mask) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -456,7 +456,7 @@ __global__ void __launch_bounds__(64) OBS_ATTR k_observe(Dev d, OutT *out, uint3
   };
 #endif
   // one round of independent loads: liveness, the FOV cache written at the end
-  // of the tick (store_player_fov) and the own cells' slots
+  // of the tick (fov_store) and the own cells' slots
   const bool alive = d.p_alive[gp];
   const double fx = d.p_fx[gp], fy = d.p_fy[gp], fs = d.p_fs[gp];
   const int ncell = d.p_ncells[gp];
@@ -1329,30 +1329,23 @@ __global__ void k_set_commands(Dev d, const double *cmd) {
   d.p_eject[gp] = cmd[4 * (size_t)gp + 3] != 0;
 }
 
-// FOV cache of every live player, and the arena's largest cell radius (bounds
-// the cell-grid expansion of the observation and the next greedy moves)
-__global__ void __launch_bounds__(256) k_player_fov(Dev d) { fov_cache_thread(d, GTID); }
-void launch_player_fov(const Dev &d, hipStream_t s) {
-  hipLaunchKernelGGL(k_player_fov, dim3((d.NP + 255) / 256), dim3(256), 0, s, d);
-}
-// ... of the players of the n listed arenas (aigar_reset_arenas).  The overflow
-// pool's epoch moves once per launch, as in fov_cache_thread (there by player 0's
-// thread, which this launch may not have: here by the first thread).
-__global__ void __launch_bounds__(256) k_player_fov_list(Dev d, const int *al, int n) {
+// FOV cache of every live player of the selected arenas (ArenaSel), and each
+// arena's largest cell radius (bounds the cell-grid expansion of the observation
+// and the next greedy moves).  The overflow pool's epoch moves once per launch, as
+// in fov_cache_thread (there by player 0's thread, which this launch may not
+// have: here by the first thread).
+__global__ void __launch_bounds__(256) k_player_fov(Dev d, ArenaSel sel) {
   const int i = GTID;
   if (i == 0) *d.ob_epoch = 0x80000000u | ((*d.ob_epoch + 1) & 0x7FFFFFFFu);
-  if (i >= n * d.B) return;
-  const int a = al[i / d.B], gp = a * d.B + i % d.B;
+  if (i >= sel.n * d.B) return;
+  const int a = sel.arena(i / d.B), gp = a * d.B + i % d.B;
   if (!d.p_alive[gp]) return;
   const Fov f = player_fov(d, gp);
-  d.p_fx[gp] = f.fx;
-  d.p_fy[gp] = f.fy;
-  d.p_fs[gp] = f.fs;
-  d.p_mass[gp] = f.mass;
+  fov_store(d, gp, f);
   if (f.rmax > 0) atomic_max_pos(&d.ctl[a].rmax_cell, f.rmax);
 }
-void launch_player_fov_list(const Dev &d, hipStream_t s, const int *al, int n) {
-  hipLaunchKernelGGL(k_player_fov_list, dim3((n * d.B + 255) / 256), dim3(256), 0, s, d, al, n);
+void launch_player_fov(const Dev &d, hipStream_t s, const ArenaSel &sel) {
+  hipLaunchKernelGGL(k_player_fov, dim3((sel.n * d.B + 255) / 256), dim3(256), 0, s, d, sel);
 }
 // ---------------------------------------------------- pixel observation
 // RGBGenerator.get_cnn_inputRGB (rgbGenerator.py:95-110) for every player: a

@@ -207,8 +207,8 @@ __global__ void __launch_bounds__(256) k_exp_latch(Exp e, const void *obs, int d
   if (threadIdx.x == 0) e.has_old[i] = dead ? 0 : 1;
 }
 
-__global__ void k_exp_clear_arenas(uint8_t *has_old, int B, const int *al) {
-  for (int i = threadIdx.x; i < B; i += blockDim.x) has_old[(size_t)al[blockIdx.x] * B + i] = 0;
+__global__ void k_exp_clear_arenas(uint8_t *has_old, int B, ArenaSel sel) {
+  for (int i = threadIdx.x; i < B; i += blockDim.x) has_old[(size_t)sel.arena(blockIdx.x) * B + i] = 0;
 }
 __global__ void k_exp_clear_bots(uint8_t *has_old, int n, const uint8_t *mask) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

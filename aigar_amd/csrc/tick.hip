@@ -37,7 +37,7 @@
 //                             pass: they share no word with it); the arena block then executes
 //                             the plan: respawns the listed players, spawns viruses and stores
 //                             the FOV cache entries of the players the pp pass changed or that
-//                             respawned.  Tiled ticks and initialize(): lists_plan runs here
+//                             respawned.  Tiled ticks: lists_plan runs here
 //   k_pel_update              (tiled ticks only) closing pellet update: the bucket rows whose
 //                             pellets changed are rewritten; extra blocks respawn players (FOV
 //                             cache) and spawn viruses
@@ -1653,15 +1653,6 @@ __device__ __forceinline__ void prow_count(const Dev &d, int a, int j) {
   const int bx = center_bucket_coord(r.x, d.cols), by = center_bucket_coord(r.y, d.cols);
   d.pel_rank[gi] = tile_holds_bucket(d, bx, by) ? atomicAdd(&d.pncnt[(size_t)a * d.PH1 + prow_entry(d, bx, by)], 1) : -1;
 }
-__global__ void k_prow_count(Dev d) {
-  const int gi = GTID;
-  if (gi < d.A * d.Pcap) prow_count(d, gi / d.Pcap, gi % d.Pcap);
-}
-// (the arena-listed variants, aigar_reset_arenas: staged record i % Pcap of arena al[i / Pcap])
-__global__ void k_prow_count_list(Dev d, const int *al, int n) {
-  const int i = GTID;
-  if (i < n * d.Pcap) prow_count(d, al[i / d.Pcap], i % d.Pcap);
-}
 // block-wide exclusive scan of up to 4 values per thread (256 threads); returns the total
 __device__ __forceinline__ int block_scan4(int *v, int *wsum) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -1718,9 +1709,8 @@ __device__ __forceinline__ void prow_scan(const Dev &d, int r, int a) {
     }
   }
 }
-__global__ void __launch_bounds__(256) k_prow_scan(Dev d) { prow_scan(d, blockIdx.x, blockIdx.y); }
-__global__ void __launch_bounds__(256) k_prow_scan_list(Dev d, const int *al) {
-  prow_scan(d, blockIdx.x, al[blockIdx.y]);
+__global__ void __launch_bounds__(256) k_prow_scan(Dev d, ArenaSel sel) {
+  prow_scan(d, blockIdx.x, sel.arena(blockIdx.y));
 }
 __device__ __forceinline__ void prow_scatter(const Dev &d, int a, int j) {
   const int gi = a * d.Pcap + j;
@@ -1735,14 +1725,6 @@ __device__ __forceinline__ void prow_scatter(const Dev &d, int a, int j) {
   const size_t o = (size_t)a * d.PS + pos;
   d.pel[o] = r;
   d.pel_col[o] = d.pn_col[gi];
-}
-__global__ void k_prow_scatter(Dev d) {
-  const int gi = GTID;
-  if (gi < d.A * d.Pcap) prow_scatter(d, gi / d.Pcap, gi % d.Pcap);
-}
-__global__ void k_prow_scatter_list(Dev d, const int *al, int n) {
-  const int i = GTID;
-  if (i < n * d.Pcap) prow_scatter(d, al[i / d.Pcap], i % d.Pcap);
 }
 // ------------------------------------------------------------ T10 merge
 __device__ __forceinline__ void merge_player(const Dev &d, int gp) {
@@ -4488,7 +4470,8 @@ __device__ __forceinline__ void pellet_close_prep(const Dev &d, int a) {
 // it kills waits a tick (p_respawn = 1, appended at c.n_dead): the respawn order,
 // the waiters' places and every count are decided by what is here before it.
 // Untiled ticks run this in k_pp_active's launch, ahead of the pass; tiled ticks
-// and initialize() in k_spawn_plan.
+// in k_spawn_plan.  (A restart has nothing to compact and no dead list: it takes
+// spawn_counts alone, k_restart_ctl.)
 //
 // order-preserving compaction of one list of n entries (KIND 0: viruses, 1: blobs;
 // list order == creation order); returns the new length
@@ -4592,10 +4575,10 @@ __device__ __forceinline__ void dead_partition(const Dev &d, int a, int nd, int 
 // Phase marks: k_pp_active's arena block (PTK 3) marks the compaction and the
 // partition, k_spawn_plan (PTK 5) its marks of old.
 template <int PTK>
-__device__ __forceinline__ void lists_plan(const Dev &d, int a, int init, int *sh, int *gcnt PT_PARAMS) {
+__device__ __forceinline__ void lists_plan(const Dev &d, int a, int *sh, int *gcnt PT_PARAMS) {
   ArenaCtl &c = d.ctl[a];
   const int tid = threadIdx.x;
-  const int p_first = !init && tid < d.B ? d.dead[(size_t)a * d.B + tid] : 0;
+  const int p_first = tid < d.B ? d.dead[(size_t)a * d.B + tid] : 0;
   const uint32_t dirty = c.dirty;
   int n_vir = c.n_vir;
   const int n_blob = c.n_blob, n_blob_live = c.n_blob_live, nd = c.n_dead;
@@ -4615,11 +4598,11 @@ __device__ __forceinline__ void lists_plan(const Dev &d, int a, int init, int *s
   if (PTK == 5) PT_MARK(5, 3);
   if (PTK == 3) PT_MARK(3, 6);
   int n_resp = 0, n_wait = 0;
-  if (!init) dead_partition(d, a, nd, p_first, sh, n_resp, n_wait);
+  dead_partition(d, a, nd, p_first, sh, n_resp, n_wait);
   if (PTK == 3) PT_MARK(3, 7);
   if (tid == 0) {
     sin.n_vir = n_vir;  // (the compacted list's)
-    spawn_counts(d, a, init, n_resp, n_wait, sin);
+    spawn_counts(d, a, 0, n_resp, n_wait, sin);
   }
   __syncthreads();
   if (PTK == 5) PT_MARK(5, 4);
@@ -4655,7 +4638,7 @@ __global__ void __launch_bounds__(256) k_pp_active(Dev d, int close) {
   if ((int)blockIdx.x >= nblocks) {
     __shared__ int l_sh[32], l_gcnt[SG_CAP + 1];
     const int a = blockIdx.x - nblocks;
-    lists_plan<3>(d, a, 0, l_sh, l_gcnt PT_ARGS);
+    lists_plan<3>(d, a, l_sh, l_gcnt PT_ARGS);
     pellet_close_prep(d, a);
     PT_MARK(3, 5);
     return;
@@ -4664,7 +4647,7 @@ __global__ void __launch_bounds__(256) k_pp_active(Dev d, int close) {
 }
 // pp (tick only): playerPlayerOverlap's serial pass first, by wave 0 of the
 // arena's block (its pending bitmap in the dynamic LDS)
-// close 0 / 1 (initialize(), tiled ticks): then lists_plan; close 1: then the
+// close 0 / 1 (tiled ticks): then lists_plan; close 1: then the
 // closing pellet update's step 1 (pellet_close_prep); k_pel_update follows
 // close 2 (untiled ticks: the tick's last launch; k_pp_active's arena block has
 // compacted the lists, partitioned the dead list, taken every count and closed
@@ -4684,8 +4667,7 @@ __device__ __forceinline__ void pel_row_update(const Dev &d, int a, int r, PelRo
 __device__ __forceinline__ void spawn_virus(const Dev &d, int gi);
 __device__ __forceinline__ void spawn_player(const Dev &d, int gp, int j, int init, double *ox = nullptr,
                                              double *oy = nullptr);
-__global__ void __launch_bounds__(1024) k_spawn_plan(Dev d, int init, int64_t *scr_k, int *scr_v, int pp,
-                                                     int close) {
+__global__ void __launch_bounds__(1024) k_spawn_plan(Dev d, int64_t *scr_k, int *scr_v, int pp, int close) {
   FLOOR(7);
   if (close == 2 && (int)blockIdx.x >= d.A) {
     if (threadIdx.x >= PU_T) return;  // (left before any barrier: the row's barriers count the four waves that stay)
@@ -4730,7 +4712,7 @@ __global__ void __launch_bounds__(1024) k_spawn_plan(Dev d, int init, int64_t *s
   }
   PT_MARK(5, 1);
   if (close != 2) {
-    lists_plan<5>(d, a, init, sflag, gcnt PT_ARGS);
+    lists_plan<5>(d, a, sflag, gcnt PT_ARGS);
     if (close == 1) pellet_close_prep(d, a);
     PT_MARK(5, 5);
     return;
@@ -4866,12 +4848,6 @@ __device__ __forceinline__ int spawn_counts_rest(const Dev &d, int a, int init, 
   return kv;
 }
 
-__global__ void k_pnew_commit(Dev d) {
-  int a = GTID;
-  if (a >= d.A) return;
-  d.ctl[a].n_pnew += d.ctl[a].n_spawn_p;
-}
-
 // spawn j of this tick (j < n_spawn_p): its record, a function of (key, counter) only
 __device__ __forceinline__ void spawn_pellet_rec(const Dev &d, const ArenaCtl &c, int j, double &x, double &y,
                                                  double &m, int64_t &seq) {
@@ -4911,7 +4887,6 @@ __device__ __forceinline__ void spawn_pellet(const Dev &d, int gi) {
   d.pn[o] = PelRec{(double)x, (double)y, m, c.seq_base_spawn + j};
   d.pn_col[o] = -1;  // Cell(..., None): a colour of its own
 }
-__global__ void k_spawn_pellets(Dev d) { spawn_pellet(d, GTID); }
 __device__ __forceinline__ void spawn_virus(const Dev &d, int gi) {
   if (gi >= d.A * d.Vcap) return;
   int a = gi / d.Vcap, j = gi - a * d.Vcap;
@@ -4939,7 +4914,6 @@ __device__ __forceinline__ void spawn_virus(const Dev &d, int gi) {
   d.v_seq[o] = c.seq_base_spawn + c.n_spawn_p + j;
   d.v_flags[o] = F_ALIVE;  // addVirus: not hashed until the next rebuild
 }
-__global__ void k_spawn_viruses(Dev d) { spawn_virus(d, GTID); }
 // player gp (= arena a's player p) spawns j-th in spawnPlayers' order (its position also to *ox, *oy)
 __device__ __forceinline__ void spawn_player(const Dev &d, int gp, int j, int init, double *ox, double *oy) {
   const int a = gp / d.B, p = gp - a * d.B;
@@ -4976,10 +4950,6 @@ __device__ __forceinline__ void spawn_player(const Dev &d, int gp, int j, int in
     *ox = x;
     *oy = y;
   }
-}
-__global__ void k_spawn_players(Dev d, int init) {  // Field.initialize: every player, in order
-  const int gp = GTID;
-  if (gp < d.NP) spawn_player(d, gp, gp % d.B, init);
 }
 // the end of spawnStuff for live-or-dead player gp: a dead player whose respawn
 // slot k_spawn_plan set respawns, then the FOV cache of the end-of-tick state
@@ -5478,21 +5448,6 @@ __device__ __forceinline__ void init_ctl(const Dev &d, ArenaCtl &c, uint64_t see
   for (int k = 0; k < 8; k++) c.stat[k] = 0;
 }
 
-__global__ void k_init_ctl(Dev d, uint64_t seed) {
-  int a = GTID;
-  if (a >= d.A) return;
-  init_ctl(d, d.ctl[a], seed, a);
-}
-// aigar_reset_arenas: the listed arenas only, each the world a one-arena handle
-// gets from aigar_reset(seeds[i]) -- so the key's arena word is 0.  The whole
-// control block restarts (as aigar_load_state writes it), not only init_ctl's fields.
-__global__ void k_init_ctl_list(Dev d, const int *al, const uint64_t *seeds, int n) {
-  const int i = GTID;
-  if (i >= n) return;
-  ArenaCtl &c = d.ctl[al[i]];
-  c = ArenaCtl{};
-  init_ctl(d, c, seeds[i], 0);
-}
 
 // ------------------------------------------------------------ launch sequences
 static inline int nblk(long n, int t) { return (int)((n + t - 1) / t); }
@@ -5501,14 +5456,6 @@ struct Scratch {
   int64_t *k;
   int *v;
 };
-
-// Field.initialize's pellets: the staging list -> home 0 of every row (counting sort)
-void launch_pellet_rows(const Dev &d, hipStream_t s) {
-  const long n = (long)d.A * d.Pcap;
-  hipLaunchKernelGGL(k_prow_count, dim3(nblk(n, 256)), dim3(256), 0, s, d);
-  hipLaunchKernelGGL(k_prow_scan, dim3(d.cols, d.A), dim3(256), 0, s, d);
-  hipLaunchKernelGGL(k_prow_scatter, dim3(nblk(n, 256)), dim3(256), 0, s, d);
-}
 
 
 // playerPelletOverlap + playerBlobOverlap: prep, reservation rounds (>= 1),
@@ -5527,7 +5474,6 @@ static void launch_food(const Dev &d, hipStream_t s, int rounds, Scratch scr, in
   if (!fold) hipLaunchKernelGGL(k_food_serial, dim3(d.A), dim3(64), 0, s, d, scr.k, scr.v, rounds);
 }
 
-void launch_player_fov(const Dev &d, hipStream_t s);
 // One Field.update(): a single stream of dependent launches (captured once into a
 // hipGraph by api.hip).  Forking independent phases onto a second stream was
 // measured slower on MI355X (cross-queue dependencies cost more than the
@@ -5555,7 +5501,7 @@ void launch_tick_post(const Dev &d, hipStream_t s, int64_t *scr_k, int *scr_v) {
   hipLaunchKernelGGL(k_pp_active, dim3(nblk(d.NP, 4)), dim3(256), 0, s, d, 0);
   // playerPlayerOverlap's serial pass + spawnStuff's plan + the end-of-tick virus
   // grid + the closing pellet update's sorted kill / join lists (and the pellet spawns)
-  hipLaunchKernelGGL(k_spawn_plan, dim3(d.A), dim3(1024), pp_lds_bytes(d), s, d, 0, scr_k, scr_v, 1, 1);
+  hipLaunchKernelGGL(k_spawn_plan, dim3(d.A), dim3(1024), pp_lds_bytes(d), s, d, scr_k, scr_v, 1, 1);
   // the closing pellet update (survivors U joining staged records -> the new
   // current buffer) + the rest of spawnStuff as extra blocks: player respawns
   // with the FOV cache, virus spawns (fused into the pellet threads the FOV
@@ -5582,7 +5528,7 @@ void launch_tick(const Dev &d, hipStream_t s, int rounds, int64_t *scr_k, int *s
   launch_food(d, s, rounds, Scratch{scr_k, scr_v}, 0, 1);
   hipLaunchKernelGGL(k_pp_active, dim3(nblk(d.NP, 4) + d.A + nblk(d.NP, 256)), dim3(256), 0, s, d, 1);
   hipLaunchKernelGGL(k_spawn_plan, dim3(d.A + d.A * d.cols), dim3(1024), std::max(pp_lds_bytes(d), sizeof(PelRowLds)),
-                     s, d, 0, scr_k, scr_v, 1, 2);
+                     s, d, scr_k, scr_v, 1, 2);
 }
 
 // ------------------------------------------------------------ C4 tile passes
@@ -5824,43 +5770,19 @@ void launch_tile_apply(const Dev &d, hipStream_t s, int box_recs, int first) {
   hipLaunchKernelGGL(k_tile_apply, dim3(d.ntiles), dim3(256), 0, s, d, box_recs, first);
 }
 
-// Field.initialize()/reset() (field.py:57-83): players first (seq 0..B-1, empty
-// player hash), then spawnStuff's pellets and viruses.
-void launch_reset(const Dev &d, hipStream_t s, uint64_t seed) {
-  (void)hipMemsetAsync(d.c_flags, 0, sizeof(uint32_t) * (size_t)kMaxCells * d.NP, s);
-  (void)hipMemsetAsync(d.v_flags, 0, sizeof(uint32_t) * (size_t)d.A * d.Vcap, s);
-  (void)hipMemsetAsync(d.b_flags, 0, sizeof(uint32_t) * (size_t)d.A * d.Ecap, s);
-  (void)hipMemsetAsync(d.p_split, 0, sizeof(int) * d.NP, s);
-  (void)hipMemsetAsync(d.p_eject, 0, sizeof(int) * d.NP, s);
-  (void)hipMemsetAsync(d.pel_owner, 0, sizeof(uint64_t) * (size_t)d.A * d.PD, s);
-  (void)hipMemsetAsync(d.pel_dead, 0, (size_t)d.A * d.PD, s);
-  (void)hipMemsetAsync(d.b_owner, 0, sizeof(uint64_t) * (size_t)d.A * d.Ecap, s);
-  (void)hipMemsetAsync(d.scan_state, 0, sizeof(unsigned long long) * 2 * (size_t)d.A * d.scan_tiles, s);
-  (void)hipMemsetAsync(d.pl_state, 0, sizeof(unsigned long long) * (size_t)d.A * d.pl_tiles, s);
-  hipLaunchKernelGGL(k_init_ctl, dim3(nblk(d.A, 64)), dim3(64), 0, s, d, seed);
-  (void)hipMemsetAsync(d.occ, 0, sizeof(unsigned long long) * (size_t)d.A * d.occ_words, s);
-  hipLaunchKernelGGL(k_spawn_plan, dim3(d.A), dim3(1024), 0, s, d, 1, (int64_t *)nullptr, (int *)nullptr, 0, 0);
-  hipLaunchKernelGGL(k_spawn_players, dim3(nblk(d.NP, 256)), dim3(256), 0, s, d, 1);
-  hipLaunchKernelGGL(k_spawn_pellets, dim3(nblk((long)d.A * d.Pcap, 256)), dim3(256), 0, s, d);
-  if (d.virus_enabled) hipLaunchKernelGGL(k_spawn_viruses, dim3(nblk((long)d.A * d.Vcap, 256)), dim3(256), 0, s, d);
-  hipLaunchKernelGGL(k_pnew_commit, dim3(nblk(d.A, 64)), dim3(64), 0, s, d);
-  launch_pellet_rows(d, s);  // staging -> the row store
-  launch_player_fov(d, s);
-}
-
-// ---------------------------------------------- aigar_reset_arenas (api.hip)
-// The same sequence for the n arenas of the device list al (distinct, in any
-// order), the other arenas untouched: every kernel maps its block or thread
-// index through the list.  First the listed arenas' slices of what aigar_reset,
-// launch_reset and aigar_load_state clear with whole-buffer memsets, and their
-// bots' restart as aigar_load_state leaves it (commands -1 as after aigar_reset).
+// ------------------------------------------------------------ restart
+// Field.initialize()/reset() (field.py:57-83) of the arenas of a selection
+// (ArenaSel, aigar_dev.h), the other arenas untouched: players first (seq 0..B-1,
+// empty player hash), then spawnStuff's pellets and viruses.  aigar_reset runs it
+// for the whole handle, aigar_reset_arenas for its list; every kernel maps its
+// block or thread index through the selection.
 template <class T>
 __device__ __forceinline__ void fill_slice(T *p, size_t n, T v) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
 }
-constexpr int kClearBlocks = 64;  // blocks per listed arena (the longest slice: PD reservation keys)
-__global__ void __launch_bounds__(256) k_clear_arenas_list(Dev d, const int *al) {
-  const size_t a = al[blockIdx.y], B = d.B, p0 = a * B, H1 = (size_t)d.H + 1, GG = (size_t)d.G * d.G;
+// arena a's slice of every world buffer a fresh world needs cleared
+__device__ __forceinline__ void clear_world(const Dev &d, size_t a) {
+  const size_t B = d.B, p0 = a * B, H1 = (size_t)d.H + 1;
   for (int k = 0; k < kMaxCells; k++) fill_slice(d.c_flags + (size_t)k * d.NP + p0, B, 0u);
   fill_slice(d.v_flags + a * d.Vcap, (size_t)d.Vcap, 0u);
   fill_slice(d.b_flags + a * d.Ecap, (size_t)d.Ecap, 0u);
@@ -5879,9 +5801,16 @@ __global__ void __launch_bounds__(256) k_clear_arenas_list(Dev d, const int *al)
   fill_slice(d.bstart + a * H1, H1, 0);
   fill_slice(d.bmap + a * 64, (size_t)64, (uint64_t)0);
   fill_slice(d.v_active + a * d.Vcap, (size_t)d.Vcap, 0);
-  // the bots: commands, lastMass = None, lastFovSize, currentAction, the history grids
-  fill_slice(d.p_cmdx + p0, B, -1.0);
-  fill_slice(d.p_cmdy + p0, B, -1.0);
+}
+// Bot.reset (bot.py:125-164) of arena a's bots: lastMass = None, lastFovSize,
+// currentAction, the history grids, the mass history; cmds: the commands to -1
+// (a loaded snapshot brings its own)
+__device__ __forceinline__ void clear_bots(const Dev &d, size_t a, int cmds) {
+  const size_t B = d.B, p0 = a * B, GG = (size_t)d.G * d.G;
+  if (cmds) {
+    fill_slice(d.p_cmdx + p0, B, -1.0);
+    fill_slice(d.p_cmdy + p0, B, -1.0);
+  }
   fill_slice(d.o_last_mass + p0, B, __builtin_nan(""));
   fill_slice(d.o_lastfov + p0, B, 0.0);
   fill_slice(d.o_act_cur + p0 * 4, B * 4, 0.0);
@@ -5892,48 +5821,69 @@ __global__ void __launch_bounds__(256) k_clear_arenas_list(Dev d, const int *al)
   if (d.sc)  // AIGAR_FLAG_SCORE: a new episode's mass history starts empty
     for (int f = 0; f < 4; f++) fill_slice(d.sc + (size_t)f * d.NP + p0, B, 0.0);
 }
-// k_spawn_plan's init = 1 path for arena al[i]: nothing to compact in a fresh
-// world, no dead list -- spawnStuff's counts alone
-__global__ void k_spawn_plan_list(Dev d, const int *al, int n) {
-  const int i = GTID;
-  if (i >= n) return;
-  const int a = al[i];
-  spawn_counts(d, a, 1, 0, 0, spawn_in(d.ctl[a]));
+// blocks per arena: four elements a thread of the longest slices (the reservation
+// keys, a history grid), so that a full-size arena's clear spreads over the device
+static int clear_blocks(const Dev &d) {
+  const long longest = std::max<long>(d.PD, (long)d.B * d.G * d.G);
+  return (int)std::min<long>(1024, std::max<long>(64, (longest + 1023) / 1024));
 }
-__global__ void k_spawn_players_list(Dev d, const int *al, int n) {
-  const int i = GTID;
-  if (i < n * d.B) spawn_player(d, al[i / d.B] * d.B + i % d.B, i % d.B, 1);
+__global__ void __launch_bounds__(256) k_restart_clear(Dev d, ArenaSel sel, int world, int cmds) {
+  const size_t a = sel.arena(blockIdx.y);
+  if (world) clear_world(d, a);
+  clear_bots(d, a, cmds);
 }
-__global__ void k_spawn_pellets_list(Dev d, const int *al, int n) {
+// the whole control block restarts (as aigar_load_state writes it), then
+// spawnStuff's counts: nothing to compact in a fresh world and no dead list
+__global__ void k_restart_ctl(Dev d, ArenaSel sel) {
   const int i = GTID;
-  if (i < n * d.Pcap) spawn_pellet(d, al[i / d.Pcap] * d.Pcap + i % d.Pcap);
+  if (i >= sel.n) return;
+  const int a = sel.arena(i);
+  ArenaCtl &c = d.ctl[a];
+  c = ArenaCtl{};
+  init_ctl(d, c, sel.seed_of(i), sel.key_arena(i));
+  spawn_counts(d, a, 1, 0, 0, spawn_in(c));
 }
-__global__ void k_spawn_viruses_list(Dev d, const int *al, int n) {
+// one thread per item j of every selected arena (per items an arena)
+enum { RS_PLAYER, RS_PELLET, RS_VIRUS, RS_ROW_COUNT, RS_ROW_SCATTER };
+template <int STEP>
+__global__ void k_restart_items(Dev d, ArenaSel sel, int per) {
   const int i = GTID;
-  if (i < n * d.Vcap) spawn_virus(d, al[i / d.Vcap] * d.Vcap + i % d.Vcap);
+  if (i >= sel.n * per) return;
+  const int a = sel.arena(i / per), j = i % per;
+  if (STEP == RS_PLAYER) spawn_player(d, a * d.B + j, j, 1);  // Field.initialize: every player, in order
+  if (STEP == RS_PELLET) spawn_pellet(d, a * d.Pcap + j);
+  if (STEP == RS_VIRUS) spawn_virus(d, a * d.Vcap + j);
+  if (STEP == RS_ROW_COUNT) prow_count(d, a, j);
+  if (STEP == RS_ROW_SCATTER) prow_scatter(d, a, j);
 }
-__global__ void k_pnew_commit_list(Dev d, const int *al, int n) {
+__global__ void k_restart_commit(Dev d, ArenaSel sel) {  // the spawned pellets are staged
   const int i = GTID;
-  if (i >= n) return;
-  ArenaCtl &c = d.ctl[al[i]];
+  if (i >= sel.n) return;
+  ArenaCtl &c = d.ctl[sel.arena(i)];
   c.n_pnew += c.n_spawn_p;
 }
-void launch_player_fov_list(const Dev &d, hipStream_t s, const int *al, int n);
-// al, seeds: device lists of n entries (0 < n <= A), checked by the caller
-void launch_reset_arenas(const Dev &d, hipStream_t s, const int *al, const uint64_t *seeds, int n) {
-  hipLaunchKernelGGL(k_clear_arenas_list, dim3(kClearBlocks, n), dim3(256), 0, s, d, al);
-  hipLaunchKernelGGL(k_init_ctl_list, dim3(nblk(n, 64)), dim3(64), 0, s, d, al, seeds, n);
-  hipLaunchKernelGGL(k_spawn_plan_list, dim3(nblk(n, 64)), dim3(64), 0, s, d, al, n);
-  hipLaunchKernelGGL(k_spawn_players_list, dim3(nblk((long)n * d.B, 256)), dim3(256), 0, s, d, al, n);
-  const long np = (long)n * d.Pcap;
-  hipLaunchKernelGGL(k_spawn_pellets_list, dim3(nblk(np, 256)), dim3(256), 0, s, d, al, n);
-  if (d.virus_enabled)
-    hipLaunchKernelGGL(k_spawn_viruses_list, dim3(nblk((long)n * d.Vcap, 256)), dim3(256), 0, s, d, al, n);
-  hipLaunchKernelGGL(k_pnew_commit_list, dim3(nblk(n, 64)), dim3(64), 0, s, d, al, n);
-  hipLaunchKernelGGL(k_prow_count_list, dim3(nblk(np, 256)), dim3(256), 0, s, d, al, n);
-  hipLaunchKernelGGL(k_prow_scan_list, dim3(d.cols, n), dim3(256), 0, s, d, al);
-  hipLaunchKernelGGL(k_prow_scatter_list, dim3(nblk(np, 256)), dim3(256), 0, s, d, al, n);
-  launch_player_fov_list(d, s, al, n);
+void launch_player_fov(const Dev &d, hipStream_t s, const ArenaSel &sel);
+// sel: 0 < n <= A distinct arenas in range (a device list: checked by the caller)
+void launch_restart(const Dev &d, hipStream_t s, const ArenaSel &sel) {
+  const int n = sel.n;
+  const auto items = [&](auto kernel, int per) {
+    hipLaunchKernelGGL(kernel, dim3(nblk((long)n * per, 256)), dim3(256), 0, s, d, sel, per);
+  };
+  hipLaunchKernelGGL(k_restart_clear, dim3(clear_blocks(d), n), dim3(256), 0, s, d, sel, 1, 1);
+  hipLaunchKernelGGL(k_restart_ctl, dim3(nblk(n, 64)), dim3(64), 0, s, d, sel);
+  items(k_restart_items<RS_PLAYER>, d.B);
+  items(k_restart_items<RS_PELLET>, d.Pcap);
+  if (d.virus_enabled) items(k_restart_items<RS_VIRUS>, d.Vcap);
+  hipLaunchKernelGGL(k_restart_commit, dim3(nblk(n, 64)), dim3(64), 0, s, d, sel);
+  // Field.initialize's pellets: the staging list -> home 0 of every row (counting sort)
+  items(k_restart_items<RS_ROW_COUNT>, d.Pcap);
+  hipLaunchKernelGGL(k_prow_scan, dim3(d.cols, n), dim3(256), 0, s, d, sel);
+  items(k_restart_items<RS_ROW_SCATTER>, d.Pcap);
+  launch_player_fov(d, s, sel);
+}
+// the bots' restart alone (aigar_load_state: the world and the commands come from the snapshot)
+void launch_restart_bots(const Dev &d, hipStream_t s, const ArenaSel &sel) {
+  hipLaunchKernelGGL(k_restart_clear, dim3(clear_blocks(d), sel.n), dim3(256), 0, s, d, sel, 0, 0);
 }
 
 #ifdef AIGAR_PHASE_TIMING

@@ -1,7 +1,14 @@
 """GPU: aigar_reset_arenas -- Field.reset of single arenas of a batched handle on
 the device.  A reset arena must be the world of a one-arena handle after
 reset(seed) (state, later ticks, observations, bot state), every other arena must
-not notice; the vectorised environment's episode ends go through it."""
+not notice; the vectorised environment's episode ends go through it.
+
+aigar_reset (every arena), aigar_reset_arenas (the listed ones) and aigar_load_state
+(the bots of one arena) share one restart path on the device: the last four tests
+pin what the three calls have in common -- a reset dirty handle is a fresh handle,
+a loaded arena's bots restart and its neighbours do not notice, the learners' side
+buffers (pixel history, old states, Orn-Uhl state) restart with their arena, and a
+tiled handle resets like a new one."""
 import ctypes as C
 import types
 
@@ -256,3 +263,173 @@ def test_bad_lists_are_refused_on_the_host():
     with pytest.raises(RuntimeError, match="tiled"):
         tiled.reset_arenas([0], [7])
     tiled.close()
+
+
+def test_reset_of_a_dirty_handle_is_a_fresh_handle():
+    """Every arena's state, key, observation row (history channels and extras) and reward equal
+    a newly created handle's after the same reset, and stay so over later ticks.  One extra is
+    compared on its own: Bot.reset leaves lastAction alone (bot.py:125-164 resets currentAction
+    only), so the row's secondLastAction is the bot's from before the reset, as
+    test_bot_state_restarts pins for reset_arenas; a new handle's is zero."""
+    s = 17
+    g, f = dirty_handle(decisions=4), _lib.Stepper(config())
+    assert_dirty(g)
+    o_before = g.observe()
+    was_alive = ~np.isnan(o_before[:, 0])  # (a dead player's row is NaN)
+    assert was_alive.any() and o_before[was_alive][:, ACT_PREV].any()
+    keep = np.ones(o_before.shape[1], bool)
+    keep[ACT_PREV] = False
+
+    def same_rows(t):
+        og, of = g.observe(), f.observe()
+        assert parity.obs_close(og[:, keep], of[:, keep], 0.0), t
+        live = ~np.isnan(of[:, 0])
+        assert live.all() if t == "reset" else live.any(), t
+        assert np.array_equal(og[was_alive & live][:, ACT_PREV], o_before[was_alive & live][:, ACT_PREV]), t
+        assert not of[live][:, ACT_PREV].any(), t
+
+    g.reset(s)
+    f.reset(s)
+    for a in range(A):
+        sg, sf = g.get_state(a), f.get_state(a)
+        assert parity.diff_states(sg, sf, ftol=0.0) == [], a
+        assert sg["philox_key"].tolist() == [s, (a << 32) | 0x9E3779B9] == sf["philox_key"].tolist(), a
+    same_rows("reset")
+    assert np.isnan(g.rewards(update_last=False)).all() and np.isnan(f.rewards(update_last=False)).all()
+    rng = np.random.default_rng(s)
+    for t in range(10):
+        cmd = parity.synthetic_commands(rng, None, A * B, SIZE, 0.1, 0.1)
+        for h in (g, f):
+            h.set_commands(cmd)
+            h.step(1)
+        for a in range(A):
+            assert np.array_equal(g.events(a), f.events(a)), (t, a)
+            assert same_state(g.get_state(a), f.get_state(a)), (t, a)
+        same_rows(t)
+    g.close()
+    f.close()
+
+
+def test_load_state_restarts_the_arenas_bots_and_spares_its_neighbours():
+    s = 19
+    g, twin = dirty_handle(decisions=4), dirty_handle(decisions=4)
+    ref = fresh_one(s)
+    loaded = ref.get_state()
+    g.load_state(loaded, 1)
+    assert same_state(g.get_state(1), loaded)
+    rg, rt = g.rewards(update_last=False), twin.rewards(update_last=False)
+    assert np.isnan(rg[rows(1)]).all()  # lastMass is None
+    og, ot = g.observe(), twin.observe()
+    assert not np.isnan(og[rows(1)]).any()
+    assert not og[rows(1), HIST].any() and not og[rows(1), LAST_FOV].any()
+    assert np.abs(np.nan_to_num(ot[rows(1), HIST])).max() > 0  # (the twin's bots kept theirs)
+    for a in (0, 2):
+        assert same_state(g.get_state(a), twin.get_state(a)), a
+        assert np.isfinite(rg[rows(a)]).any() and np.array_equal(rg[rows(a)], rt[rows(a)], equal_nan=True), a
+        assert parity.obs_close(og[rows(a)], ot[rows(a)], 0.0), a
+    rng = np.random.default_rng(s)
+    for t in range(5):
+        cmd = parity.synthetic_commands(rng, None, A * B, SIZE, 0.1, 0.1)
+        for h in (g, twin):
+            h.set_commands(cmd)
+            h.step(1)
+        og, ot = g.observe(), twin.observe()
+        for a in (0, 2):
+            assert np.array_equal(g.events(a), twin.events(a)), (t, a)
+            assert same_state(g.get_state(a), twin.get_state(a)), (t, a)
+            assert parity.obs_close(og[rows(a)], ot[rows(a)], 0.0), (t, a)
+    for h in (g, twin, ref):
+        h.close()
+
+
+SIDE = 12  # pixel state: SIDE x SIDE x [current | previous frame]
+
+
+def learner_handle(draws):
+    """The 3-arena world with a pixel history (AIGAR_PIX_LAST), a replay memory and
+    Orn-Uhl noise, after one actor-critic decision per entry of draws."""
+    g = _lib.Stepper(config())
+    g.reset(3)
+    g.pixel_config(SIDE, last=True, color_seed=1)
+    g.exp_config(1024, dtype="float32")
+    g.noise_config(2, "Orn-Uhl", mu_dtype="float64", seed=5)
+    last = None
+    for d in draws:
+        last = decide(g, d)
+    return g, last
+
+
+def decide(g, draw):
+    """One env_step_ac with the caller's mu rows and uniforms: (noisy actions, pixel states,
+    transitions the decision added to the memory)."""
+    import torch
+    dev = lambda x: torch.as_tensor(np.ascontiguousarray(x), device="cuda")  # noqa: E731
+    mu, u = draw
+    reward = torch.zeros(A * B, dtype=torch.float64, device="cuda")
+    obs = torch.zeros(g.pixel_state_shape, dtype=torch.float32, device="cuda")
+    noisy = torch.full((A * B, 2), -7.0, dtype=torch.float64, device="cuda")
+    before = g.exp_info()["added"]
+    g.env_step_ac(dev(mu), dev(np.array([0.3])), reward, obs, u=dev(u), noisy=noisy)
+    g.sync()
+    return noisy.cpu().numpy(), obs.cpu().numpy(), g.exp_info()["added"] - before
+
+
+@pytest.mark.parametrize("call", ("reset", "reset_arenas", "load_state"))
+def test_side_buffers_restart_with_their_arena(call):
+    """has_old, the Orn-Uhl state and the pixel history of the restarted arenas read as on a
+    fresh handle at the next decision (no transition, the noise of a zero state, a zero
+    previous frame); the other arenas' go on as the twin's."""
+    s = 23
+    rng = np.random.default_rng(s)
+    draws = [(rng.random((A * B, 2)), rng.integers(0, 2 ** 53, (A * B, 2, 4, 2)) * 2.0 ** -53) for t in range(4)]
+    (g, _), (twin, last) = learner_handle(draws[:3]), learner_handle(draws[:3])
+    fresh, _ = learner_handle([])
+    had_old = ~np.isnan(last[1][:, 0, 0, 0])  # the bots alive at the last decision hold an old state
+    assert last[2] > 0 and had_old[rows(0)].any() and had_old[rows(2)].any()
+    if call == "reset":
+        g.reset(s)
+    elif call == "reset_arenas":
+        g.reset_arenas([1], [s])
+    else:
+        ref = fresh_one(s)
+        g.load_state(ref.get_state(), 1)
+        ref.close()
+    restarted = (0, 1, 2) if call == "reset" else (1,)
+    (ng, og, added_g), (nt, ot, added_t), (nf, of, added_f) = (decide(h, draws[3]) for h in (g, twin, fresh))
+    assert added_f == 0 and added_t == int(had_old.sum())
+    assert added_g == sum(int(had_old[rows(a)].sum()) for a in range(A) if a not in restarted)
+    for a in range(A):
+        r = rows(a)
+        if a in restarted:
+            assert not np.isnan(nf[r]).any() and np.array_equal(ng[r].view(np.uint64), nf[r].view(np.uint64)), a
+            assert not np.isnan(og[r]).any() and not og[r][..., 1].any() and not of[r][..., 1].any(), a
+        else:
+            assert np.array_equal(ng[r].view(np.uint64), nt[r].view(np.uint64)), a
+            assert np.array_equal(og[r], ot[r], equal_nan=True), a
+            live = ~np.isnan(nt[r][:, 0])
+            assert (nt[r][live] != nf[r][live]).any() and np.nan_to_num(ot[r][..., 1]).any(), a  # (not a fresh bot's)
+    for h in (g, twin, fresh):
+        h.close()
+
+
+def test_reset_of_a_dirty_tiled_handle_is_a_fresh_tiled_handle():
+    from aigar_amd.tiles import TiledArena
+    s = 29
+    cfg = make_config(bots=B, field_size=SIZE, virus=True, max_viruses=6, channels=CH, extras=EX)
+    ta, tf = TiledArena(cfg, 2, 1), TiledArena(cfg, 2, 1)
+    ta.reset(3)
+    rng = np.random.default_rng(s)
+    for t in range(12):
+        ta.set_commands(parity.synthetic_commands(rng, None, B, SIZE, 0.1, 0.1))
+        ta.tick()
+        ta.observe()  # (history grids, observers and hand-offs to restart)
+    ta.reset(s)
+    tf.reset(s)
+    assert parity.diff_states(ta.get_state(), tf.get_state(), ftol=0.0) == []
+    for x, y in zip(ta.tiles, tf.tiles):
+        assert same_state(x.get_state(), y.get_state())
+    og, of = ta.observe(), tf.observe()
+    assert not np.isnan(of).any() and parity.obs_close(og, of, 0.0)
+    assert np.array_equal(ta.last_observers, tf.last_observers)
+    ta.close()
+    tf.close()
