@@ -140,6 +140,8 @@ def load(build_if_missing=False):
         "aigar_spg_reset": [vp],
         "aigar_net_get_weights": [vp, i32, i32, vp, vp, i32],
         "aigar_net_pad_check": [vp, i32, C.POINTER(C.c_int64)],
+        "aigar_train_config_cnn": [vp, C.POINTER(_abi.TrainParams)],
+        "aigar_net_get_conv_weights": [vp, i32, i32, vp, vp, i32],
         "aigar_exp_extra_get": [vp, vp, i32, vp, vp],
         "aigar_exp_extra_set": [vp, vp, vp, i32],
         "aigar_warnings": [vp, i32, C.POINTER(C.c_uint32)],
@@ -800,7 +802,24 @@ class Stepper:
         b [out]) float32 per dense layer, numpy arrays or (device=True) device tensors.  which:
         "online", or with a train configuration "target", "m", "v" (Adam's state)."""
         n_in, units, _ = self._need_net("net_get_weights")
-        return self._read_dense("net_get_weights", self._NET_CODES, which, n_in, units, device)
+        if which not in self._NET_CODES:
+            raise ValueError("net_get_weights: which must be one of %s" % sorted(self._NET_CODES))
+        out = []
+        if self.conv is not None:  # the conv pairs first, (W [k, k, Cin, F], b [F]) (aigar_net_get_conv_weights)
+            cin = self.conv[1]
+            for l, (k, _, f) in enumerate(self.conv[2]):
+                if device:
+                    import torch
+                    dev = "cuda:%d" % self.cfg.device
+                    W = torch.empty((k, k, cin, f), dtype=torch.float32, device=dev)
+                    b = torch.empty((f,), dtype=torch.float32, device=dev)
+                else:
+                    W, b = np.empty((k, k, cin, f), np.float32), np.empty((f,), np.float32)
+                self._chk(self.L.aigar_net_get_conv_weights(self.h, self._NET_CODES[which], l, _ptr(W)[0], _ptr(b)[0],
+                                                            int(device)))
+                out.append((W, b))
+                cin = f
+        return out + self._read_dense("net_get_weights", self._NET_CODES, which, n_in, units, device)
 
     def net_pad_check(self, which="online"):
         """A debug read (aigar_net_pad_check): how many padded entries of the packed copies are
@@ -850,6 +869,21 @@ class Stepper:
         prm = _abi.TrainParams(int(batch), int(min_size), int(target_steps), 0, float(lr), float(beta1), float(beta2),
                                float(epsilon), float(discount))
         self._chk(self.L.aigar_train_config(self.h, C.byref(prm)))
+        self.trn = int(batch)
+
+    def train_config_cnn(self, batch=32, min_size=0, target_steps=0, lr=1e-4, beta1=0.9, beta2=0.999, epsilon=1e-7,
+                         discount=0.85):
+        """train_config for an acting network with a conv part (aigar_train_config_cnn): the same
+        parameters; needs net_config with a CnnSpec (linear head) and an exp_config whose states
+        are the conv part's images.  train_step, train_info, train_td, train_sync_target and
+        train_reset serve it.  train_config_cnn(None) turns it off."""
+        if batch is None:
+            self._chk(self.L.aigar_train_config_cnn(self.h, None))
+            self.trn = None
+            return
+        prm = _abi.TrainParams(int(batch), int(min_size), int(target_steps), 0, float(lr), float(beta1), float(beta2),
+                               float(epsilon), float(discount))
+        self._chk(self.L.aigar_train_config_cnn(self.h, C.byref(prm)))
         self.trn = int(batch)
 
     def train_step(self, n=1, u=None):

@@ -58,6 +58,7 @@ using namespace aigar;
 #include "net.inc"
 #include "conv.inc"
 #include "train.inc"
+#include "convtrain.inc"
 #include "actrain.inc"
 #include "dpg.inc"
 #include "spg.inc"
@@ -162,6 +163,8 @@ struct TrainKey {  // aigar_*_step: one training step (every buffer is the train
   int kind;   // whose step it is: kTrainQ, kTrainCacla, kTrainDpg, kTrainSpg
   int has_u;  // the draws come from the handle's u row (the caller's draws are copied there)
   int has_zu;  // SPG: the search's uniforms come from the trainer's zu rows (the caller's are copied there)
+  int pad;
+  Conv conv;  // kTrainQ under aigar_train_config_cnn: the conv part the step runs through (n_conv 0: none)
 };
 enum { kTrainQ, kTrainCacla, kTrainDpg, kTrainSpg };
 struct EnvKey {  // aigar_env_step*: one learner decision
@@ -325,6 +328,7 @@ struct aigar_handle {
   // The trainer (batch 0: off).  At most one is configured -- each needs another head or critic --
   // so they share one block of buffers and one step graph (trainer_free).
   Train trn;     // aigar_train_config: Q-learning (train.inc)
+  ConvTrain ctrn{};  // aigar_train_config_cnn: ... of a network with a conv part, trn its dense part (convtrain.inc)
   ACTrain act;   // aigar_actrain_config: CACLA (actrain.inc)
   DPGTrain dpg;  // aigar_dpg_config: DPG (dpg.inc)
   SPGTrain spg;  // aigar_spg_config: SPG on DPG's critic half (spg.inc)
@@ -1474,6 +1478,7 @@ static void trainer_free(aigar_handle *h) {
   h->train.drop(h);
   h->trn_mem.release();
   h->trn = Train{};
+  h->ctrn = ConvTrain{};
   h->act = ACTrain{};
   h->dpg = DPGTrain{};
   h->spg = SPGTrain{};
@@ -2558,6 +2563,7 @@ static int trainer_step(aigar_handle *h, const char *who, int kind, int n_steps,
   k.kind = kind;
   k.has_u = u ? 1 : 0;
   k.has_zu = zu ? 1 : 0;
+  if (kind == kTrainQ && h->ctrn.on) key_put(k.conv, h->conv);
   const int has = k.has_u | k.has_zu << 1;
   const bool graph = h->use_graph;
   if (graph && !h->train.ensure(h, k, [&](hipStream_t cs) { launch(h, cs, has); }))
@@ -2655,7 +2661,7 @@ extern "C" int aigar_train_config(aigar_handle *h, const aigar_train_params *p) 
   }
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipStreamSynchronize(h->stream));
-  if (p || h->trn.batch) trainer_free(h);  // (a null p turns off this trainer, not another)
+  if (p || (h->trn.batch && !h->ctrn.on)) trainer_free(h);  // (a null p turns off this trainer, not another)
   if (!p) return 0;
   bool ok = true;
   const Train t = train_view(h, ok, train_shared(h, ok, p), h->net, p->lr, true);
@@ -2685,9 +2691,148 @@ static void launch_train_step(aigar_handle *h, hipStream_t s, int has_u) {
   hipLaunchKernelGGL(k_train_tail, dim3(64), dim3(256), 0, s, on, t);
 }
 
+// ... of a network with a conv part (convtrain.inc): the same parameters and the same checks of
+// them under its own name; trn is the dense part's view, ctrn the conv part's.
+static size_t conv_w_bytes(const Conv &c, int l) {
+  const int cin = l ? c.filters[l - 1] : c.channels;
+  return (size_t)conv_k_pad(c.k[l] * c.k[l] * cin) * net_out_pad(c.filters[l]) * sizeof(float);
+}
+static size_t conv_b_bytes(const Conv &c, int l) { return (size_t)net_out_pad(c.filters[l]) * sizeof(float); }
+
+extern "C" int aigar_train_config_cnn(aigar_handle *h, const aigar_train_params *p) {
+  const char *who = "train_config_cnn";
+  if (p && (check_train_sizes(who, p) || check_positive(who, "lr", p->lr) || check_train_adam(who, p))) return -1;
+  if (!h) return fail("null handle");
+  if (p) {
+    if (h->d.tiled) return fail("%s: a tiled handle has no training", who);
+    if (need_net(h, who)) return -1;
+    if (!h->conv.n_conv)
+      return fail("train_config_cnn: the network has no conv part (a dense network is trained by aigar_train_config)");
+    if (h->net.out_act != AIGAR_ACT_LINEAR)
+      return fail("train_config_cnn: the network's head is %s, Q-learning needs a linear head",
+                  net_act_name(h->net.out_act));
+    if (need_exp(h, who)) return -1;
+    const int img = h->conv.side * h->conv.side * h->conv.channels;
+    if (h->exp.L != img)
+      return fail("train_config_cnn: the conv part takes %d x %d x %d = %d values, the memory's states %d values",
+                  h->conv.side, h->conv.side, h->conv.channels, img, h->exp.L);
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (p || h->ctrn.on) trainer_free(h);  // (a null p turns off this trainer, not another)
+  if (!p) return 0;
+  bool ok = true;
+  const Train t = train_view(h, ok, train_shared(h, ok, p), h->net, p->lr, true);
+  const Conv &c = h->conv;
+  ConvTrain ct{};
+  ct.on = 1;
+  for (int l = 0; l < c.n_conv; l++) {
+    const size_t nw = conv_w_bytes(c, l), nb = conv_b_bytes(c, l);
+    const size_t na = (size_t)t.bpad * c.osz[l] * c.osz[l] * c.filters[l] * sizeof(float);
+    const int K = c.k[l] * c.k[l] * (l ? c.filters[l - 1] : c.channels);
+    ct.tw[l] = (float *)train_get(h, ok, nw);
+    ct.tb[l] = (float *)train_get(h, ok, nb);
+    ct.mw[l] = (float *)train_get(h, ok, nw);
+    ct.mb[l] = (float *)train_get(h, ok, nb);
+    ct.vw[l] = (float *)train_get(h, ok, nw);
+    ct.vb[l] = (float *)train_get(h, ok, nb);
+    ct.act[l] = (float *)train_get(h, ok, na);
+    ct.tact[l] = (float *)train_get(h, ok, na);
+    ct.delta[l] = (float *)train_get(h, ok, na);
+    ct.tile0[l + 1] = ct.tile0[l] + (K + 1 + 15) / 16 * (net_out_pad(c.filters[l]) / 16);
+    if (ok) {
+      (void)hipMemcpyAsync(ct.tw[l], c.w[l], nw, hipMemcpyDeviceToDevice, h->stream);
+      (void)hipMemcpyAsync(ct.tb[l], c.b[l], nb, hipMemcpyDeviceToDevice, h->stream);
+    }
+  }
+  if (!ok) {
+    h->trn_mem.release();
+    return fail("train_config_cnn: out of device memory");
+  }
+  HIPCHK(hipGetLastError());
+  h->trn = t;
+  h->ctrn = ct;
+  return 0;
+}
+
+// c on the trainer's buffers: the online pass's kept activations, or the target's filters and activations
+static Conv train_conv(Conv c, const ConvTrain &ct, int bpad, bool target) {
+  c.cap = bpad;
+  for (int l = 0; l < c.n_conv; l++) {
+    c.act[l] = target ? ct.tact[l] : ct.act[l];
+    if (target) {
+      c.w[l] = ct.tw[l];
+      c.b[l] = ct.tb[l];
+    }
+  }
+  return c;
+}
+
+// One training step's launches on stream s for a network with a conv part (convtrain.inc).
+static void launch_cnn_train_step(aigar_handle *h, hipStream_t s, int has_u) {
+  const Train &t = h->trn;
+  const ConvTrain &ct = h->ctrn;
+  const Exp &e = h->exp;
+  const Conv &cv = h->conv;
+  const Conv con = train_conv(cv, ct, t.bpad, false), ctg = train_conv(cv, ct, t.bpad, true);
+  const int nc = cv.n_conv, B = t.batch;
+  Net on = h->net;
+  on.x_dtype = 1;  // (the dense part reads the float32 feature rows)
+  const Net tg = target_net(on, t);
+  Train td = t;  // the dense part's view: its first layer's h is the feature row
+  td.s = (char *)ct.act[nc - 1];
+  launch_draw_fetch(h, s, t, has_u);
+  launch_conv(s, con, t.s, e.dtype, B, nullptr, nullptr);
+  launch_net_save(s, on, B, td.s, t.q, t.hsave);
+  launch_conv(s, ctg, t.s2, e.dtype, B, nullptr, nullptr);
+  launch_net(s, tg, ct.tact[nc - 1], B, t.q2, nullptr, nullptr);
+  hipLaunchKernelGGL(k_td, dim3(1), dim3(kTrainMaxBatch), 0, s, t, e, h->d, on.n_layers, on.out[on.n_layers - 1]);
+  // every reader of the weights ...
+  if (on.n_layers > 1)
+    hipLaunchKernelGGL(k_net_bwd, dim3((unsigned)(t.bpad / kNetRows)), dim3(64 * kNetWaves), 0, s, on, t);
+  {
+    const unsigned tiles = (unsigned)((cv.n_flat + 15) / 16);
+    hipLaunchKernelGGL(k_net_bwd_feat, dim3((tiles + kNetWaves - 1) / kNetWaves, (unsigned)(t.bpad / kNetRows)),
+                       dim3(64 * kNetWaves), 0, s, on, t, ct.act[nc - 1], ct.delta[nc - 1]);
+  }
+  for (int l = nc - 1; l >= 1; l--) {
+    ConvBwd L;
+    L.H = cv.osz[l - 1];
+    L.cin = cv.filters[l - 1];
+    L.k = cv.k[l];
+    L.stride = cv.stride[l];
+    L.O = cv.osz[l];
+    L.F = cv.filters[l];
+    L.K = L.k * L.k * L.F;
+    L.Fp = net_out_pad(L.F);
+    L.mF = conv_magic(L.F);
+    L.mk = conv_magic(L.k);
+    L.ms = conv_magic(L.stride);
+    L.mH = conv_magic(L.H);
+    const size_t M = (size_t)B * L.H * L.H;
+    const dim3 grid((unsigned)((M + 16 * kConvWaves - 1) / (16 * kConvWaves))), block(64 * kConvWaves);
+#define AIGAR_CONV_BWD(NT) \
+  hipLaunchKernelGGL((k_conv_bwd<NT>), grid, block, 0, s, L, t, ct.delta[l], cv.w[l], ct.act[l - 1], ct.delta[l - 1])
+    switch ((L.cin + 15) / 16) {
+      case 1: AIGAR_CONV_BWD(1); break;
+      case 2: AIGAR_CONV_BWD(2); break;
+      case 3: AIGAR_CONV_BWD(3); break;
+      default: AIGAR_CONV_BWD(4); break;
+    }
+#undef AIGAR_CONV_BWD
+  }
+  // ... before every kernel that updates them
+  hipLaunchKernelGGL(k_net_grad_adam<float>, dim3(t.tile0[on.n_layers]), dim3(64), 0, s, on, td);
+  if (e.dtype == 0) hipLaunchKernelGGL(k_conv_grad_adam<double>, dim3(ct.tile0[nc]), dim3(64), 0, s, cv, ct, t);
+  else hipLaunchKernelGGL(k_conv_grad_adam<float>, dim3(ct.tile0[nc]), dim3(64), 0, s, cv, ct, t);
+  if (e.prio) hipLaunchKernelGGL(k_exp_update, dim3(1), dim3(kExpPlanThreads), 0, s, e, t.idx, t.prio, B);
+  hipLaunchKernelGGL(k_conv_train_tail, dim3(16), dim3(256), 0, s, cv, ct, t);
+  hipLaunchKernelGGL(k_train_tail, dim3(64), dim3(256), 0, s, on, t);
+}
+
 extern "C" int aigar_train_step(aigar_handle *h, int n_steps, const double *u) {
   if (need_trn(h, "train_step")) return -1;
-  return trainer_step(h, "train_step", kTrainQ, n_steps, u, h->trn, launch_train_step);
+  return trainer_step(h, "train_step", kTrainQ, n_steps, u, h->trn, h->ctrn.on ? launch_cnn_train_step : launch_train_step);
 }
 
 extern "C" int aigar_train_info(aigar_handle *h, int64_t info[4]) {
@@ -2711,6 +2856,10 @@ extern "C" int aigar_train_sync_target(aigar_handle *h) {
   if (need_trn(h, "train_sync_target")) return -1;
   HIPCHK(hipSetDevice(h->cfg.device));
   if (target_copy(h, h->net, h->trn)) return -1;
+  for (int l = 0; h->ctrn.on && l < h->conv.n_conv; l++) {
+    HIPCHK(hipMemcpyAsync(h->ctrn.tw[l], h->conv.w[l], conv_w_bytes(h->conv, l), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->ctrn.tb[l], h->conv.b[l], conv_b_bytes(h->conv, l), hipMemcpyDeviceToDevice, h->stream));
+  }
   hipLaunchKernelGGL(k_train_clear, dim3(1), dim3(1), 0, h->stream, h->trn.ctl, 1);
   HIPCHK(hipGetLastError());
   return 0;
@@ -2720,6 +2869,13 @@ extern "C" int aigar_train_reset(aigar_handle *h) {
   if (need_trn(h, "train_reset")) return -1;
   HIPCHK(hipSetDevice(h->cfg.device));
   if (adam_clear(h, h->net, h->trn)) return -1;
+  for (int l = 0; h->ctrn.on && l < h->conv.n_conv; l++) {
+    const size_t nw = conv_w_bytes(h->conv, l), nb = conv_b_bytes(h->conv, l);
+    HIPCHK(hipMemsetAsync(h->ctrn.mw[l], 0, nw, h->stream));
+    HIPCHK(hipMemsetAsync(h->ctrn.vw[l], 0, nw, h->stream));
+    HIPCHK(hipMemsetAsync(h->ctrn.mb[l], 0, nb, h->stream));
+    HIPCHK(hipMemsetAsync(h->ctrn.vb[l], 0, nb, h->stream));
+  }
   hipLaunchKernelGGL(k_train_clear, dim3(1), dim3(1), 0, h->stream, h->trn.ctl, 0);
   HIPCHK(hipGetLastError());
   return 0;
@@ -3222,7 +3378,6 @@ extern "C" int aigar_net_get_weights(aigar_handle *h, int which, int layer, floa
   const float *wp, *bp;
   const Net *np;
   if (net_which(h, "net_get_weights", which, layer, &np, &wp, &bp)) return -1;
-  if (h->conv.n_conv) return fail("net_get_weights: a network with a conv part has no read-back");
   if (!W || !b) return fail("net_get_weights: null argument");
   HIPCHK(hipSetDevice(h->cfg.device));
   const int in = np->in[layer], out = np->out[layer];
@@ -3235,6 +3390,41 @@ extern "C" int aigar_net_get_weights(aigar_handle *h, int which, int layer, floa
   if (!on_device) {
     HIPCHK(hipMemcpyAsync(W, dW, nw * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(b, db, (size_t)out * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  return 0;
+}
+
+// The conv part's read-back: which 0 online, 1 target, 2 Adam's m, 3 Adam's v (the last three need
+// aigar_train_config_cnn); W [k][k][cin][F], b [F] in Keras' layout.
+static int conv_which(aigar_handle *h, const char *who, int which, int layer, const float **wp, const float **bp) {
+  if (need_net(h, who)) return -1;
+  const Conv &c = h->conv;
+  if (!c.n_conv) return fail("%s: the network has no conv part (aigar_net_config_cnn)", who);
+  if (which < 0 || which > 3) return fail("%s: which = %d is outside 0..3", who, which);
+  if (layer < 0 || layer >= c.n_conv) return fail("%s: layer %d is outside 0..%d", who, layer, c.n_conv - 1);
+  if (which && !h->ctrn.on) return fail("%s: no CNN training is configured (aigar_train_config_cnn)", who);
+  const ConvTrain &t = h->ctrn;
+  *wp = which == 0 ? c.w[layer] : which == 1 ? t.tw[layer] : which == 2 ? t.mw[layer] : t.vw[layer];
+  *bp = which == 0 ? c.b[layer] : which == 1 ? t.tb[layer] : which == 2 ? t.mb[layer] : t.vb[layer];
+  return 0;
+}
+
+extern "C" int aigar_net_get_conv_weights(aigar_handle *h, int which, int layer, float *W, float *b, int on_device) {
+  const float *wp, *bp;
+  if (conv_which(h, "net_get_conv_weights", which, layer, &wp, &bp)) return -1;
+  if (!W || !b) return fail("net_get_conv_weights: null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const Conv &c = h->conv;
+  const int K = c.k[layer] * c.k[layer] * (layer ? c.filters[layer - 1] : c.channels), F = c.filters[layer];
+  const size_t nw = (size_t)K * F;
+  float *dW = on_device ? W : h->conv_stage, *db = on_device ? b : h->conv_stage + nw;
+  hipLaunchKernelGGL(k_conv_unpack, dim3((unsigned)std::min<size_t>((nw + 255) / 256, 4096)), dim3(256), 0, h->stream, wp, bp,
+                     dW, db, K, F, net_out_pad(F));
+  HIPCHK(hipGetLastError());
+  if (!on_device) {
+    HIPCHK(hipMemcpyAsync(W, dW, nw * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(b, db, (size_t)F * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
   }
   return 0;
@@ -3254,6 +3444,16 @@ extern "C" int aigar_net_pad_check(aigar_handle *h, int which, int64_t *count) {
     const int in = np->in[l], out = np->out[l], ip = net_in_pad(in), op = net_out_pad(out);
     hipLaunchKernelGGL(k_net_pad_count, dim3((unsigned)std::min<size_t>(((size_t)ip * op + 255) / 256, 4096)), dim3(256), 0,
                        h->stream, wp, bp, in, out, ip, op, dc);
+    er = hipGetLastError();
+  }
+  // the conv part's copies of the acting network: the same code's (1 .. 3: under aigar_train_config_cnn)
+  for (int l = 0; which < 4 && (which == 0 || h->ctrn.on) && l < h->conv.n_conv && er == hipSuccess; l++) {
+    const float *cw, *cb;
+    (void)conv_which(h, "net_pad_check", which, l, &cw, &cb);
+    const Conv &c = h->conv;
+    const int K = c.k[l] * c.k[l] * (l ? c.filters[l - 1] : c.channels), F = c.filters[l], Kp = conv_k_pad(K), Fp = net_out_pad(F);
+    hipLaunchKernelGGL(k_net_pad_count, dim3((unsigned)std::min<size_t>(((size_t)Kp * Fp + 255) / 256, 4096)), dim3(256), 0,
+                       h->stream, cw, cb, K, F, Kp, Fp, dc);
     er = hipGetLastError();
   }
   if (er == hipSuccess) er = hipMemcpyAsync(&n, dc, sizeof n, hipMemcpyDeviceToHost, h->stream);

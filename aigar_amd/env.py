@@ -128,7 +128,11 @@ With a pixel state (`pixels=` or CNN_REPR and CNN_P_REPR) the network is the ref
 (DESIGN.md §4k): `network=True` builds a CnnSpec from `parameters` (aigar_amd.net.cnn_spec: CNN_L1/2/3,
 CNN_USE_L1/2/3 and the dense settings above), a CnnSpec overrides it; the conv layers run on the
 device too, in the same graph, and `set_weights` takes the conv pairs first (a torch module of
-nn.Conv2d and nn.Linear layers is converted, aigar_amd.net.cnn_weights_from_torch).
+nn.Conv2d and nn.Linear layers is converted, aigar_amd.net.cnn_weights_from_torch).  With
+`discrete=`, `memory=` and `train=` the CNN is trained on the device as the MLP is (DESIGN.md §4p:
+the conv layers' backward pass and Adam on the packed filters, in the step's graph); `get_weights()`
+then returns the conv pairs first (aigar_amd.net.cnn_weights_to_torch).  With `continuous=` a pixel
+state is not trained on the device.
 """
 import collections
 
@@ -400,11 +404,13 @@ class AgarVecEnv:
             row = _TRAINERS[kind]
             if getattr(self, row.needs) is None or self.network is None or self.memory is None:
                 raise ValueError(row.refusal)
-            if self.pixels is not None or hasattr(self.network, "convs"):
+            cnn = self.pixels is not None or hasattr(self.network, "convs")
+            if cnn and kind != "train":  # (Q-learning alone trains a conv part: DESIGN.md §4p)
                 raise ValueError("train=: CNN / pixel states are not trained on the device")
             # the trainer's settings: the parameters' own with the memory's batch, then the
             # overrides of a train= dict, whose "algorithm" key is no setting
-            tp = row.settings(parameters)
+            # (the CNN Q-learner: CNN_REPR is what train_params refuses for the other settings' sake)
+            tp = row.settings(_net._Dense(parameters) if cnn and parameters is not None else parameters)
             tp["batch"] = int(self.memory["batch"])
             if isinstance(train, dict):
                 own = {k: v for k, v in train.items() if k != "algorithm"}
@@ -429,7 +435,7 @@ class AgarVecEnv:
                 self.critic = cs
                 getattr(self.stepper, row.critic_config)(cs, self.obs.dtype)
             self.training, self._trainer = tp, kind
-            getattr(self.stepper, kind + "_config")(**tp)
+            getattr(self.stepper, kind + ("_config_cnn" if cnn else "_config"))(**tp)
         self.cacla = self._trainer == "actrain"  # (the trainer is the CACLA learner's: DESIGN.md §4m)
         self.dpg = self._trainer == "dpg"  # (... the DPG learner's: §4n)
         self.spg = self._trainer == "spg"  # (... the SPG learner's, on the DPG learner's critic: §4o)
@@ -469,6 +475,11 @@ class AgarVecEnv:
             u = torch.as_tensor(u, dtype=torch.float64, device=self.dev).reshape(n, self.training["batch"]).contiguous()
         self._ordered(getattr(self.stepper, self._trainer + "_step"), n, u)  # (u is freed when this returns)
 
+    def sync_target(self):
+        """The trainer's target network(s) <- the online one(s) now (aigar_*_sync_target)."""
+        self._need_training()
+        self._ordered(getattr(self.stepper, self._trainer + "_sync_target"))
+
     def train_info(self):
         """{steps, skipped, since_target} (aigar_train_info: a host round trip); the CACLA trainer's
         also has actor_epochs, selected, epochs, cut and epochs_skipped (aigar_actrain_info), the
@@ -489,10 +500,9 @@ class AgarVecEnv:
     def get_weights(self, target=False):
         """The acting network's dense weights as [(W [in, out], b [out])] float32 numpy arrays
         (Keras' layout; aigar_amd.net.weights_to_torch loads them into a module); target=True:
-        the trainer's target network."""
+        the trainer's target network.  With a conv part its pairs (W [k, k, Cin, F], b [F]) come
+        first (aigar_amd.net.cnn_weights_to_torch loads the list into a module)."""
         self._need_network()
-        if hasattr(self.network, "convs"):
-            raise RuntimeError("get_weights: a network with a conv part has no read-back")
         if target:
             self._need_training()
         return self._ordered(self.stepper.net_get_weights, "target" if target else "online")

@@ -264,6 +264,52 @@ def weights_to_torch(weights, module):
     return module
 
 
+def cnn_weights_to_torch(pairs, spec, module=None):
+    """The inverse of cnn_weights_from_torch: the conv pairs (W [k, k, Cin, F], b [F]) first, then
+    the dense pairs (W [in, out], b [out]), numpy arrays or tensors in Keras' layout, for a
+    CnnSpec -> an ordered state dict {"conv0.weight": [F, Cin, k, k], "conv0.bias", ...,
+    "fc0.weight": [out, in], "fc0.bias", ...} of float32 tensors, the first Linear's input
+    permuted from the device's (y, x, c) order back to the (c, y, x) order of a torch Flatten of
+    NCHW.  With a module, its nn.Conv2d and nn.Linear layers, in order, are loaded instead and
+    the module is returned."""
+    import collections
+    import torch
+    pairs = [(np.asarray(_np(W), np.float32), np.asarray(_np(b), np.float32)) for W, b in pairs]
+    nc = len(spec.convs)
+    if len(pairs) != nc + len(spec.units):
+        raise ValueError("cnn_weights_to_torch: %d pairs given, the spec has %d conv and %d dense layers"
+                         % (len(pairs), nc, len(spec.units)))
+    cnn_weights_from_torch(pairs, spec)  # (the shapes)
+    out = collections.OrderedDict()
+    for l, (W, b) in enumerate(pairs):
+        if l < nc:
+            w, name = W.transpose(3, 2, 0, 1), "conv%d" % l
+        else:
+            if l == nc:
+                f = spec.convs[-1][2]
+                o = conv_out_side(spec.side, spec.convs)[-1]
+                W = W.reshape(o, o, f, W.shape[1]).transpose(2, 0, 1, 3).reshape(f * o * o, W.shape[1])
+            w, name = W.T, "fc%d" % (l - nc)
+        out[name + ".weight"] = torch.as_tensor(np.ascontiguousarray(w))
+        out[name + ".bias"] = torch.as_tensor(np.ascontiguousarray(b))
+    if module is None:
+        return out
+    layers = [m for m in module.modules() if isinstance(m, (torch.nn.Conv2d, torch.nn.Linear))]
+    if len(layers) != len(pairs):
+        raise ValueError("cnn_weights_to_torch: %d pairs given, the module has %d nn.Conv2d / nn.Linear"
+                         % (len(pairs), len(layers)))
+    with torch.no_grad():
+        for m, name in zip(layers, list(out)[0::2]):
+            w, b = out[name], out[name[:-len("weight")] + "bias"]
+            if tuple(w.shape) != tuple(m.weight.shape):
+                raise ValueError("cnn_weights_to_torch: %s is %s, the layer's weight %s"
+                                 % (name, tuple(w.shape), tuple(m.weight.shape)))
+            m.weight.copy_(w.to(m.weight))
+            if m.bias is not None:
+                m.bias.copy_(b.to(m.bias))
+    return module
+
+
 def train_params(parameters=None):
     """The device trainer's settings from the reference's parameters: Q-learning
     with Keras' Adam, what qLearning.py and network.py do by default.  Everything else the

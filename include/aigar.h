@@ -754,6 +754,40 @@ int aigar_train_sync_target(aigar_handle *h);
 int aigar_train_reset(aigar_handle *h);
 int aigar_net_get_weights(aigar_handle *h, int which, int layer, float *W, float *b, int on_device);
 int aigar_net_pad_check(aigar_handle *h, int which, int64_t *count);
+/* The Q-learning trainer of an acting network with a conv part (the pixel learner: CNN_REPR with
+ * CNN_P_REPR; tests/cnn_train_model.py is the specification in plain Python, on
+ * tests/conv_model.py and tests/train_model.py).  One step is the step above with the conv
+ * layers around the dense part, in place on the packed filters and kernels the decision acts
+ * with; s and s2 are images [side][side][channels] of the memory's dtype:
+ *   every conv layer's post-relu output a_l is kept; feat = a_last flattened in (y, x, f) order is
+ *   the dense part's float32 input, and the first dense layer's gradient is taken with h = feat;
+ *   q2 comes from the target network, conv part included, on s2;
+ *   e[r][i] = ONE float32 fmaf chain from +0.0f over ascending unit j of delta_1[r][j] W_dense0[i][j];
+ *   delta_conv_last = e where feat > 0, else +0.0f, as [B][O][O][F];
+ *   dW_l[ky][kx][c][f] = ONE fmaf chain from +0.0f over ascending m = (r O + oy) O + ox of
+ *   h_{l-1}[r][oy s + ky][ox s + kx][c] delta_l[r][oy][ox][f]; db_l[f] = the plain float32 sum of
+ *   delta_l[m][f] over ascending m;
+ *   for l >= 2, e_{l-1}[r][iy][ix][c] = ONE chain from +0.0f over ALL k k F taps in ascending
+ *   (ky k + kx) F + f of fmaf(x, W_l[ky][kx][c][f], acc) with x = delta_l[r][(iy - ky) / s][(ix - kx) / s][f]
+ *   when both differences are >= 0, divisible by s and their quotients < O, else x = -0.0f (the
+ *   padded steps are executed); delta_{l-1} = e where a_{l-1} > 0, else +0.0f;
+ *   Adam on every conv W and b as on the dense ones, one lr_t and one t; every gradient is taken
+ *   with the weights as they were before the step; the hard target copy takes the filters as well.
+ * The skip rules, the warn bit and the counters are the dense trainer's.
+ *
+ * aigar_train_config_cnn: the same parameters, checked before the handle with the same messages
+ * under its own name.  It needs an acting network with a conv part (aigar_net_config_cnn; on a
+ * dense one it refuses and names aigar_train_config) and a linear head, a replay memory whose
+ * state length is side * side * channels, and no tiled handle.  NULL turns it off.  It is dropped
+ * by what drops a train configuration.  aigar_train_config on a network with a conv part is
+ * refused as before.  aigar_train_step, aigar_train_info, aigar_train_td, aigar_train_sync_target
+ * and aigar_train_reset serve both configurations.
+ * aigar_net_get_conv_weights: conv layer's W[k][k][cin][F] and b[F] in Keras' layout, into host or
+ * (on_device) DEVICE buffers; which as aigar_net_get_weights' 0..3 (1..3 need this configuration).
+ * aigar_net_get_weights on such a network reads the dense layers; aigar_net_pad_check counts the
+ * conv copies' padding too. */
+int aigar_train_config_cnn(aigar_handle *h, const aigar_train_params *p);
+int aigar_net_get_conv_weights(aigar_handle *h, int which, int layer, float *W, float *b, int on_device);
 /* The CACLA learner's critic and trainer on the device (actorCritic.py ActorCritic.learn for
  * ALGORITHM == "CACLA": train_critic 1032-1065, train_actor_batch 791-858, the critic's hard
  * target copy 745-746; tests/cacla_model.py is the specification in plain Python).
